@@ -9,6 +9,12 @@
 One step = one quantized forward (fp32 images resident in HBM -> int8-grid logits) over one batch of 256
 synthetic images per GPU, followed -- when N>1 -- by the single RCCL all-gather of the logits
 (SURVEY.md 8e).  Weak scaling: per-GPU batch fixed.  Prints ONE JSON line on rank 0.
+
+A plain run sets up (weights, host calibration, plan), runs W warm-up steps, times ONE loop of exactly K steps and prints the line
+(`value`, `ms_per_step`, what ran).  --full adds what the headline does not need: 5 timed loops (median), top-1 against the fp32
+model, the calibration against the reference fixture, the gathered logits against per-rank forwards, the roofline and per-kernel
+profile, the CPU baseline.  --dump-outputs DIR writes the logits of the last timed step (DIR/logits.npy, float32); weights, images and
+calibration come from fixed seeds, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -67,7 +73,8 @@ def bench_swin(args, dva, dev, world, rank):
     arch = model.arch
     base = dva.synth.images(1000 + rank, args.batch, arch['img_size'])
     with torch.no_grad():
-        fp32_top1 = model(base.to(dev)).argmax(1).cpu()
+        if args.full:
+            fp32_top1 = model(base.to(dev)).argmax(1).cpu()
         t_cal = time.perf_counter()
         dva.harness.calibrate_model(model, dva.synth.images(SEED, 2, arch['img_size']).to(dev))
         torch.cuda.synchronize()
@@ -88,6 +95,16 @@ def bench_swin(args, dva, dev, world, rank):
         step()
     times = timed_repeats(step, args.steps, args.repeats, world, dev, dist)
     el = times[len(times) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gat[0])
+    line = headline(args, world, B, times, 'images/sec %s (quantized forward)' % args.model,
+                    '%s PoT-PTQ forward, int%d weights, %dx%d, batch %d per GPU' % (args.model, args.bits, arch['img_size'], arch['img_size'], B))
+    line['config'].update({'streams_per_gpu': args.streams, 'side_streams': dva.engine.SIDE_STREAM_REPORT.get(dev.index),
+                           'collective': 'all_gather(logits)' if dist is not None else 'none', 'backend': args.backend if dist is not None else None,
+                           **args.identity})
+    calibration = {'seconds': round(t_cal, 2), 'device': 'gpu'}
+    if not args.full:
+        return finish(dict(line, calibration=calibration), rank, dist)
     # roofline of the dominant op kind: one launch = one stream slice, timed by p2v_run_ops_profile (HIP events on the launch stream)
     n_sl = len(sw_slices) if sw_slices else (args.streams if (args.streams > 1 and B >= 16 * args.streams) else 1)
     Bl = max(sw_slices) if sw_slices else (B + n_sl - 1) // n_sl
@@ -107,24 +124,46 @@ def bench_swin(args, dva, dev, world, rank):
     roof = dict(kernel=dom, bound='mfma', achieved=round(ach, 2), peak=PEAK_INT8_TOPS, unit='TFLOP/s', frac=round(ach / PEAK_INT8_TOPS, 4),
                 avg_launch_us=round(ms_l / n_l * 1e3, 2), launches_per_step=n_sl * n_l, images_per_launch=Bl, traffic=None)
     model_ops = n_sl * sum(v[2] for v in kinds.values())
+    finish(dict(line, **{
+        'roofline': roof,
+        'top1_agreement_fp32': round(float((out[0][:base.shape[0]].argmax(1).cpu() == fp32_top1).float().mean()), 4),
+        'model_mfma_frac': round(model_ops / (el / args.steps) / 1e12 / PEAK_INT8_TOPS, 4),
+        'kernel_ms_per_step': {k: round(n_sl * v[1], 3) for k, v in sorted(kinds.items(), key=lambda kv: -kv[1][1])},
+        'cpu_baseline': None, 'calibration': calibration,
+    }), rank, dist)
+
+
+def headline(args, world, B, times, metric, workload):
+    """The part of the JSON line every run prints: the timed steps and what ran.  `times`: sorted seconds per timed loop."""
+    el = times[len(times) // 2]                                      # median loop
+    return {
+        'metric': metric, 'value': round(world * B * args.steps / el, 1), 'unit': 'images/sec',
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(el / args.steps * 1e3, 3),
+        'repeats': args.repeats, 'ms_per_step_min_max': [round(times[0] / args.steps * 1e3, 3), round(times[-1] / args.steps * 1e3, 3)],
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'int8' if args.bits == 8 else 'int4w/int8a', 'data': 'synthetic',
+        'config': {'workload': workload, 'global_batch': world * B, 'parallelism': 'dp%d' % world},
+    }
+
+
+def finish(line, rank, dist):
     if rank == 0:
-        print(json.dumps({
-            'metric': 'images/sec %s (quantized forward)' % args.model, 'value': round(world * B * args.steps / el, 1), 'unit': 'images/sec',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(el / args.steps * 1e3, 3),
-            'repeats': args.repeats, 'ms_per_step_min_max': [round(times[0] / args.steps * 1e3, 3), round(times[-1] / args.steps * 1e3, 3)],
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'int8' if args.bits == 8 else 'int4w/int8a', 'data': 'synthetic',
-            'config': {'workload': '%s PoT-PTQ forward, int%d weights, %dx%d, batch %d per GPU' % (args.model, args.bits, arch['img_size'], arch['img_size'], B),
-                       'global_batch': world * B, 'parallelism': 'dp%d' % world, 'streams_per_gpu': args.streams, 'side_streams': dva.engine.SIDE_STREAM_REPORT.get(dev.index),
-                       'collective': 'all_gather(logits)' if dist is not None else 'none', 'backend': args.backend if dist is not None else None,
-                       **args.identity},
-            'roofline': roof,
-            'top1_agreement_fp32': round(float((out[0][:base.shape[0]].argmax(1).cpu() == fp32_top1).float().mean()), 4),
-            'model_mfma_frac': round(model_ops / (el / args.steps) / 1e12 / PEAK_INT8_TOPS, 4),
-            'kernel_ms_per_step': {k: round(n_sl * v[1], 3) for k, v in sorted(kinds.items(), key=lambda kv: -kv[1][1])},
-            'cpu_baseline': None, 'calibration': {'seconds': round(t_cal, 2), 'device': 'gpu'},
-        }))
+        print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, logits):
+    """--dump-outputs: DIR/logits.npy, float32, one row per image.  Above DUMP_MAX_BYTES only a fixed, seeded sample of the rows is
+    written (in row order), the same rows in every run with the same arguments."""
+    import numpy as np
+    a = logits.float().cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        a = a[np.sort(np.random.RandomState(0).choice(len(a), DUMP_MAX_BYTES // a[0].nbytes, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'logits.npy'), a)
 
 
 def spawn_ranks(n):
@@ -169,7 +208,7 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--repeats', type=int, default=5, help='timed loops of --steps steps; the value is the median loop')
+    ap.add_argument('--repeats', type=int, default=None, help='timed loops of --steps steps; the value is the median loop (default: 1, with --full 5)')
     ap.add_argument('--batch', type=int, default=BATCH, help='images per GPU (BASELINE config 2: 256)')
     ap.add_argument('--bits', type=int, default=8, choices=(4, 8))
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -181,7 +220,14 @@ def main():
                     'says so in config.devices / distinct_devices).  Without it such a launch exits non-zero instead of printing an "N-GPU" number')
     ap.add_argument('--force-dist', action='store_true', help='initialise the process group and run the all-gather of the logits even at '
                     'world size 1 (under torch.distributed.run --nproc-per-node 1): exercises the RCCL branch on a one-GPU box')
+    ap.add_argument('--full', action='store_true', help='also measure and check what the headline does not need: 5 timed loops, top-1 against '
+                    'the fp32 model, calibration against the reference fixture, the gathered logits against per-rank forwards, the roofline '
+                    'and per-kernel profile, the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write the logits of the last step as DIR/logits.npy '
+                    '(float32; rank 0: the gathered logits of all ranks)')
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus)
@@ -249,20 +295,14 @@ def main():
     model.load_state_dict(sd, strict=False)
     model = model.to(dev).eval()
     base = dva.synth.images(1000 + rank, args.batch, arch['img_size'])
-    with torch.no_grad():                                 # fp32 teacher on the distinct images, before any calibration
-        fp32_top1 = model(base.to(dev))[0].argmax(1).cpu()
+    if args.full:
+        with torch.no_grad():                             # fp32 teacher on the distinct images, before any calibration
+            fp32_top1 = model(base.to(dev))[0].argmax(1).cpu()
     t_cal = time.perf_counter()
     dva.harness.calibrate_model(model, dva.synth.images(SEED, 2, arch['img_size']).to(dev), where='host')    # exact exponents (harness.py)
     torch.cuda.synchronize()
     t_cal = time.perf_counter() - t_cal
     calib = model.export_calib()
-    mine = calib_io.flatten(calib)
-    ref_calib = calib_io.flatten(calib_io.load_npz(os.path.join(ROOT, 'tests', 'golden', 'deit_small.npz'))) if args.model == MODEL else mine
-    # agreement with the REAL reference's calibration of the same weights/batch (float pass: expect ulp-level noise in the
-    # PTF base scales and, on near-ties of the per-channel MSE search, an occasional exponent one step away)
-    n_equal = sum(int(torch.equal(mine[k].reshape(-1), ref_calib[k].reshape(-1))) for k in ref_calib)
-    exp_flips = sum(int((torch.log2(mine[k].reshape(-1) / ref_calib[k].reshape(-1)).abs() > 0.5).sum()) for k in ref_calib)
-    n_elems = sum(ref_calib[k].numel() for k in ref_calib)
     plan = model.freeze(dev)
     B = args.batch
     # every image of the batch is distinct (counter-based generator, seed 1000 + rank)
@@ -287,7 +327,23 @@ def main():
         step()
     times = timed_repeats(step, args.steps, args.repeats, world, dev, dist)
     el = times[len(times) // 2]                                      # median loop
-    value = world * B * args.steps / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out[0])
+    line = headline(args, world, B, times, 'images/sec DeiT-S int8 224^2 b=256 (quantized forward)' if args.model == MODEL else 'images/sec %s (quantized forward)' % args.model,
+                    args.model + ' PoT-PTQ forward, bit_config=[%d]*50, 224x224, batch %d per GPU' % (args.bits, B))
+    line['config'].update({'streams_per_gpu': args.streams, 'side_streams': dva.engine.SIDE_STREAM_REPORT.get(dev.index), 'batch_slices': slices,
+                           'collective': 'all_gather(logits)' if dist is not None else 'none', 'backend': args.backend if dist is not None else None})
+    calibration = {'seconds': round(t_cal, 2), 'device': 'host cpu (float pass + observer searches; harness.calibrate_model where=host)'}
+    if not args.full:
+        line['config'].update(args.identity)
+        return finish(dict(line, calibration=calibration), rank, dist)
+    mine = calib_io.flatten(calib)
+    ref_calib = calib_io.flatten(calib_io.load_npz(os.path.join(ROOT, 'tests', 'golden', 'deit_small.npz'))) if args.model == MODEL else mine
+    # agreement with the REAL reference's calibration of the same weights/batch (float pass: expect ulp-level noise in the
+    # PTF base scales and, on near-ties of the per-channel MSE search, an occasional exponent one step away)
+    n_equal = sum(int(torch.equal(mine[k].reshape(-1), ref_calib[k].reshape(-1))) for k in ref_calib)
+    exp_flips = sum(int((torch.log2(mine[k].reshape(-1) / ref_calib[k].reshape(-1)).abs() > 0.5).sum()) for k in ref_calib)
+    n_elems = sum(ref_calib[k].numel() for k in ref_calib)
     gather_ok = None
     if dist is not None:
         # the gathered tensor holds every rank's logits: rank 0 recomputes each shard itself (rank r's images come from seed 1000 + r)
@@ -458,32 +514,21 @@ def main():
                           'host has %d hardware threads' % (nb, ts[1], best_th, n_host),
                    logits_equal_gpu=same)
 
-    if rank == 0:
-        print(json.dumps({
-            'metric': 'images/sec DeiT-S int8 224^2 b=256 (quantized forward)' if args.model == MODEL else 'images/sec %s (quantized forward)' % args.model, 'value': round(value, 1), 'unit': 'images/sec',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(el / args.steps * 1e3, 3),
-            'repeats': args.repeats, 'ms_per_step_min_max': [round(times[0] / args.steps * 1e3, 3), round(times[-1] / args.steps * 1e3, 3)],
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'int%d' % args.bits if args.bits == 8 else 'int4w/int8a',
-            'data': 'synthetic',
-            'config': {'workload': args.model + ' PoT-PTQ forward, bit_config=[%d]*50, 224x224, batch %d per GPU' % (args.bits, B),
-                       'global_batch': world * B, 'parallelism': 'dp%d' % world, 'streams_per_gpu': args.streams, 'side_streams': dva.engine.SIDE_STREAM_REPORT.get(dev.index), 'batch_slices': slices,
-                       'collective': 'all_gather(logits)' if dist is not None else 'none', 'backend': args.backend if dist is not None else None,
-                       'gathered_logits_equal_per_rank_forwards': gather_ok, **args.identity},
-            'roofline': roof,
-            'top1_agreement_fp32': round(top1_fp32, 4),
-            'model_mfma_frac': round(model_ops / (el / args.steps) / 1e12 / PEAK_INT8_TOPS, 4),
-            'kernel_ms_per_step': breakdown,
-            'kernel_us_per_launch': {k: {'isolated': round(iso[k]['median'] * 1e3, 2), 'under_overlap': round(ovl[k]['median'] * 1e3, 2) if k in ovl else None,
-                                         'share_under_overlap': round(tot_ovl[k] / sum(tot_ovl.values()), 3) if k in tot_ovl else None}
-                                     for k in sorted(iso, key=lambda k: -tot_ovl.get(k, 0.0))},
-            'overlap': {'longest_stream_ms_with_events': ovl_wall, 'note': 'medians over all launches; under_overlap = launch duration while the other slices '
-                        'run (HIP events on each stream, FrozenPlan.profile_streams); isolated = one slice alone'} if ovl else None,
-            'cpu_baseline': cpu,
-            'calibration': {'seconds': round(t_cal, 2), 'device': 'host cpu (float pass + observer searches; harness.calibrate_model where=host)', 'tensors': len(ref_calib), 'tensors_bit_equal_reference': n_equal,
-                            'scale_elements': n_elems, 'elements_off_by_a_power_of_two': exp_flips},
-        }))
-    if dist is not None:
-        dist.destroy_process_group()
+    line['config'].update({'gathered_logits_equal_per_rank_forwards': gather_ok, **args.identity})
+    finish(dict(line, **{
+        'roofline': roof,
+        'top1_agreement_fp32': round(top1_fp32, 4),
+        'model_mfma_frac': round(model_ops / (el / args.steps) / 1e12 / PEAK_INT8_TOPS, 4),
+        'kernel_ms_per_step': breakdown,
+        'kernel_us_per_launch': {k: {'isolated': round(iso[k]['median'] * 1e3, 2), 'under_overlap': round(ovl[k]['median'] * 1e3, 2) if k in ovl else None,
+                                     'share_under_overlap': round(tot_ovl[k] / sum(tot_ovl.values()), 3) if k in tot_ovl else None}
+                                 for k in sorted(iso, key=lambda k: -tot_ovl.get(k, 0.0))},
+        'overlap': {'longest_stream_ms_with_events': ovl_wall, 'note': 'medians over all launches; under_overlap = launch duration while the other slices '
+                    'run (HIP events on each stream, FrozenPlan.profile_streams); isolated = one slice alone'} if ovl else None,
+        'cpu_baseline': cpu,
+        'calibration': dict(calibration, **{'tensors': len(ref_calib), 'tensors_bit_equal_reference': n_equal,
+                                            'scale_elements': n_elems, 'elements_off_by_a_power_of_two': exp_flips}),
+    }), rank, dist)
 
 
 if __name__ == '__main__':

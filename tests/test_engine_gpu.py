@@ -1420,7 +1420,7 @@ def test_bench_two_ranks_on_one_gpu_gloo(dva):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1',
-           '--repeats', '2', '--batch', '12', '--model', 'deit_tiny', '--no-cpu-baseline']
+           '--repeats', '2', '--batch', '12', '--model', 'deit_tiny', '--full', '--no-cpu-baseline']
     if torch.cuda.device_count() < 2:
         # more ranks than GPUs without the rehearsal flag: a loud refusal before anything touches the GPU, never an "N-GPU" number
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
@@ -1454,7 +1454,7 @@ def test_bench_rccl_branch_on_one_gpu(dva):
         port = sk.getsockname()[1]
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                         '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '1', '--backend', 'nccl', '--force-dist',
-                        '--steps', '2', '--warmup', '1', '--repeats', '2', '--batch', '24', '--model', 'deit_tiny', '--no-cpu-baseline'],
+                        '--steps', '2', '--warmup', '1', '--repeats', '2', '--batch', '24', '--model', 'deit_tiny', '--full', '--no-cpu-baseline'],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -1466,6 +1466,31 @@ def test_bench_rccl_branch_on_one_gpu(dva):
     assert c['ranks_seen'] == 1 and c['distinct_devices'] == 1 and len(c['devices']) == 1 and c['shared_device_rehearsal'] is False
     assert c['gpu_max_hw_queues']['in_effect'] is True
     assert d['roofline']['dominant_by'] and d['roofline']['launch_us']['median'] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(dva, tmp_path):
+    """a plain bench run times exactly --steps steps in one loop and measures nothing beyond the headline; --dump-outputs writes the
+    logits of the last timed step, and a --full run with the same arguments writes the same logits (seeded weights, images, calibration)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    lines, dumps = [], []
+    for extra in ([], ['--full', '--no-cpu-baseline']):
+        d = str(tmp_path / ('full' if extra else 'plain'))
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '12',
+                            '--model', 'deit_tiny', '--dump-outputs', d] + extra, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+        dumps.append(np.load(os.path.join(d, 'logits.npy')))
+    plain, full = lines
+    assert plain['steps'] == 3 and plain['repeats'] == 1 and plain['ms_per_step'] > 0 and plain['value'] > 0
+    assert plain['unit'] == 'images/sec' and plain['higher_is_better'] is True and plain['dtype'] == 'int8'
+    assert 'roofline' not in plain and 'cpu_baseline' not in plain and 'top1_agreement_fp32' not in plain
+    assert full['repeats'] == 5 and 'roofline' in full and full['metric'] == plain['metric']
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (12, 1000) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 @pytest.mark.parametrize('M,K,N', [(777, 128, 256), (1000, 448, 384), (261, 768, 128)])

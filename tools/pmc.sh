@@ -1,11 +1,11 @@
 #!/bin/bash
 # rocprofv3 PMC passes over a short single-stream bench run at the launch size of the default bench (one slice of the default run, PMC_BATCH images:
 # the same kernels and shapes as the sliced run, without a concurrent kernel polluting the counters) (counters in their own runs: no trace domains besides kernel-trace)
-# usage (GPU box): [PMC_MODEL=deit_small] [PMC_BATCH=86] [PMC_BITS=8] bash tools/pmc.sh
+# usage (GPU box): PMC_OUT=<output dir> [PMC_MODEL=deit_small] [PMC_BATCH=86] [PMC_BITS=8] bash tools/pmc.sh
 set -e
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-OUT=$R/gpurun_out/pmc
+OUT=$(realpath -m "${PMC_OUT:?set PMC_OUT to the output directory}")
 rm -rf $OUT
 mkdir -p $OUT
 run() { name=$1; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --streams 1 --model ${PMC_MODEL:-deit_small} --bits ${PMC_BITS:-8} --batch ${PMC_BATCH:-86} > $OUT/$name.log 2>&1 || tail -5 $OUT/$name.log; }
