@@ -1,0 +1,219 @@
+"""CKA model diff: layer-wise similarity heat maps between two models (the reference's own analysis, cka_utility.py, efficient_CKA.py,
+DDV_CKA.py), on the fused engine.
+
+    get_activations(images, model, bit_config, device, normalize_act=False, layer_indices=None)     cka_utility.py:26-113
+    MinibatchCKA(num_layers, num_layers2=None, across_models=False, dtype=torch.float32)           efficient_CKA.py
+    MinibatchAdvCKA(...)                                                                            DDV_CKA.py
+    compute_cka(model1, model2, batches, bit_config1, bit_config2, normalize_act=False)           float vs quantized heat map
+
+On a fused model (``model_quant()`` state) ``get_activations`` makes ONE ``p2v_forward_linear_taps`` call: its forward hooks on
+QConv2d / QLinear are fed by the engine (``VisionTransformer._forward_hooked``).  Otherwise (float model, ``-1`` entries, dequant) the
+module graph runs with the hooks, as in the reference.  The CKA classes send GPU activations through the HIP kernels
+(``torch.ops.p2vit.cka_grams`` / ``hsic_accumulate``: one grouped Gram launch sequence for all layers of an update) and CPU
+activations through ``gram_matrix``, a plain-torch restatement of the same formula.
+
+``python -m diff_vit_amd.cka --model deit_small --bits 8 --batch 50 --iters 2`` writes ``<result-name>/_heatmap.pkl`` (float vs
+quantized on the synthetic data of ``harness``)."""
+import argparse
+import copy
+import os
+import pickle
+
+import torch
+
+from . import ops  # noqa: F401  (registers torch.ops.p2vit.*)
+from .ptq import QConv2d, QLinear
+from .vit import Attention, Mlp
+
+
+def normalize_activations(act):
+    """cka_utility.py:6-21 (reshape instead of view: the patch-embed tap of the engine is a permuted view)."""
+    act = act.reshape(act.size(0), -1)
+    return act / (torch.norm(act, p=2, dim=1, keepdim=True) + 1e-8)
+
+
+def get_activations(images, model, bit_config, device, normalize_act=False, layer_indices=None):
+    """cka_utility.py:26-113: the outputs of every QConv2d / QLinear (and, without a bit_config, Attention.qkv_output /
+    Mlp.fc1_output) in named_modules order.  Returns the list, or (list, layer_info) when ``layer_indices`` is given."""
+    model = model.to(device)
+    activations, layer_info, hooks = [], [], []
+
+    def hook_return(index, name):
+        def hook(module, input, output):
+            if isinstance(module, Attention):
+                activations.append(module.qkv_output)
+            elif isinstance(module, Mlp):
+                activations.append(module.fc1_output)
+            else:
+                activations.append(output)
+            layer_info.append({'relative_index': len(layer_info), 'absolute_index': index, 'name': name, 'layer_type': type(module),
+                               'path': '%s.%s' % (type(module).__module__, type(module).__name__)})
+        return hook
+
+    kinds = (QConv2d, QLinear, Attention, Mlp) if bit_config is None else (QConv2d, QLinear)
+    for index, (name, layer) in enumerate(model.named_modules()):
+        if type(layer) in kinds:
+            hooks.append(layer.register_forward_hook(hook_return(index, name)))
+    try:
+        with torch.no_grad():
+            model(images.to(device), bit_config=bit_config, plot=False)
+    finally:
+        for h in hooks:
+            h.remove()
+    order = sorted(range(len(layer_info)), key=lambda k: layer_info[k]['absolute_index'])
+    layer_info = [layer_info[i] for i in order]
+    activations = [activations[i] for i in order]
+    for i, info in enumerate(layer_info):
+        info['relative_index'] = i
+    if layer_indices is not None:
+        keep = [i for i, info in enumerate(layer_info) if info['relative_index'] == layer_indices]
+        activations = [activations[i] for i in keep]
+        layer_info = [layer_info[i] for i in keep]
+    if normalize_act:
+        activations = [normalize_activations(a) for a in activations]
+    if layer_indices is None:
+        return activations
+    return activations, layer_info
+
+
+def gram_matrix(x, y=None, dtype=torch.float32):
+    """efficient_CKA.py:23-39 / DDV_CKA.py:20-39 in plain torch: the centred Gram matrix of one layer, flattened to n*n."""
+    x = x.reshape(x.size(0), -1)
+    gram = x @ (x if y is None else y.reshape(y.size(0), -1)).t()
+    n = gram.size(0)
+    gram.diagonal().fill_(0)
+    gram = gram.to(dtype)
+    means = gram.sum(0) / (n - 2)
+    means -= means.sum() / (2 * (n - 1))
+    gram -= means.unsqueeze(0)
+    gram -= means.unsqueeze(1)
+    gram.diagonal().fill_(0)
+    return gram.reshape(-1)
+
+
+def _grams(xs, ys, dtype):
+    """centred grams: [L, n, n] from the HIP kernels for GPU tensors, [L, n*n] from the restatement for CPU tensors."""
+    if xs[0].is_cuda:
+        return torch.ops.p2vit.cka_grams(list(xs), list(ys) if ys is not None else [])
+    return torch.stack([gram_matrix(x, None if ys is None else y, dtype) for x, y in zip(xs, ys if ys is not None else xs)])
+
+
+class MinibatchCKA:
+    """efficient_CKA.MinibatchCKA: unbiased-HSIC CKA accumulated over minibatches.  The accumulators live on the device of the first
+    update (the reference hard-codes .cuda())."""
+
+    def __init__(self, num_layers, num_layers2=None, across_models=False, dtype=torch.float32):
+        if num_layers2 is None:
+            num_layers2 = num_layers
+        self.dtype = dtype
+        self.across_models = across_models
+        self.hsic_accumulator = torch.zeros((num_layers, num_layers2), dtype=dtype)
+        self.hsic_accumulator_model1 = torch.zeros((num_layers,), dtype=dtype)
+        self.hsic_accumulator_model2 = torch.zeros((num_layers2,), dtype=dtype)
+        self._device = None
+
+    def _to(self, device):
+        if self._device is None:
+            self._device = device
+            self.hsic_accumulator = self.hsic_accumulator.to(device)
+            self.hsic_accumulator_model1 = self.hsic_accumulator_model1.to(device)
+            self.hsic_accumulator_model2 = self.hsic_accumulator_model2.to(device)
+        elif device != self._device:
+            raise AssertionError('activations on %s, accumulators on %s' % (device, self._device))
+
+    def _accumulate(self, g1, g2, self_terms):
+        self._to(g1.device)
+        if g1.is_cuda:
+            torch.ops.p2vit.hsic_accumulate(g1, g2, self.hsic_accumulator, self.hsic_accumulator_model1 if self_terms else None,
+                                            self.hsic_accumulator_model2 if self_terms else None)
+            return
+        self.hsic_accumulator.add_(g1 @ g2.t())
+        if self_terms:
+            self.hsic_accumulator_model1.add_(torch.einsum('ij,ij->i', g1, g1))
+            self.hsic_accumulator_model2.add_(torch.einsum('ij,ij->i', g2, g2))
+
+    def update_state(self, activations):
+        g = _grams(activations, None, self.dtype)
+        self._accumulate(g, g, False)
+
+    def update_state_across_models(self, activations1, activations2):
+        assert self.hsic_accumulator.size(0) == len(activations1), 'Number of activation vectors does not match num_layers.'
+        assert self.hsic_accumulator.size(1) == len(activations2), 'Number of activation vectors does not match num_layers.'
+        self._accumulate(_grams(activations1, None, self.dtype), _grams(activations2, None, self.dtype), True)
+
+    def result(self):
+        mean_hsic = self.hsic_accumulator
+        if self.across_models:
+            mean_hsic = mean_hsic / torch.sqrt(self.hsic_accumulator_model1).unsqueeze(1)
+            return mean_hsic / torch.sqrt(self.hsic_accumulator_model2).unsqueeze(0)
+        norm = torch.sqrt(mean_hsic.diagonal())
+        return mean_hsic / norm.unsqueeze(1) / norm.unsqueeze(0)
+
+
+class MinibatchAdvCKA(MinibatchCKA):
+    """DDV_CKA.MinibatchAdvCKA: grams of X (adv X)^T per model; the result is always normalised by the two self terms."""
+
+    def update_state(self, model1_activations, model1_adv_activations, model2_activations, model2_adv_activations):
+        g1 = _grams(model1_activations, model1_adv_activations, self.dtype)
+        g2 = _grams(model2_activations, model2_adv_activations, self.dtype)
+        self._accumulate(g1, g2, True)
+
+    def result(self):
+        mean_hsic = self.hsic_accumulator / torch.sqrt(self.hsic_accumulator_model1).unsqueeze(1)
+        return mean_hsic / torch.sqrt(self.hsic_accumulator_model2).unsqueeze(0)
+
+
+def _device_of(model):
+    p = next(model.parameters(), None)
+    return p.device if p is not None else torch.device('cpu')
+
+
+def compute_cka(model1, model2, batches, bit_config1, bit_config2, normalize_act=False, dtype=torch.float32):
+    """the CKA heat map [layers of model1, layers of model2] between two models over ``batches`` (image tensors, or (images, labels)
+    pairs), one update_state_across_models per batch."""
+    cka = None
+    for images in batches:
+        if isinstance(images, (tuple, list)):
+            images = images[0]
+        a1 = get_activations(images, model1, bit_config1, _device_of(model1), normalize_act)
+        a2 = get_activations(images, model2, bit_config2, _device_of(model2), normalize_act)
+        if cka is None:
+            cka = MinibatchCKA(len(a1), len(a2), across_models=True, dtype=dtype)
+        cka.update_state_across_models(a1, [a.to(a1[0].device) for a in a2])
+    if cka is None:
+        raise ValueError('compute_cka: no batches')
+    return cka.result()
+
+
+def main(argv=None):
+    from . import harness, synth
+    from .config import Config
+    p = argparse.ArgumentParser(description='float vs quantized CKA heat map on synthetic data (cka_utility.py)')
+    p.add_argument('--model', default='deit_small')
+    p.add_argument('--bits', default='8', choices=['8', '4', 'mixed'])
+    p.add_argument('--batch', default=50, type=int)
+    p.add_argument('--iters', default=2, type=int)
+    p.add_argument('--seed', default=0, type=int)
+    p.add_argument('--device', default='cuda')
+    p.add_argument('--result-name', default='cka_result')
+    args = p.parse_args(argv)
+    device = torch.device(args.device)
+    fp = harness.str2model(args.model)(cfg=Config(True, True, 'minmax'))
+    fp.load_state_dict(synth.vit_state_dict(fp.arch, args.seed), strict=False)
+    fp = fp.to(device).eval()
+    q = copy.deepcopy(fp)
+    harness.calibrate_model(q, synth.images(args.seed + 1, 10, fp.arch['img_size']).to(device))
+    L = 4 * fp.depth + 2
+    bits = {'8': [8] * L, '4': [4] * L, 'mixed': [8 if (i * 7 + 3) % 5 < 3 else 4 for i in range(L)]}[args.bits]
+    loader = harness.SyntheticLoader(args.batch * args.iters, args.batch, fp.arch['img_size'], fp.arch['num_classes'], args.seed + 2, device)
+    heatmap = compute_cka(fp, q, loader, None, bits).cpu().numpy()
+    os.makedirs(args.result_name, exist_ok=True)
+    path = os.path.join(args.result_name, '_heatmap.pkl')
+    with open(path, 'wb') as f:
+        pickle.dump(heatmap, f)
+    print('heat map %s -> %s' % (heatmap.shape, path))
+    return heatmap
+
+
+if __name__ == '__main__':
+    main()

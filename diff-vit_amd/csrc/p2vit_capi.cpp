@@ -531,7 +531,7 @@ static int prof_pool_size(const p2v_plan* p) { return p ? 7 * p->d.depth + 10 : 
 
 static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
                         size_t workspace_bytes, int stop_after, void* stream, Prof* prof, float* const* qkv_tap = nullptr,
-                        float* const* fc1_tap = nullptr) {
+                        float* const* fc1_tap = nullptr, float* const* lin_tap = nullptr) {
   if (!p || !images || !bit_config || !logits || !workspace) return fail(P2V_E_ARG, "p2v_forward: null argument");
   if (batch <= 0) return fail(P2V_E_SHAPE, "batch must be positive");
   if (n_cfg != p->n_layers) return fail(P2V_E_BITS, "bit_config has %d entries, model needs %d", n_cfg, p->n_layers);
@@ -545,6 +545,8 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
     if (!p->block_set[i]) return fail(P2V_E_STATE, "plan incomplete (block %d)", i);
   const WsLayout w = ws_layout(p, batch);
   if (workspace_bytes < w.total) return fail(P2V_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, w.total);
+  if (lin_tap && lin_tap[0] && !(p->inv_s_input > 0.f))
+    return fail(P2V_E_UNSUPPORTED, "p2v_forward_linear_taps: no patch-embed tap for input_quant = False (the fp32-image convolution); pass NULL for taps[0]");
   hipStream_t st = (hipStream_t)stream;
   int8_t* ws = reinterpret_cast<int8_t*>(workspace);
   int8_t *bufP = ws + w.patches, *bufX = ws + w.x, *bufLN = ws + w.ln, *bufQKV = ws + w.qkv, *bufATT = ws + w.att,
@@ -566,6 +568,15 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
     if (rc) return rc;                                \
     launched += (kind_ == P2V_K_LN_GEMM_QKV || kind_ == P2V_K_LN_GEMM_FC1) ? 2 : 1;   /* a fused launch fills two slots of the stop_after numbering */ \
   } while (0)
+  // layer-output tap of p2v_forward_linear_taps: a P2V_EPI_F32 GEMM over the layer's int8 input, still in the workspace right after the
+  // layer's own launch (not counted by stop_after: the entry point that passes lin_tap runs everything)
+#define LIN_TAP(idx, A, lda, M_, K_, N_, lin)                                                                              \
+  do {                                                                                                                    \
+    if (lin_tap && lin_tap[idx]) {                                                                                        \
+      rc = run_gemm(P2V_EPI_F32, A, lda, M_, K_, N_, lin, p2v_epilogue{}, lin_tap[idx], N_, nullptr, st);                 \
+      if (rc) return rc;                                                                                                  \
+    }                                                                                                                     \
+  } while (0)
 
   // qact_input + PatchEmbed + cls/pos/qact1                                 vit_fquant.py:705-733
   if (p->inv_s_input > 0.f) {
@@ -573,6 +584,7 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
                                        p->k_patch_pad, st), "quantize_patchify"));
     const p2v_linear& l = p->lin[bit_index(bit_config[0])][0];
     STEP(P2V_K_GEMM_EMBED, run_gemm(P2V_EPI_EMBED, bufP, p->k_patch_pad, batch * p->patches, p->k_patch_pad, D, l, p->embed_epi, bufX, D, nullptr, st));
+    LIN_TAP(0, bufP, p->k_patch_pad, batch * p->patches, p->k_patch_pad, D, l);
   } else {
     // input_quant = False (vit_fquant.py:705, the vit_large factory :925): the fp32 image feeds the fake-quantised convolution
     const p2v_linear& l = p->lin[bit_index(bit_config[0])][0];
@@ -597,7 +609,7 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
     // qkv -> qact1                                                          vit_fquant.py:293,307
     p2v_epilogue e{};
     e.inv_s_out = b.inv_s_qkv[bq];
-    e.tap_out = qkv_tap ? qkv_tap[i] : nullptr;
+    e.tap_out = qkv_tap ? qkv_tap[i] : (lin_tap ? lin_tap[1 + 4 * i] : nullptr);
     if (p->lin[bq][1 + 4 * i].w_frag && p2v_ln_gemm_supported(P2V_EPI_REQUANT, D, 3 * D, 0)) {              // one launch: the LayerNorm output stays in LDS
       if (!taps) ln.out = nullptr;
       STEP(P2V_K_LN_GEMM_QKV, run_ln_gemm(P2V_EPI_REQUANT, ln, p->lin[bq][1 + 4 * i], e, 3 * D, bufQKV, st));
@@ -613,6 +625,7 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
     ep.residual = bufX;
     ep.resid_tab = p->resid_tab[(size_t)i * 4 + bp];
     STEP(P2V_K_GEMM_PROJ, run_gemm(P2V_EPI_RESID, bufATT, D, M, Dk, D, p->lin[bp][2 + 4 * i], ep, bufX, D, nullptr, st));
+    LIN_TAP(2 + 4 * i, bufATT, D, M, Dk, D, p->lin[bp][2 + 4 * i]);
     // norm2 (attention's channel scale!) -> /mlp.channel_scale -> mlp.qact0 vit_fquant.py:464, layers_quant.py:305-311
     LnArgs ln2{bufX, D, M, D, b.ln2[bq][b1], bufLN, D};
     ln2.pre = b.ln2[bq][b1].pre;
@@ -620,7 +633,7 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
     p2v_epilogue e1{};
     e1.inv_s_out = b.inv_s_fc1;
     e1.gelu = b.gelu_fc1;
-    e1.tap_out = fc1_tap ? fc1_tap[i] : nullptr;
+    e1.tap_out = fc1_tap ? fc1_tap[i] : (lin_tap ? lin_tap[3 + 4 * i] : nullptr);
     if (p->lin[b1][3 + 4 * i].w_frag && p2v_ln_gemm_supported(P2V_EPI_GELU, D, Hd, e1.gelu.table ? e1.gelu.cells : 0)) {
       if (!taps) ln2.out = nullptr;
       STEP(P2V_K_LN_GEMM_FC1, run_ln_gemm(P2V_EPI_GELU, ln2, p->lin[b1][3 + 4 * i], e1, Hd, bufHID, st));
@@ -633,6 +646,7 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
     e2.residual = bufX;
     e2.resid_tab = p->resid_tab[(size_t)i * 4 + 2 + b2];
     STEP(P2V_K_GEMM_FC2, run_gemm(P2V_EPI_RESID, bufHID, Hd, M, Hk, D, p->lin[b2][4 + 4 * i], e2, bufX, D, nullptr, st));
+    LIN_TAP(4 + 4 * i, bufHID, Hd, M, Hk, D, p->lin[b2][4 + 4 * i]);
   }
   // norm over the cls rows only ([:,0]) -> qact2 -> head -> act_out         vit_fquant.py:766-796
   LnArgs lf{bufX, (long long)T * D, batch, D, p->final_ln, bufCLS, D};
@@ -643,6 +657,8 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
   eh.s_out = p->head_s;
   STEP(P2V_K_GEMM_HEAD, run_gemm(P2V_EPI_HEAD, bufCLS, D, batch, Dk, d.num_classes, p->lin[bit_index(bit_config[n_cfg - 1])][n_cfg - 1], eh, logits,
                 d.num_classes, nullptr, st));
+  LIN_TAP(n_cfg - 1, bufCLS, D, batch, Dk, d.num_classes, p->lin[bit_index(bit_config[n_cfg - 1])][n_cfg - 1]);
+#undef LIN_TAP
 #undef STEP
   if (prof) {
     if (prof->used + 2 > (int)prof->ev.size()) return fail(P2V_E_LAUNCH, "profile: event pool exhausted");
@@ -661,6 +677,12 @@ int p2v_forward(p2v_plan* p, const float* images, int batch, const int8_t* bit_c
 int p2v_forward_taps(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
                      size_t workspace_bytes, float* const* qkv_out, float* const* fc1_out, void* stream) {
   return forward_impl(p, images, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, -1, stream, nullptr, qkv_out, fc1_out);
+}
+
+int p2v_forward_linear_taps(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                            size_t ws_bytes, float* const* taps, void* stream) {
+  if (!taps) return fail(P2V_E_ARG, "p2v_forward_linear_taps: null taps array");
+  return forward_impl(p, images, batch, bit_config, n_cfg, logits, ws, ws_bytes, -1, stream, nullptr, nullptr, nullptr, taps);
 }
 
 static int prof_collect(Prof& prof, float* ms_out, int32_t* kind_out, int max_launches) {
@@ -981,3 +1003,41 @@ int p2v_gelu_err_sweep(unsigned first_bits, unsigned count, float* max_err, void
 }
 
 }  // extern "C"
+
+// ---- CKA model diff (p2vit_cka.hip) ------------------------------------------------------------------------------------------------
+static int cka_check(const p2v_cka_layer* layers, int n_layers, int n, const char* what) {
+  if (!layers || n_layers <= 0) return fail(P2V_E_ARG, "%s: no layers", what);
+  if (n < P2V_CKA_MIN_N || n > P2V_CKA_MAX_N) return fail(P2V_E_SHAPE, "%s: n = %d images, the kernels take %d ... %d", what, n, P2V_CKA_MIN_N, P2V_CKA_MAX_N);
+  for (int l = 0; l < n_layers; ++l) {
+    const p2v_cka_layer& a = layers[l];
+    if (!a.x) return fail(P2V_E_ARG, "%s: layer %d has a null x", what, l);
+    if (a.features < 1 || a.ldx < a.features) return fail(P2V_E_ARG, "%s: layer %d: F = %lld, ldx = %lld", what, l, a.features, a.ldx);
+    if (a.y && a.y != a.x && a.ldy < a.features) return fail(P2V_E_ARG, "%s: layer %d: ldy = %lld < F", what, l, a.ldy);
+  }
+  return P2V_OK;
+}
+
+size_t p2v_cka_workspace_bytes(const p2v_cka_layer* layers, int n_layers, int n) {
+  if (cka_check(layers, n_layers, n, "p2v_cka_workspace_bytes") != P2V_OK) return 0;
+  return p2v_cka_layout(layers, n_layers, n, nullptr).total;
+}
+
+int p2v_cka_grams(const p2v_cka_layer* layers, int n_layers, int n, float* grams, void* ws, size_t ws_bytes, void* stream) {
+  int rc = cka_check(layers, n_layers, n, "p2v_cka_grams");
+  if (rc != P2V_OK) return rc;
+  if (!grams || !ws) return fail(P2V_E_ARG, "p2v_cka_grams: null grams / workspace");
+  std::vector<CkaDesc> descs;
+  descs.reserve(n_layers);
+  const CkaLayout w = p2v_cka_layout(layers, n_layers, n, &descs);
+  if (ws_bytes < w.total) return fail(P2V_E_WORKSPACE, "p2v_cka_grams: workspace %zu < %zu bytes", ws_bytes, w.total);
+  if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_cka_grams: the workspace must be 256-byte aligned");
+  return launch_rc(p2v_launch_cka_grams(descs, w, n, grams, ws, (hipStream_t)stream), "cka_grams");
+}
+
+int p2v_hsic_accumulate(const float* g1, int l1, const float* g2, int l2, int n, void* acc, void* self1, void* self2, int dtype,
+                        void* stream) {
+  if (!g1 || !g2 || !acc || l1 <= 0 || l2 <= 0) return fail(P2V_E_ARG, "p2v_hsic_accumulate: null gram / accumulator or no layers");
+  if (n < P2V_CKA_MIN_N || n > P2V_CKA_MAX_N) return fail(P2V_E_SHAPE, "p2v_hsic_accumulate: n = %d images, the kernels take %d ... %d", n, P2V_CKA_MIN_N, P2V_CKA_MAX_N);
+  if (dtype != 0 && dtype != 1) return fail(P2V_E_ARG, "p2v_hsic_accumulate: dtype %d (0 = fp32, 1 = fp64)", dtype);
+  return launch_rc(p2v_launch_hsic(g1, l1, g2, l2, n, acc, self1, self2, dtype, (hipStream_t)stream), "hsic_accumulate");
+}

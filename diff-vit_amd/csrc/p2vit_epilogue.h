@@ -51,10 +51,32 @@ __device__ __forceinline__ void gemm_stage_epilogue(EpiLds* e, int n0, int tid, 
   }
 }
 
-// EMBED and HEAD epilogues (one launch each per forward, k_gemm_i8); the per-block epilogues of the layer GEMMs are gemm_epilogue_tile2
+// EMBED and HEAD epilogues (one launch each per forward, k_gemm_i8) and F32 (the layer-output taps of p2v_forward_linear_taps); the
+// per-block epilogues of the layer GEMMs are gemm_epilogue_tile2
 template <int EPI>
 __device__ __forceinline__ void gemm_epilogue_tile(const v16i& acc, int m, int n_tile, int nl, int h, const GemmArgs& g, const EpiLds* e) {
-  static_assert(EPI == P2V_EPI_EMBED || EPI == P2V_EPI_HEAD, "stem / head epilogue");
+  static_assert(EPI == P2V_EPI_EMBED || EPI == P2V_EPI_HEAD || EPI == P2V_EPI_F32, "stem / head / tap epilogue");
+  if constexpr (EPI == P2V_EPI_F32) {
+    // QLinear / QConv2d output fmaf(acc, colscale, bias) stored as fp32 [M][ldo]: one rounding, as gemm_epilogue_tile2's tap_out
+    if (m >= g.M) return;
+    float* orow = reinterpret_cast<float*>(g.out) + (long long)m * g.ldo;
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const int n = n_tile + 8 * gq + 4 * h, c = nl + 8 * gq + 4 * h;
+      const float4 cs = *reinterpret_cast<const float4*>(e->colscale + c);
+      const float4 bs = *reinterpret_cast<const float4*>(e->bias + c);
+      const float y[4] = {__builtin_fmaf((float)acc[4 * gq + 0], cs.x, bs.x), __builtin_fmaf((float)acc[4 * gq + 1], cs.y, bs.y),
+                          __builtin_fmaf((float)acc[4 * gq + 2], cs.z, bs.z), __builtin_fmaf((float)acc[4 * gq + 3], cs.w, bs.w)};
+      if (n + 3 < g.N && (g.ldo & 3) == 0) {
+        *reinterpret_cast<float4*>(orow + n) = make_float4(y[0], y[1], y[2], y[3]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (n + i < g.N) orow[n + i] = y[i];
+      }
+    }
+    return;
+  }
   // lane owns output row m, channels n_tile + 8*gq + 4*h + {0..3}, gq = 0..3   (C/D map of 32x32 MFMA);
   // nl = n_tile - n0 (column offset inside the block tile, for the LDS constants)
   const bool row_ok = m < g.M;

@@ -438,7 +438,7 @@ int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
   g.stamps = g_gemm_stamps;
 #endif
   g.tiles_n = (g.N + GBN - 1) / GBN;
-  if (epi != P2V_EPI_HEAD && epi != P2V_EPI_EMBED) {
+  if (epi != P2V_EPI_HEAD && epi != P2V_EPI_EMBED && epi != P2V_EPI_F32) {
     // the tiled kernel addresses both matrices with 32-bit lane offsets
     if ((long long)g.M * g.lda + g.K >= (1LL << 32) || (long long)g.tiles_n * GBN * g.K >= (1LL << 32)) return -1;
     // 256-row tiles (8 waves, two workgroups per CU) when the grid still gives every CU its two workgroups; else 128-row tiles
@@ -487,10 +487,13 @@ int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
     CHECK_LAUNCH();
     return 0;
   }
-  // EMBED / HEAD: one launch each per forward; 8-wave shape (64x32 wave tiles, <= 128 VGPRs)
+  // EMBED / HEAD: one launch each per forward; F32: a tap of p2v_forward_linear_taps; 8-wave shape (64x32 wave tiles, <= 128 VGPRs)
   const int tiles_m = (g.M + GBM - 1) / GBM;
   dim3 grid(g.tiles_n * tiles_m), block(512);
-  if (epi == P2V_EPI_EMBED) {
+  if (epi == P2V_EPI_F32) {
+    if (g.w4) hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_F32, true>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_F32, false>), grid, block, 0, st, g);
+  } else if (epi == P2V_EPI_EMBED) {
     if (g.w4) hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED, true>), grid, block, 0, st, g);
     else hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED, false>), grid, block, 0, st, g);
   } else {

@@ -6,6 +6,7 @@
 #include "../../include/p2vit.h"
 
 #define GBK_PAD 64   // K granularity of the GEMM tiles: weights/activations are padded to this
+#define P2V_EPI_F32 7     // internal: the layer output fmaf(acc, colscale, bias) as fp32, no QAct (taps of p2v_forward_linear_taps)
 
 struct GemmArgs {
   const int8_t* A;      // activations [M][lda] int8
@@ -91,3 +92,21 @@ int p2v_launch_gelu_sweep(unsigned first_bits, unsigned count, float* max_err, h
 // exact GELU->requant threshold table (see the GELU section of p2vit_device.h)
 int p2v_launch_gelu_table_build(float inv_s, const p2v_gelu_tab& t, unsigned* scratch, hipStream_t st);
 int p2v_launch_gelu_table_check(float inv_s, const p2v_gelu_tab& t, unsigned long long* mismatches, hipStream_t st);
+
+// CKA grams (p2vit_cka.hip): one record per layer in the workspace, and where the workspace's parts start
+#include <vector>
+struct CkaDesc {
+  const float* x;
+  const float* y;        // == x for X X^T
+  long long F, ldx, ldy;
+  long long item0;       // first workgroup of the layer in k_cka_partial's grid
+  long long part0;       // first float of the layer's chunk partials
+  int nchunks, sym, vec, pad;
+};
+struct CkaLayout {
+  long long items;       // workgroups of k_cka_partial
+  size_t desc_off, part_off, g64_off, total;
+};
+CkaLayout p2v_cka_layout(const p2v_cka_layer* layers, int L, int n, std::vector<CkaDesc>* descs);
+int p2v_launch_cka_grams(const std::vector<CkaDesc>& descs, const CkaLayout& w, int n, float* grams, void* ws, hipStream_t st);
+int p2v_launch_hsic(const float* g1, int l1, const float* g2, int l2, int n, void* acc, void* self1, void* self2, int dtype, hipStream_t st);

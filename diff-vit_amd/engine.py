@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libp2vit_hip.so')
 
-P2V_ABI_VERSION = 5
+P2V_ABI_VERSION = 6
 EPI_REQUANT, EPI_GELU, EPI_RESID, EPI_EMBED, EPI_HEAD = 0, 1, 2, 3, 4
 E_ARG, E_BITS, E_SHAPE, E_UNSUPPORTED, E_WORKSPACE, E_LAUNCH, E_STATE = -1, -2, -3, -4, -5, -6, -7
 
@@ -74,6 +74,11 @@ class Op(C.Structure):
                 ('lin', Linear), ('ep', Epilogue), ('ln', Ln), ('wa', WinAttn)]
 
 
+class CkaLayer(C.Structure):
+    """``p2v_cka_layer``: one layer of a CKA minibatch (n rows of F fp32 features; y None = X X^T)."""
+    _fields_ = [('x', _p), ('y', _p), ('features', _ll), ('ldx', _ll), ('ldy', _ll)]
+
+
 class P2VError(RuntimeError):
     pass
 
@@ -119,6 +124,11 @@ def lib():
     L.p2v_workspace_view.restype = _ll
     L.p2v_forward.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _p]
     L.p2v_forward_taps.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, C.POINTER(_p), C.POINTER(_p), _p]
+    L.p2v_forward_linear_taps.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, C.POINTER(_p), _p]
+    L.p2v_cka_workspace_bytes.argtypes = [C.POINTER(CkaLayer), _i, _i]
+    L.p2v_cka_workspace_bytes.restype = C.c_size_t
+    L.p2v_cka_grams.argtypes = [C.POINTER(CkaLayer), _i, _i, _p, _p, C.c_size_t, _p]
+    L.p2v_hsic_accumulate.argtypes = [_p, _i, _p, _i, _i, _p, _p, _p, _i, _p]
     L.p2v_forward_profile.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_int32), _i]
     L.p2v_forward_profile_begin.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(_p)]

@@ -11,6 +11,8 @@ one without the built library raises ``RuntimeError`` from ``engine.lib()``.
     torch.ops.p2vit.int_layernorm(x, s1, mask, gamma, beta, inv_out, post_mul)  QIntLayerNorm 'int'        layers.py:255-289
     torch.ops.p2vit.lis_attention(qkv, heads, s_qkv_sq, qk_scale, inv_s_attn, av_mul, x0, b, c)   vit_fquant.py:309-326, layers.py:323-376
     torch.ops.p2vit.forward(plan_handle, images, bit_config)                    VisionTransformer.forward  vit_fquant.py:780-799
+    torch.ops.p2vit.cka_grams(xs, ys)                                           _generate_gram_matrix      efficient_CKA.py:23-39
+    torch.ops.p2vit.hsic_accumulate(g1, g2, acc, self1, self2)                  update_state*              efficient_CKA.py:41-58
 """
 import ctypes as C
 
@@ -26,6 +28,8 @@ _LIB.define('linear_gelu_requant(Tensor x, Tensor w, Tensor colscale, Tensor bia
 _LIB.define('int_layernorm(Tensor x, float s1, Tensor mask, Tensor gamma, Tensor beta, Tensor inv_out, Tensor post_mul) -> Tensor')
 _LIB.define('lis_attention(Tensor qkv, int heads, float s_qkv_sq, float qk_scale, float inv_s_attn, float av_mul, int x0, int b, int c) -> Tensor')
 _LIB.define('forward(int plan, Tensor images, int[] bit_config) -> Tensor')
+_LIB.define('cka_grams(Tensor[] xs, Tensor[] ys) -> Tensor')
+_LIB.define('hsic_accumulate(Tensor g1, Tensor g2, Tensor(a!) acc, Tensor(b!)? self1, Tensor(c!)? self2) -> ()')
 
 
 def _f32(t):
@@ -101,6 +105,71 @@ def _forward(plan, images, bit_config):
     return p.forward(images, list(bit_config))
 
 
+def _cka_rows(x, n):
+    """(tensor kept alive, row stride) of ``x`` viewed as n rows of F = x[0].numel() fp32 features, without a copy where the rows
+    already lie in memory one after another (any feature order: a Gram matrix does not depend on it), e.g. the permuted
+    [B, D, H/P, W/P] patch-embed tap."""
+    if x.dim() == 0 or x.shape[0] != n:
+        raise AssertionError('cka_grams: every activation needs %d rows (got shape %s)' % (n, tuple(x.shape)))
+    x = x.float()
+    F = x[0].numel()
+    if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= F:
+        return x, x.stride(0)
+    order = [0] + sorted(range(1, x.dim()), key=lambda d: -x.stride(d))
+    if x.stride(0) == F and x.permute(order).is_contiguous():
+        return x, F
+    return x.reshape(n, -1).contiguous(), F
+
+
+def _cka_grams(xs, ys):
+    if not xs:
+        raise AssertionError('cka_grams: no layers')
+    if ys and len(ys) != len(xs):
+        raise AssertionError('cka_grams: %d x layers but %d y layers' % (len(xs), len(ys)))
+    n, dev = xs[0].shape[0] if xs[0].dim() else 0, xs[0].device
+    keep, descs = [], (E.CkaLayer * len(xs))()
+    for k, x in enumerate(xs):
+        xt, ldx = _cka_rows(x, n)
+        keep.append(xt)
+        d = descs[k]
+        d.x, d.features, d.ldx = xt.data_ptr(), xt[0].numel(), ldx
+        if ys:
+            if tuple(ys[k].shape[1:]) != tuple(x.shape[1:]) and ys[k][0].numel() != xt[0].numel():
+                raise AssertionError('cka_grams: layer %d: x and y differ in features' % k)
+            yt, ldy = _cka_rows(ys[k], n)
+            keep.append(yt)
+            d.y, d.ldy = yt.data_ptr(), ldy
+        for t in keep[-2:]:
+            if t.device != dev:
+                raise AssertionError('cka_grams: every activation must be on %s' % dev)
+    L = E.lib()
+    with torch.cuda.device(dev):
+        nbytes = L.p2v_cka_workspace_bytes(descs, len(xs), n)
+        if nbytes == 0:
+            E.check(L.p2v_cka_grams(descs, len(xs), n, None, None, 0, None))       # raises with the validation message
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(len(xs), n, n, dtype=torch.float32, device=dev)
+        E.check(L.p2v_cka_grams(descs, len(xs), n, E.ptr(out), E.ptr(ws), nbytes, E.stream_ptr(dev)))
+    return out
+
+
+def _hsic_accumulate(g1, g2, acc, self1, self2):
+    dt = {torch.float32: 0, torch.float64: 1}.get(acc.dtype)
+    if dt is None:
+        raise AssertionError('hsic_accumulate: the accumulators are fp32 or fp64')
+    n = g1.shape[-1]                          # grams [layers][n][n]
+    l1, l2 = g1.shape[0], g2.shape[0]
+    for t, shp in ((acc, (l1, l2)), (self1, (l1,)), (self2, (l2,))):
+        if t is not None and (tuple(t.shape) != shp or t.dtype != acc.dtype or not t.is_contiguous() or t.device != g1.device):
+            raise AssertionError('hsic_accumulate: accumulator of shape %s, dtype %s, contiguous, on %s expected' % (shp, acc.dtype, g1.device))
+    g1, g2 = g1.float().contiguous(), g2.float().contiguous()
+    if g1.numel() != l1 * n * n or g2.numel() != l2 * n * n:
+        raise AssertionError('hsic_accumulate: grams must be [layers][n][n]')
+    with torch.cuda.device(g1.device):
+        E.check(E.lib().p2v_hsic_accumulate(E.ptr(g1), l1, E.ptr(g2), l2, n, E.ptr(acc), E.ptr(self1), E.ptr(self2), dt,
+                                            E.stream_ptr(g1.device)))
+
+
 _LIB.impl('fake_quant', _fake_quant, 'CUDA')
 _LIB.impl('quantize_patchify', _quantize_patchify, 'CUDA')
 _LIB.impl('linear_requant', lambda x, w, cs, b, inv: _linear(E.EPI_REQUANT, x, w, cs, b, inv), 'CUDA')
@@ -108,5 +177,8 @@ _LIB.impl('linear_gelu_requant', lambda x, w, cs, b, inv: _linear(E.EPI_GELU, x,
 _LIB.impl('int_layernorm', _int_layernorm, 'CUDA')
 _LIB.impl('lis_attention', _lis_attention, 'CUDA')
 _LIB.impl('forward', _forward, 'CUDA')
+_LIB.impl('cka_grams', _cka_grams, 'CUDA')
+_LIB.impl('hsic_accumulate', _hsic_accumulate, 'CUDA')
 
-OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'forward')
+OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'forward', 'cka_grams',
+       'hsic_accumulate')

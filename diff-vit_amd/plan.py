@@ -310,6 +310,36 @@ class FrozenPlan:
                 taps['qkv_output'], taps['fc1_output'] = qkv, fc1
         return out
 
+    def tap_shapes(self, batch):
+        """shapes of the ``forward_linear_taps`` buffers, in bit_config order: the patch-embed output channels last [B*patches, D],
+        qkv / proj / fc1 / fc2 of each block [B, tokens, width], the head [B, classes]."""
+        T, D = self.tokens, self.D
+        blk = [(batch, T, 3 * D), (batch, T, D), (batch, T, self.hidden), (batch, T, D)]
+        return [(batch * self.patches, D)] + blk * self.depth + [(batch, self.arch['num_classes'])]
+
+    def forward_linear_taps(self, images, bit_config, want=None, out=None):
+        """p2v_forward_linear_taps: logits plus the output of every linear layer (what cka_utility.py:26-113 hooks on QConv2d /
+        QLinear).  Returns (logits, taps): taps[k] for bit_config index k is an fp32 tensor of ``tap_shapes`` (the patch-embed tap as
+        the [B, D, H/P, W/P] view of the reference's QConv2d output), or None where ``want`` (indices) leaves it out."""
+        images, cfg = self._check(images, bit_config)
+        B = images.shape[0]
+        shapes = self.tap_shapes(B)
+        want = set(range(len(shapes))) if want is None else set(want)
+        with torch.cuda.device(self.device):
+            ws = self.workspace(B)
+            if out is None:
+                out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
+            else:
+                self._check_out(out, B)
+            bufs = [torch.empty(s, dtype=torch.float32, device=self.device) if k in want else None for k, s in enumerate(shapes)]
+            ptrs = (C.c_void_p * len(bufs))(*[None if t is None else t.data_ptr() for t in bufs])
+            E.check(E.lib().p2v_forward_linear_taps(self._handle, E.ptr(images), B, cfg, len(bit_config), E.ptr(out), E.ptr(ws),
+                                                    ws.numel(), ptrs, E.stream_ptr(self.device)))
+        g = self.arch['img_size'] // self.arch['patch_size']
+        if bufs[0] is not None:
+            bufs[0] = bufs[0].view(B, g, g, self.D).permute(0, 3, 1, 2)
+        return out, bufs
+
     def slice_sizes(self, batch, n_streams=3):
         """Batch slices of ``forward_streams`` for up to ``n_streams`` side streams plus the caller's own stream (256 -> 68 + 68 + 68 + 52).
         Four kernels in flight on four hardware queues is what the device sustains - a fourth SIDE stream (five streams with the caller's)

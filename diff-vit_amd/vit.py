@@ -483,6 +483,9 @@ class VisionTransformer(nn.Module):
                 raise ValueError('None is not in list')          # bit_pool.index(None), vit_fquant.py:282
             if self._plan is None:
                 self.freeze(x.device if x.is_cuda else None)
+            linear = self.linear_modules()
+            if any(m._forward_hooks for m in linear):
+                return self._forward_hooked(x, bit_config, linear)
             if not self.capture_taps:
                 bits = [int(b) for b in bit_config]
                 if x.shape[0] >= 64:       # large batches: contiguous slices on up to four HIP streams (same logits, +4 ... +29 %: FrozenPlan.slice_sizes)
@@ -503,6 +506,36 @@ class VisionTransformer(nn.Module):
         FLOPs.append(C * x.shape[1])
         x = self.act_out(x)
         return x, FLOPs, global_distance
+
+
+    def linear_modules(self):
+        """the QConv2d / QLinear modules in bit_config order (= named_modules order): patch_embed.proj, then qkv, proj, fc1, fc2 of
+        every block, then head."""
+        mods = [self.patch_embed.proj]
+        for blk in self.blocks:
+            mods += [blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2]
+        return mods + [self.head]
+
+    def _forward_hooked(self, x, bit_config, linear):
+        """fused forward of a model with forward hooks on its QConv2d / QLinear modules (cka_utility.get_activations registers them):
+        one p2v_forward_linear_taps call, then every hook once, in module order, as hook(module, (), output) with the layer's fp32
+        output (QConv2d: the [B, D, H/P, W/P] view).  The engine cannot consume a replaced output: a hook that returns one raises."""
+        hooked = [k for k, m in enumerate(linear) if m._forward_hooks]
+        want = set(hooked)
+        if self.capture_taps:
+            want |= {1 + 4 * i for i in range(self.depth)} | {3 + 4 * i for i in range(self.depth)}
+        out, taps = self._plan.forward_linear_taps(x, [int(b) for b in bit_config], want)
+        if self.capture_taps:
+            for i, blk in enumerate(self.blocks):
+                blk.attn.qkv_output, blk.mlp.fc1_output = taps[1 + 4 * i], taps[3 + 4 * i]
+        for k in hooked:
+            m = linear[k]
+            for hid, hook in list(m._forward_hooks.items()):
+                r = hook(m, (), {}, taps[k]) if m._forward_hooks_with_kwargs.get(hid, False) else hook(m, (), taps[k])
+                if r is not None:
+                    raise RuntimeError('a forward hook on %s returned a replacement output: the fused engine cannot consume it '
+                                       '(model_dequant() runs the module graph, where it can)' % type(m).__name__)
+        return out, self.flops(), []
 
 
 def _factory(name, embed_dim, depth, num_heads, input_quant=True):

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define P2V_ABI_VERSION 5
+#define P2V_ABI_VERSION 6
 #define P2V_MAX_TOKENS 608            /* tokens per image of the RESIDENT ViT attention kernel (K / V^T of a head in LDS; 19 pairs of 32 keys) */
 #define P2V_MAX_TOKENS_STREAMED 4096  /* tokens per image of the streaming attention kernel that takes over beyond the resident one's limit (round 4) */
 /* tokens per image a plan / p2v_lis_attention accepts at this head dimension (P2V_MAX_TOKENS_STREAMED; 0: head_dim not instantiated), and how many of
@@ -265,6 +265,19 @@ int p2v_forward_taps(p2v_plan* plan, const float* images, int batch, const int8_
                      float* logits, void* workspace, size_t workspace_bytes, float* const* qkv_out, float* const* fc1_out,
                      void* stream);
 
+/* p2v_forward with the output of EVERY linear layer (ABI 6): what cka_utility.py:26-113 hooks on QConv2d / QLinear when it is given a
+ * bit_config.  taps: HOST array of n_cfg device pointers indexed like bit_config (entries may be NULL = skip):
+ *   taps[0]            fp32 [batch*patches][embed_dim]           patch-embed convolution output (row b*patches + p: the [B, D, H/P, W/P]
+ *                                                                  tensor of the reference, channels last)
+ *   taps[1+4i+{0..3}]  fp32 [batch*tokens][3D | D | hidden | D]   qkv / proj / fc1 / fc2 of block i
+ *   taps[n_cfg-1]      fp32 [batch][num_classes]                 head output before act_out
+ * Every entry holds the QLinear / QConv2d output fmaf(acc, colscale, bias) - one fp32 rounding, the value of p2v_forward_taps' qkv / fc1
+ * taps.  qkv and fc1 come from the epilogues of their own launches; proj, fc2, embed and head from one extra fp32-output GEMM each over
+ * the layer's int8 input right after the layer's launch.  The logits equal p2v_forward's.  A plan with inv_s_input == 0 (input_quant =
+ * False) has no integer patch-embed input: taps[0] != NULL returns P2V_E_UNSUPPORTED there (the other taps work). */
+int p2v_forward_linear_taps(p2v_plan* plan, const float* images, int batch, const int8_t* bit_config, int n_cfg,
+                            float* logits, void* ws, size_t ws_bytes, float* const* taps, void* stream);
+
 /* Kernel kinds reported by p2v_forward_profile. */
 enum {
   P2V_K_PATCHIFY = 0, P2V_K_GEMM_EMBED = 1, P2V_K_FILL_CLS = 2, P2V_K_LAYERNORM = 3, P2V_K_GEMM_QKV = 4,
@@ -437,6 +450,31 @@ int p2v_gelu_err_sweep(unsigned first_bits, unsigned count, float* max_err, void
  * a dispatch pipe, or that share a queue, take 0.46 - 0.60 ms - and a sliced forward on such a pair runs BELOW the one-stream rate
  * (profiles/r04_stream_pool.txt).  The host side probes candidate side streams with it before the first sliced forward (engine.side_streams). */
 int p2v_stream_probe(void* stream, int kernels, int usec, int workgroups, int lds_bytes);
+
+/* ---- CKA model diff (ABI 6): efficient_CKA.MinibatchCKA / DDV_CKA.MinibatchAdvCKA on device ------------------------------------
+ * One layer of a minibatch: n rows (images) of F features, row i at x + i * ldx (fp32, device).  y == NULL or y == x: the Gram X X^T
+ * (only the upper-triangle tiles are computed and the result is exactly symmetric); else X Y^T (MinibatchAdvCKA's x vs adv_x). */
+typedef struct p2v_cka_layer {
+  const float* x;      /* dev [n][ldx] */
+  const float* y;      /* dev [n][ldy] or NULL */
+  long long features;  /* F >= 1 */
+  long long ldx, ldy;  /* row strides in floats (>= F) */
+} p2v_cka_layer;
+#define P2V_CKA_MIN_N 4
+#define P2V_CKA_MAX_N 256
+#define P2V_CKA_CHUNK 4096    /* features per partial product: the chunking depends on (n, F) only */
+size_t p2v_cka_workspace_bytes(const p2v_cka_layer* layers, int n_layers, int n);
+/* grams: dev fp32 [n_layers][n][n], per layer the reference's _generate_gram_matrix (efficient_CKA.py:23-39): G = X Y^T with a zero
+ * diagonal, means = colsum(G) / (n-2), means -= sum(means) / (2(n-1)), G[i][j] -= means[j] + means[i] (in that order), diagonal
+ * zeroed.  Products are exact fp32 MFMA chains over 4096-feature chunks; the chunk partials are combined and centred in fp64 in a
+ * fixed order (no atomics): the result is bitwise repeatable.  layers: HOST array (copied to the workspace before the call returns).
+ * Three launches on `stream`. */
+int p2v_cka_grams(const p2v_cka_layer* layers, int n_layers, int n, float* grams, void* ws, size_t ws_bytes, void* stream);
+/* update_state / update_state_across_models: acc[a][b] += <G1[a], G2[b]> over the n*n flattened grams (g1: dev fp32 [l1][n*n],
+ * g2: dev fp32 [l2][n*n]); self1[a] += <G1[a], G1[a]>, self2[b] += <G2[b], G2[b]> when non-NULL.  Dot products in fp64, fixed order;
+ * dtype 0: acc / self are fp32, 1: fp64 (the accumulator dtype of MinibatchCKA). */
+int p2v_hsic_accumulate(const float* g1, int l1, const float* g2, int l2, int n, void* acc, void* self1, void* self2, int dtype,
+                        void* stream);
 
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
