@@ -531,8 +531,10 @@ static int prof_pool_size(const p2v_plan* p) { return p ? 7 * p->d.depth + 10 : 
 
 static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
                         size_t workspace_bytes, int stop_after, void* stream, Prof* prof, float* const* qkv_tap = nullptr,
-                        float* const* fc1_tap = nullptr, float* const* lin_tap = nullptr) {
-  if (!p || !images || !bit_config || !logits || !workspace) return fail(P2V_E_ARG, "p2v_forward: null argument");
+                        float* const* fc1_tap = nullptr, float* const* lin_tap = nullptr, const uint8_t* u8 = nullptr, int layout = 0,
+                        const void* lut = nullptr) {
+  // u8 != nullptr: p2v_forward_u8 (images == nullptr; the input stage reads the uint8 images through `lut`, the rest is shared)
+  if (!p || !(images || u8) || !bit_config || !logits || !workspace) return fail(P2V_E_ARG, "p2v_forward: null argument");
   if (batch <= 0) return fail(P2V_E_SHAPE, "batch must be positive");
   if (n_cfg != p->n_layers) return fail(P2V_E_BITS, "bit_config has %d entries, model needs %d", n_cfg, p->n_layers);
   for (int i = 0; i < n_cfg; ++i) {
@@ -580,8 +582,12 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
 
   // qact_input + PatchEmbed + cls/pos/qact1                                 vit_fquant.py:705-733
   if (p->inv_s_input > 0.f) {
-    STEP(P2V_K_PATCHIFY, launch_rc(p2v_launch_patchify(images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, p->inv_s_input, bufP,
-                                       p->k_patch_pad, st), "quantize_patchify"));
+    if (u8)
+      STEP(P2V_K_PATCHIFY, launch_rc(p2v_launch_u8_patchify(u8, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, layout,
+                                                            (const int8_t*)lut, bufP, p->k_patch_pad, st), "u8_patchify"));
+    else
+      STEP(P2V_K_PATCHIFY, launch_rc(p2v_launch_patchify(images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, p->inv_s_input, bufP,
+                                         p->k_patch_pad, st), "quantize_patchify"));
     const p2v_linear& l = p->lin[bit_index(bit_config[0])][0];
     STEP(P2V_K_GEMM_EMBED, run_gemm(P2V_EPI_EMBED, bufP, p->k_patch_pad, batch * p->patches, p->k_patch_pad, D, l, p->embed_epi, bufX, D, nullptr, st));
     LIN_TAP(0, bufP, p->k_patch_pad, batch * p->patches, p->k_patch_pad, D, l);
@@ -595,7 +601,11 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
 #ifdef P2V_DIAG
     g.stamps = nullptr;
 #endif
-    STEP(P2V_K_GEMM_EMBED, launch_rc(p2v_launch_embed_fp32(images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, g, st), "embed_fp32"));
+    if (u8)
+      STEP(P2V_K_GEMM_EMBED, launch_rc(p2v_launch_embed_u8(u8, layout, (const float*)lut, batch, d.in_chans, d.img_size, d.img_size, d.patch_size,
+                                                           g, st), "embed_u8"));
+    else
+      STEP(P2V_K_GEMM_EMBED, launch_rc(p2v_launch_embed_fp32(images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, g, st), "embed_fp32"));
   }
   STEP(P2V_K_FILL_CLS, launch_rc(p2v_launch_fill_cls(bufX, batch, T, D, p->cls_codes, st), "fill_cls"));
 
@@ -674,6 +684,22 @@ int p2v_forward(p2v_plan* p, const float* images, int batch, const int8_t* bit_c
   return forward_impl(p, images, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stop_after, stream, nullptr);
 }
 
+// uint8 input (p2v_forward_u8, p2v_u8_patchify): images and table present, a known layout, images 4-byte aligned (the kernels read dwords)
+static int check_u8_input(const char* what, const uint8_t* img, int layout, const void* lut) {
+  if (!img || !lut) return fail(P2V_E_ARG, "%s: null images or lut", what);
+  if (layout != P2V_LAYOUT_NCHW && layout != P2V_LAYOUT_NHWC) return fail(P2V_E_ARG, "%s: unknown layout %d (P2V_LAYOUT_NCHW = 0, NHWC = 1)", what, layout);
+  if (reinterpret_cast<uintptr_t>(img) & 3) return fail(P2V_E_ARG, "%s: images must start on a 4-byte boundary", what);
+  return P2V_OK;
+}
+
+int p2v_forward_u8(p2v_plan* p, const uint8_t* images, int layout, const void* lut, int batch, const int8_t* bit_config, int n_cfg,
+                   float* logits, void* workspace, size_t workspace_bytes, int stop_after, void* stream) {
+  const int rc = check_u8_input("p2v_forward_u8", images, layout, lut);
+  if (rc) return rc;
+  return forward_impl(p, nullptr, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stop_after, stream, nullptr, nullptr, nullptr,
+                      nullptr, images, layout, lut);
+}
+
 int p2v_forward_taps(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
                      size_t workspace_bytes, float* const* qkv_out, float* const* fc1_out, void* stream) {
   return forward_impl(p, images, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, -1, stream, nullptr, qkv_out, fc1_out);
@@ -742,6 +768,18 @@ int p2v_quantize_patchify(const float* img, int batch, int chans, int height, in
   if (patch <= 0 || patch % 4 || height % patch || width % patch) return fail(P2V_E_SHAPE, "image %dx%d not divisible into %d-patches", height, width, patch);
   if (k_pad % 4 || k_pad < chans * patch * patch) return fail(P2V_E_ARG, "k_pad %d too small / unaligned", k_pad);
   return launch_rc(p2v_launch_patchify(img, batch, chans, height, width, patch, inv_s, out, k_pad, (hipStream_t)stream), "quantize_patchify");
+}
+
+int p2v_u8_patchify(const uint8_t* img, int layout, const void* lut_i8, int batch, int chans, int height, int width, int patch, int8_t* out,
+                    int k_pad, void* stream) {
+  int rc = check_u8_input("p2v_u8_patchify", img, layout, lut_i8);
+  if (rc) return rc;
+  if (!out) return fail(P2V_E_ARG, "p2v_u8_patchify: null argument");
+  if (batch <= 0 || chans <= 0) return fail(P2V_E_SHAPE, "p2v_u8_patchify: batch %d, %d channels", batch, chans);
+  if (patch <= 0 || patch % 4 || height % patch || width % patch) return fail(P2V_E_SHAPE, "image %dx%d not divisible into %d-patches", height, width, patch);
+  if (k_pad % 4 || k_pad < chans * patch * patch) return fail(P2V_E_ARG, "k_pad %d too small / unaligned", k_pad);
+  return launch_rc(p2v_launch_u8_patchify(img, batch, chans, height, width, patch, layout, (const int8_t*)lut_i8, out, k_pad, (hipStream_t)stream),
+                   "u8_patchify");
 }
 
 int p2v_gemm_i8(int kind, const int8_t* A, int lda, int M, int K, int N, const p2v_linear* lin, const p2v_epilogue* epi, void* out,

@@ -164,6 +164,106 @@ __global__ __launch_bounds__(256) void k_embed_fp32(const float* __restrict__ im
   }
 }
 
+// pixels of a uint8 image (NHWC or NCHW) through the fp32 table [Cin][256] in LDS: the values data.normalize_uint8 produces
+template <int NHWC>
+struct EmbedPixU8 {
+  const uint8_t* base;
+  const float* tab;
+  __device__ __forceinline__ void at(const uint8_t* img, int b_, int Cin, int H, int Wd, int P, int py, int px) {
+    base = img + (long long)b_ * Cin * H * Wd + (NHWC ? ((long long)py * P * Wd + px * P) * Cin : (long long)py * P * Wd + px * P);
+  }
+  __device__ __forceinline__ float4 load4(int c, int i, int j, int H, int Wd, int Cin) const {
+    const float* t = tab + c * 256;
+    if (NHWC) {
+      const uint8_t* s = base + ((long long)i * Wd + j) * Cin + c;
+      return make_float4(t[s[0]], t[s[Cin]], t[s[2 * Cin]], t[s[3 * Cin]]);
+    }
+    const unsigned s = *reinterpret_cast<const unsigned*>(base + ((long long)c * H + i) * Wd + j);
+    return make_float4(t[s & 255u], t[(s >> 8) & 255u], t[(s >> 16) & 255u], t[s >> 24]);
+  }
+};
+
+// k_embed_fp32's tile loop with the pixel load as a parameter, for the uint8 kernel below (k_embed_fp32 keeps its own text: its code
+// object stays exactly what it was)
+template <class Pix, class Img>
+__device__ __forceinline__ void embed_fp64_tile(Pix pix, const Img* __restrict__ img, int B, int Cin, int H, int Wd, int P, const GemmArgs& g) {
+  __shared__ __attribute__((aligned(16))) float sX[16][68], sW[16][68];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int gw = Wd / P, gh = H / P, patches = gw * gh;
+  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+  const int K = Cin * P * P;
+  // loader role: row lr of the tile, 4 consecutive k
+  const int lr = tid >> 2, lk = (tid & 3) * 4;
+  int mrow = m0 + lr;
+  mrow = mrow < g.M ? mrow : g.M - 1;
+  const int b_ = mrow / patches, pr = mrow % patches, py = pr / gw, px = pr % gw;
+  pix.at(img, b_, Cin, H, Wd, P, py, px);
+  const int8_t* wbase = g.W + (long long)(n0 + lr) * g.K + lk;           // rows padded to n_pad, zero beyond N
+  double acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+  for (int k0 = 0; k0 < K; k0 += 16) {
+    const int k = k0 + lk;
+    float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
+    unsigned wv = 0;
+    if (k < K) {                                                          // K is a multiple of 4 (patch_size % 4 == 0)
+      const int c = k / (P * P), rem = k % (P * P), i = rem / P, j = rem % P;
+      xv = pix.load4(c, i, j, H, Wd, Cin);
+      wv = *reinterpret_cast<const unsigned*>(wbase + k0);
+    }
+    __syncthreads();
+    sX[lk + 0][lr] = xv.x; sX[lk + 1][lr] = xv.y; sX[lk + 2][lr] = xv.z; sX[lk + 3][lr] = xv.w;
+    sW[lk + 0][lr] = (float)sx8(wv, 0); sW[lk + 1][lr] = (float)sx8(wv, 1); sW[lk + 2][lr] = (float)sx8(wv, 2); sW[lk + 3][lr] = (float)sx8(wv, 3);
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      const float4 xa = *reinterpret_cast<const float4*>(&sX[kk][ty * 4]);
+      const float4 wa = *reinterpret_cast<const float4*>(&sW[kk][tx * 4]);
+      const double xd[4] = {(double)xa.x, (double)xa.y, (double)xa.z, (double)xa.w};
+      const double wd[4] = {(double)wa.x, (double)wa.y, (double)wa.z, (double)wa.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_fma(xd[i], wd[j], acc[i][j]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + ty * 4 + i;
+    if (m >= g.M) continue;
+    const int bb = m / patches, tok = m % patches + 1;
+    const long long out_row = (long long)bb * (patches + 1) + tok;
+    const int n = n0 + tx * 4;
+    if (n >= g.N) continue;                                               // N is a multiple of 4
+    float q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float y = (float)__builtin_fma(acc[i][j], (double)g.colscale[n + j], (double)g.bias[n + j]);   // ONE rounding
+      const float q1 = sat8f(y * g.ep.inv_s_pe);                          // PatchEmbed.qact
+      const float q2 = sat8f(q1 * g.ep.pe_to_embed);                      // qact_embed (both PoT: exact ratio)
+      const float xs = __builtin_fmaf(q2, g.ep.s_embed, g.ep.pos_deq[(long long)tok * g.N + n + j]);   // + qact_pos(pos_embed)
+      q[j] = rintf(xs / g.ep.s_next[n + j]);                              // qact1 (PTF): IEEE division like the reference
+    }
+    *reinterpret_cast<unsigned*>(reinterpret_cast<int8_t*>(g.out) + out_row * g.ldo + n) = pack4_sat(q[0], q[1], q[2], q[3]);
+  }
+}
+
+
+// the same convolution over uint8 images: every pixel enters the fp64 accumulation as lut[c][byte], the fp32 value the normalised image
+// holds there, so the result equals k_embed_fp32's on that image
+template <int NHWC>
+__global__ __launch_bounds__(256) void k_embed_u8(const uint8_t* __restrict__ img, const float* __restrict__ lut, int B, int Cin, int H, int Wd,
+                                                  int P, GemmArgs g) {
+  extern __shared__ float embed_lut[];
+  for (int i = threadIdx.x; i < Cin * 256; i += blockDim.x) embed_lut[i] = lut[i];
+  __syncthreads();                                  // (the tile loop also syncs before its first LDS write; this one orders the table)
+  EmbedPixU8<NHWC> pix;
+  pix.tab = embed_lut;
+  embed_fp64_tile(pix, img, B, Cin, H, Wd, P, g);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // K1d: the tiled GEMM with LDS-DMA staging (global_load_lds_dwordx4, gfx950).
 //   Why: in the register-staged round-1 kernel (removed) every k-tile moved 16 KB global -> VGPR -> ds_write_b128 -> LDS.  ds_write_b128 sustains ~79 B/clk per
@@ -401,6 +501,17 @@ int p2v_launch_embed_fp32(const float* img, int B, int C, int H, int W, int P, c
   if (g.w4 || g.N % 4 || P % 4) return -1;
   const dim3 grid((unsigned)((g.N + 63) / 64), (unsigned)((g.M + 63) / 64));
   hipLaunchKernelGGL(k_embed_fp32, grid, dim3(256), 0, st, img, B, C, H, W, P, g);
+  CHECK_LAUNCH();
+  return 0;
+}
+
+int p2v_launch_embed_u8(const uint8_t* img, int nhwc, const float* lut, int B, int C, int H, int W, int P, const GemmArgs& g, hipStream_t st) {
+  if (g.w4 || g.N % 4 || P % 4) return -1;
+  if ((size_t)C * 256 * sizeof(float) > 65536) return -3;
+  const dim3 grid((unsigned)((g.N + 63) / 64), (unsigned)((g.M + 63) / 64));
+  const size_t lds = (size_t)C * 256 * sizeof(float);
+  if (nhwc) hipLaunchKernelGGL(k_embed_u8<1>, grid, dim3(256), lds, st, img, lut, B, C, H, W, P, g);
+  else hipLaunchKernelGGL(k_embed_u8<0>, grid, dim3(256), lds, st, img, lut, B, C, H, W, P, g);
   CHECK_LAUNCH();
   return 0;
 }

@@ -70,6 +70,11 @@ int p2v_launch_patchify(const float* img, int B, int C, int H, int W, int P, flo
 int p2v_launch_fill_cls(int8_t* x, int B, int T, int D, const int8_t* cls, hipStream_t st);
 // fp32 image x fake-quantised conv weights (input_quant = False): EMBED epilogue, g.A unused, g.W unpacked int8 codes [n_pad][K]
 int p2v_launch_embed_fp32(const float* img, int B, int C, int H, int W, int P, const GemmArgs& g, hipStream_t st);
+// uint8 input (p2v_forward_u8): the patch matrix through the int8 table [C][256] (-3: table + one patch exceed 64 KB of LDS), and the
+// fp32-image convolution through the fp32 table [C][256]; nhwc: 1 = [B][H][W][C], 0 = [B][C][H][W]
+int p2v_launch_u8_patchify(const uint8_t* img, int B, int C, int H, int W, int P, int nhwc, const int8_t* lut, int8_t* out, int k_pad,
+                           hipStream_t st);
+int p2v_launch_embed_u8(const uint8_t* img, int nhwc, const float* lut, int B, int C, int H, int W, int P, const GemmArgs& g, hipStream_t st);
 int p2v_launch_gemm(int epi, const GemmArgs& g, hipStream_t st);
 // table of the pre-folded RESID epilogue (p2v_epilogue.resid_tab): [ceil(N/128)][6][128] floats; flags: dev [2] preset to {1, 0}
 int p2v_launch_resid_prefold(const p2v_linear& lin, const p2v_epilogue& ep, int N, float* tab, unsigned* flags, hipStream_t st);

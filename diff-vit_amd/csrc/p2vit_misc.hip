@@ -97,6 +97,78 @@ __global__ __launch_bounds__(256) void k_quantize_patchify(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// K0u: the same patch matrix from uint8 images.  The normalised fp32 value of a pixel, and so its code, depends only on (channel, byte):
+// lut[c][v] holds the code k_quantize_patchify writes for it (built on the host, data.uint8_lut), the kernel only gathers.
+// One workgroup = one image, one band of P pixel rows, `Q` consecutive patches of it (the whole band unless it is wide).  The band
+// (NHWC: P runs of Q*P*C bytes; NCHW: C*P runs of Q*P bytes) and the table go to LDS, with 16-byte loads where the runs allow; then every
+// thread assembles 16 output columns (c, i, j order) and writes them with one store (VEC; k_pad % 16 != 0: one dword per thread).
+// ---------------------------------------------------------------------------------------------------
+template <int PT, int NHWC, int VEC>
+__global__ __launch_bounds__(256) void k_u8_patchify(const uint8_t* __restrict__ img, int C, int H, int W, int P_, const int8_t* __restrict__ lut,
+                                                     int8_t* __restrict__ out, int k_pad, int Q) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char u8p_lds[];
+  const int P = PT ? PT : P_;
+  const int gw = W / P, gh = H / P, nseg = (gw + Q - 1) / Q;
+  const int seg = (int)(blockIdx.x % nseg), py = (int)((blockIdx.x / nseg) % gh), b = (int)(blockIdx.x / ((unsigned)nseg * gh));
+  const int px0 = seg * Q, qn = gw - px0 < Q ? gw - px0 : Q, QP = qn * P;
+  unsigned char* sT = u8p_lds;                  // [C][256] codes
+  unsigned char* sB = u8p_lds + C * 256;        // the band: NHWC [P][QP][C], NCHW [C][P][QP]
+  for (int i = threadIdx.x; i < C * 256; i += blockDim.x) sT[i] = (unsigned char)lut[i];
+  const int rows = NHWC ? P : C * P, run = NHWC ? QP * C : QP;       // run: bytes per staged row (a multiple of 4: P % 4 == 0)
+  const long long img0 = (long long)b * C * H * W;
+  auto src = [&](int r) -> const uint8_t* {
+    return NHWC ? img + img0 + ((long long)(py * P + r) * W + px0 * P) * C
+                : img + img0 + ((long long)(r / P) * H + py * P + r % P) * W + px0 * P;
+  };
+  // 16-byte loads when every run starts on a 16-byte boundary and is whole 16-byte pieces (224^2 images: both layouts), else dwords
+  const bool v16 = ((reinterpret_cast<uintptr_t>(src(0)) | (uintptr_t)(NHWC ? W * C : W) | (uintptr_t)run) & 15) == 0;
+  if (v16) {
+    const int per = run >> 4;
+    for (int t = threadIdx.x; t < rows * per; t += blockDim.x) {
+      const int r = t / per, o = (t % per) << 4;
+      *reinterpret_cast<uint4*>(sB + r * run + o) = *reinterpret_cast<const uint4*>(src(r) + o);
+    }
+  } else {
+    const int per = run >> 2;
+    for (int t = threadIdx.x; t < rows * per; t += blockDim.x) {
+      const int r = t / per, o = (t % per) << 2;
+      *reinterpret_cast<unsigned*>(sB + r * run + o) = *reinterpret_cast<const unsigned*>(src(r) + o);
+    }
+  }
+  __syncthreads();
+  const int PP = P * P, CPP = C * PP;
+  constexpr int per = VEC ? 4 : 1;                // dwords per thread and store
+  const int chunks = (k_pad >> 2) / per;
+  int8_t* out0 = out + ((long long)(b * gh + py) * gw + px0) * k_pad;
+  for (int t = threadIdx.x; t < qn * chunks; t += blockDim.x) {
+    const int q = t / chunks, d0 = (t % chunks) * per;
+    unsigned v[per];
+#pragma unroll
+    for (int u = 0; u < per; ++u) {
+      const int col = (d0 + u) * 4;
+      unsigned w = 0;
+      if (col < CPP) {                            // 4 consecutive j of one (c, i): P % 4 == 0
+        const int c = col / PP, rem = col % PP, i = rem / P, j = rem % P;
+        const unsigned char* tab = sT + c * 256;
+        unsigned x0, x1, x2, x3;
+        if (NHWC) {
+          const unsigned char* s = sB + ((i * QP + q * P + j) * C + c);
+          x0 = s[0]; x1 = s[C]; x2 = s[2 * C]; x3 = s[3 * C];
+        } else {
+          const unsigned s = *reinterpret_cast<const unsigned*>(sB + (c * P + i) * QP + q * P + j);
+          x0 = s & 255u; x1 = (s >> 8) & 255u; x2 = (s >> 16) & 255u; x3 = s >> 24;
+        }
+        w = (unsigned)tab[x0] | ((unsigned)tab[x1] << 8) | ((unsigned)tab[x2] << 16) | ((unsigned)tab[x3] << 24);
+      }
+      v[u] = w;
+    }
+    int8_t* dst = out0 + (long long)q * k_pad + d0 * 4;
+    if (VEC) *reinterpret_cast<uint4*>(dst) = make_uint4(v[0], v[per > 1 ? 1 : 0], v[per > 2 ? 2 : 0], v[per > 3 ? 3 : 0]);
+    else *reinterpret_cast<unsigned*>(dst) = v[0];
+  }
+}
+
 // cls rows of the residual stream: constant per model (vit_fquant.py:718-733 applied to cls_token)
 __global__ void k_fill_cls(int8_t* __restrict__ x, int B, int T, int D, const int8_t* __restrict__ cls) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -196,6 +268,29 @@ int p2v_launch_patchify(const float* img, int B, int C, int H, int W, int P, flo
   const int rows_per_block = 8;
   hipLaunchKernelGGL(k_quantize_patchify, dim3((unsigned)((rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0, st, img, B, C, H, W, P,
                      inv_s, out, k_pad, rows_per_block);
+  CHECK_LAUNCH();
+  return 0;
+}
+
+int p2v_launch_u8_patchify(const uint8_t* img, int B, int C, int H, int W, int P, int nhwc, const int8_t* lut, int8_t* out, int k_pad,
+                           hipStream_t st) {
+  const int gw = W / P, gh = H / P, patch_bytes = P * P * C;
+  if (C * 256 + patch_bytes > 65536) return -3;                       // one patch and the table must fit the 64 KB of dynamic LDS
+  int Q = (32768 - C * 256) / patch_bytes;                              // patches per workgroup: the band, or as much of it as fits 32 KB
+  Q = Q < 1 ? 1 : (Q > gw ? gw : Q);
+  const int nseg = (gw + Q - 1) / Q;
+  const unsigned blocks = (unsigned)B * gh * nseg;
+  const size_t lds = (size_t)C * 256 + (size_t)P * Q * P * C;
+  const bool vec = k_pad % 16 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+#define U8P(PT, L, V) hipLaunchKernelGGL((k_u8_patchify<PT, L, V>), dim3(blocks), dim3(256), lds, st, img, C, H, W, P, lut, out, k_pad, Q)
+#define U8P_L(PT, V) do { if (nhwc) U8P(PT, 1, V); else U8P(PT, 0, V); } while (0)
+  if (!vec) U8P_L(0, 0);
+  else if (P == 16) U8P_L(16, 1);
+  else if (P == 8) U8P_L(8, 1);
+  else if (P == 4) U8P_L(4, 1);
+  else U8P_L(0, 1);
+#undef U8P_L
+#undef U8P
   CHECK_LAUNCH();
   return 0;
 }

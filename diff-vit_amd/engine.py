@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(_HERE, 'csrc', 'libp2vit_hip.so')
 P2V_ABI_VERSION = 6
 EPI_REQUANT, EPI_GELU, EPI_RESID, EPI_EMBED, EPI_HEAD = 0, 1, 2, 3, 4
 E_ARG, E_BITS, E_SHAPE, E_UNSUPPORTED, E_WORKSPACE, E_LAUNCH, E_STATE = -1, -2, -3, -4, -5, -6, -7
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1                  # uint8 image layouts of p2v_forward_u8 / p2v_u8_patchify
+LAYOUTS = {'NCHW': LAYOUT_NCHW, 'NHWC': LAYOUT_NHWC}
 
 KERNEL_KINDS = ('patchify', 'gemm_embed', 'fill_cls', 'layernorm', 'gemm_qkv', 'attention', 'gemm_proj', 'gemm_fc1',
                 'gemm_fc2', 'gemm_head', 'ln_gemm_qkv', 'ln_gemm_fc1', 'event_gap')
@@ -134,6 +136,8 @@ def lib():
     L.p2v_forward_profile_begin.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(_p)]
     L.p2v_forward_profile_end.argtypes = [_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), _i]
     L.p2v_quantize_patchify.argtypes = [_p, _i, _i, _i, _i, _i, _f, _p, _i, _p]
+    L.p2v_forward_u8.argtypes = [_p, _p, _i, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _p]
+    L.p2v_u8_patchify.argtypes = [_p, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p]
     L.p2v_gemm_i8.argtypes = [_i, _p, _i, _i, _i, _i, C.POINTER(Linear), C.POINTER(Epilogue), _p, _i, _p, _p]
     L.p2v_int_layernorm.argtypes = [_p, _ll, _i, _i, C.POINTER(Ln), _p, _ll, _p]
     L.p2v_lis_attention.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Attn), _p, _p, _p]

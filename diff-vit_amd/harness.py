@@ -51,6 +51,9 @@ def build_parser():
     p.add_argument('--n-val', default=500, type=int, help='number of synthetic validation images')
     p.add_argument('--bits', default=8, type=int, choices=[4, 8], help='uniform bit_config for the validation run')
     p.add_argument('--calib-on', default='host', choices=['host', 'model'], help="where the calibration pass runs: 'host' reproduces the reference's exponents exactly")
+    p.add_argument('--uint8-input', default=False, action='store_true',
+                   help='loaders yield uint8 NHWC crops (a quarter of the bytes to copy) and the model normalises them on the device '
+                        '(forward_uint8 with the family\'s MODEL_STATS; logits identical to the fp32 loaders)')
     p.add_argument('--search-pop', default=25, type=int, help='--mixed: population size (test_quant.py:340)')
     p.add_argument('--search-iter', default=8, type=int, help='--mixed: evolutionary iterations (test_quant.py:343)')
     p.add_argument('--search-max-configs', default=50, type=int, help='--mixed: Pareto candidates kept (test_quant.py:281)')
@@ -74,13 +77,27 @@ def _is_swin(model):
     return isinstance(model, SwinTransformer)
 
 
-def _forward(model, data, bit_config=None):
+def _forward(model, data, bit_config=None, stats=None):
     """``model(data, bit_config, plot)`` -> (output, FLOPs, distance).  The reference's Swin returns the logits alone and takes
-    no bit_config (swin_quant.py:813-817): a uniform bit_config selects its weight width, FLOPs/distance stay empty."""
+    no bit_config (swin_quant.py:813-817): a uniform bit_config selects its weight width, FLOPs/distance stay empty.
+    ``stats`` = (mean, std): ``data`` is a uint8 NHWC batch for ``forward_uint8``."""
     if _is_swin(model):
         bits = int(bit_config[0]) if bit_config else 8
+        if stats is not None:
+            return model.forward_uint8(data, bits, stats[0], stats[1], 'NHWC'), [], []
         return model(data, bits=bits), [], []
+    if stats is not None:
+        return model.forward_uint8(data, bit_config, stats[0], stats[1], 'NHWC')
     return model(data, bit_config, False)
+
+
+def uint8_stats(args):
+    """(mean, std) of the model family (data.MODEL_STATS) when ``--uint8-input`` is on, else None"""
+    if not getattr(args, 'uint8_input', False):
+        return None
+    from .data import MODEL_STATS, model_family
+    mean, std, _ = MODEL_STATS[model_family(args.model)]
+    return mean, std
 
 
 def seed(seed=0):
@@ -161,8 +178,8 @@ class SyntheticLoader:
     """ImageNet-shaped batches from the deterministic generator; labels = argmax of a float teacher pass are supplied
     by the caller (there is no dataset offline), default labels are a fixed pseudo-random class per image."""
 
-    def __init__(self, n, batch_size, img_size=224, num_classes=1000, seed=0, device='cpu', targets=None):
-        self.n, self.bs, self.img, self.seed, self.device = n, batch_size, img_size, seed, device
+    def __init__(self, n, batch_size, img_size=224, num_classes=1000, seed=0, device='cpu', targets=None, uint8=False):
+        self.n, self.bs, self.img, self.seed, self.device, self.uint8 = n, batch_size, img_size, seed, device, uint8
         self.targets = targets if targets is not None else torch.from_numpy(
             (synth._stream(seed, 'labels', n) % np.uint64(num_classes)).astype(np.int64))
 
@@ -172,15 +189,18 @@ class SyntheticLoader:
     def __iter__(self):
         for i in range(0, self.n, self.bs):
             k = min(self.bs, self.n - i)
-            yield synth.images(self.seed, k, self.img, offset=i).to(self.device), self.targets[i:i + k].to(self.device)
+            gen = synth.images_uint8 if self.uint8 else synth.images         # uint8: NHWC crops, as a loader of PIL images yields them
+            yield gen(self.seed, k, self.img, offset=i).to(self.device), self.targets[i:i + k].to(self.device)
 
 
 class DevicePrefetcher:
-    """``for data, target in DevicePrefetcher(loader, device)``: the batches of ``loader`` on ``device``, batch i + 1 copied while batch i
-    runs.  The reference's loop does ``data.cuda()`` and then the forward, one after the other (test_quant.py:425-431); at 256 x 3 x 224^2 fp32
+    """``for data, target in DevicePrefetcher(loader, device)``: the batches of ``loader`` on ``device`` (any dtype: fp32 images or the
+    uint8 crops of ``forward_uint8``), batch i + 1 copied while batch i runs.  The reference's loop does ``data.cuda()`` and then the forward, one after the other (test_quant.py:425-431); at 256 x 3 x 224^2 fp32
     the copy (154 MB, 2.8 ms at 55 GB/s) is longer than the DeiT-S forward (2.5 ms).  The copies run on ``engine.copy_stream`` - a stream
     probed to have a dispatch pipe of its own, which the sliced forward then leaves alone: 82 k img/s from pinned host memory against 45 k
-    for copy-then-forward and 50 k for a double buffer on an arbitrary fifth stream (profiles/r04_pcie.txt).  Pinned batches
+    for copy-then-forward and 50 k for a double buffer on an arbitrary fifth stream (profiles/r04_pcie.txt).  uint8 batches for
+    ``forward_uint8`` (38.5 MB instead of 154 MB): 102 k img/s against 87 k for the same images as fp32, 3 % below resident input
+    (profiles/uint8_input.txt).  Pinned batches
     (``DataLoader(pin_memory=True)``, as the reference's loaders are) copy asynchronously; pageable ones work, without the overlap."""
 
     def __init__(self, loader, device):
@@ -230,10 +250,11 @@ def validate(args, val_loader, model, criterion, device, bit_config=None):
     model.eval()
     val_start_time = end = time.time()
     n_img, fwd = 0, 0.0
+    stats = uint8_stats(args)
     for i, (data, target) in enumerate(DevicePrefetcher(val_loader, device)):
         t0 = time.time()
         with torch.no_grad():
-            output, FLOPs, distance = _forward(model, data, bit_config)
+            output, FLOPs, distance = _forward(model, data, bit_config, stats)
         if data.is_cuda:
             torch.cuda.synchronize()
         fwd += time.time() - t0
@@ -280,19 +301,23 @@ def main(argv=None):
     if args.real_data:
         # test_quant.py:118-144: ImageFolder val / train trees with the model family's mean / std / crop
         from .data import build_loaders
-        loader, train_loader = build_loaders(args.data, args.model, args.val_batchsize, args.calib_batchsize, 0)
+        loader, train_loader = build_loaders(args.data, args.model, args.val_batchsize, args.calib_batchsize, 0, uint8=args.uint8_input)
     else:
         # labels: the float model's own top-1 ("agreement with fp32"), the metric BASELINE.json names besides images/sec
-        loader = SyntheticLoader(args.n_val, args.val_batchsize, arch['img_size'], arch['num_classes'], args.seed, device)
+        u8 = args.uint8_input
+        loader = SyntheticLoader(args.n_val, args.val_batchsize, arch['img_size'], arch['num_classes'], args.seed, device, uint8=u8)
         with torch.no_grad():
-            tgt = torch.cat([_forward(model, d)[0].argmax(1).cpu() for d, _ in loader])
-        loader = SyntheticLoader(args.n_val, args.val_batchsize, arch['img_size'], arch['num_classes'], args.seed, device, tgt)
+            tgt = torch.cat([_forward(model, d, None, uint8_stats(args))[0].argmax(1).cpu() for d, _ in loader])
+        loader = SyntheticLoader(args.n_val, args.val_batchsize, arch['img_size'], arch['num_classes'], args.seed, device, tgt, uint8=u8)
     criterion = nn.CrossEntropyLoss().to(device)
     bit_config = None
     if args.quant:
         if args.mode == 0 and train_loader is not None:
             print('Calibrating with real data...')                       # test_quant.py:214-233, mode 0: the first training batch
             calib_data = next(iter(train_loader))[0].to(device)
+            if calib_data.dtype == torch.uint8:                          # --uint8-input: the normalised batch, through the fp32 table
+                from .data import expand_uint8, uint8_lut
+                calib_data = expand_uint8(calib_data, uint8_lut(*uint8_stats(args)), 'NHWC')
         else:
             print('Calibrating with Gaussian noise...')
             calib_data = synth.images(args.seed + 1, args.calib_batchsize, arch['img_size']).to(device)

@@ -166,7 +166,8 @@ class FrozenPlan:
         epi.s_next = E.ptr(self._dev(s_res))
         epi.pos_deq = E.ptr(self._dev(pos_deq))
         epi.patches = self.patches
-        E.check(L.p2v_plan_set_embed(self._handle, float(1.0 / s_in) if self.input_quant else 0.0, C.byref(epi),
+        self.inv_s_input = float(1.0 / s_in) if self.input_quant else 0.0
+        E.check(L.p2v_plan_set_embed(self._handle, self.inv_s_input, C.byref(epi),
                                      E.ptr(self._dev(cls_codes, torch.int8))))
         # ---- blocks ----------------------------------------------------------------------------
         for i in range(self.depth):
@@ -284,6 +285,71 @@ class FrozenPlan:
         if tuple(out.shape) != (B, self.arch['num_classes']) or out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous():
             raise AssertionError('out must be a contiguous fp32 [%d, %d] tensor on %s' % (B, self.arch['num_classes'], self.device))
 
+    def input_lut(self, lut_f32):
+        """the device table ``forward_uint8`` reads for the fp32 table ``lut_f32`` [C, 256] (data.uint8_lut): its codes under this plan's
+        input scale (int8, data.uint8_lut_i8), or the fp32 values themselves for a plan without an input QAct (input_quant=False)."""
+        from .data import uint8_lut_i8
+        lut_f32 = lut_f32.detach().float().cpu()
+        t = uint8_lut_i8(lut_f32, self.inv_s_input) if self.input_quant else lut_f32
+        return t.contiguous().to(self.device)
+
+    def _check_u8(self, images, lut, bit_config, layout):
+        """``_check`` for uint8 images in ``layout`` ('NHWC' [B, H, W, C] or 'NCHW' [B, C, H, W]) and the device table of ``input_lut``:
+        the C ABI trusts the geometry, the table's size and type, and the device, so every one is checked here (same exception classes)."""
+        a, S, Cin = self.arch, self.arch['img_size'], self.in_chans
+        if layout not in E.LAYOUTS:
+            raise AssertionError("layout must be 'NHWC' or 'NCHW', got %r" % (layout,))
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8:
+            raise AssertionError('forward_uint8 takes uint8 images, got %s (fp32 images go to forward)' % getattr(images, 'dtype', type(images)))
+        want = (S, S, Cin) if layout == 'NHWC' else (Cin, S, S)
+        if images.dim() != 4 or tuple(images.shape[1:]) != want:
+            raise AssertionError('uint8 images in layout %s must be [B, %d, %d, %d], got %s' % ((layout,) + want + (tuple(images.shape),)))
+        if not images.is_cuda:
+            raise RuntimeError('the quantized forward runs on the HIP engine only: move the input to the GPU')
+        if images.device != self.device:
+            raise RuntimeError('images live on %s, the frozen plan on %s' % (images.device, self.device))
+        if images.shape[0] < 1:
+            raise AssertionError('empty batch')
+        lut_dtype = torch.int8 if self.input_quant else torch.float32
+        if (not isinstance(lut, torch.Tensor) or lut.dtype != lut_dtype or tuple(lut.shape) != (Cin, 256) or lut.device != self.device
+                or not lut.is_contiguous()):
+            raise AssertionError('lut must be a contiguous %s [%d, 256] tensor on %s (FrozenPlan.input_lut)' % (lut_dtype, Cin, self.device))
+        if bit_config is None:
+            raise ValueError('None is not in list')        # bit_pool.index(None), vit_fquant.py:282
+        cfg = (C.c_int8 * len(bit_config))(*[int(b) if -128 <= int(b) <= 127 else 127 for b in bit_config])
+        return images.contiguous(), cfg
+
+    def forward_uint8(self, images, lut, bit_config, layout='NHWC', out=None, stop_after=-1):
+        """``forward`` on uint8 images: p2v_forward_u8 reads them through ``lut`` (``input_lut``) in its first launch; the logits equal
+        ``forward`` on the fp32 images ``data.normalize_uint8`` makes of them, bit for bit (so does the patch matrix after stop_after=1)."""
+        images, cfg = self._check_u8(images, lut, bit_config, layout)
+        B = images.shape[0]
+        with torch.cuda.device(self.device):
+            ws = self.workspace(B)
+            if out is None:
+                out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
+            else:
+                self._check_out(out, B)
+            E.check(E.lib().p2v_forward_u8(self._handle, E.ptr(images), E.LAYOUTS[layout], E.ptr(lut), B, cfg, len(bit_config), E.ptr(out),
+                                           E.ptr(ws), ws.numel(), stop_after, E.stream_ptr(self.device)))
+        return out
+
+    def forward_uint8_streams(self, images, lut, bit_config, out, layout='NHWC', n_streams=3, slices=None):
+        """``forward_streams`` on uint8 images: the same slices (contiguous in the batch dimension in both layouts), each one
+        p2v_forward_u8 call."""
+        images, cfg = self._check_u8(images, lut, bit_config, layout)
+        B = images.shape[0]
+        n_streams = min(n_streams, E.compute_side_streams(self.device))
+        sizes = list(slices) if slices is not None else self.slice_sizes(B, n_streams)
+        if sum(sizes) != B or min(sizes) < 1:
+            raise AssertionError('slices %r do not cover a batch of %d' % (sizes, B))
+        self._check_out(out, B)
+        if len(sizes) == 1:
+            return self.forward_uint8(images, lut, bit_config, layout, out=out)
+        L, handle, n_cfg, lay, lp = E.lib(), self._handle, len(bit_config), E.LAYOUTS[layout], E.ptr(lut)
+        return self._run_slices(images, sizes, out, n_streams,
+                                lambda xi, n_i, oi, ws, ws_n, st: L.p2v_forward_u8(handle, xi, lay, lp, n_i, cfg, n_cfg, oi, ws, ws_n, -1, st))
+
     def forward(self, images, bit_config, stop_after=-1, out=None, taps=None):
         """images: fp32 [B,C,H,W] on the plan's device -> fp32 logits [B, classes] (int8 grid * act_out scale).
         ``taps`` (dict): filled with 'qkv_output' / 'fc1_output' -> list of fp32 [B, tokens, 3D] / [B, tokens, hidden] tensors per
@@ -379,6 +445,13 @@ class FrozenPlan:
         self._check_out(out, B)
         if len(sizes) == 1:
             return self.forward(images, bit_config, out=out)
+        L, handle, n_cfg = E.lib(), self._handle, len(bit_config)
+        return self._run_slices(images, sizes, out, n_streams,
+                                lambda xi, n_i, oi, ws, ws_n, st: L.p2v_forward(handle, xi, n_i, cfg, n_cfg, oi, ws, ws_n, -1, st))
+
+    def _run_slices(self, images, sizes, out, n_streams, launch):
+        """the scheduling of ``forward_streams``: contiguous batch slices (``sizes``, more than one) on their own workspaces, round robin
+        over the side streams and the caller's stream; ``launch(images_ptr, n, out_ptr, ws_ptr, ws_bytes, stream_ptr)`` enqueues one slice"""
         with torch.cuda.device(self.device):
             n_side = min(len(sizes), max(n_streams, 1))
             self._streams = E.side_streams(self.device, n_side)         # the process's shared side streams of this device, never new ones
@@ -401,13 +474,13 @@ class FrozenPlan:
                     used.append(st)
                 per_stream[j].append((E.ptr(images[lo:hi]), n_i, E.ptr(out[lo:hi]), E.ptr(self._ws_multi[i]), self._ws_multi[i].numel(),
                                       C.c_void_p(st.cuda_stream)))
-            n_cfg, handle, dev_index = len(bit_config), self._handle, self.device.index
+            dev_index = self.device.index
 
             def enqueue(calls, worker):
                 if worker:
                     torch.cuda.set_device(dev_index)                 # (the current device is a per-thread setting)
                 for xi, n_i, oi, ws, ws_n, st_ptr in calls:
-                    E.check(L.p2v_forward(handle, xi, n_i, cfg, n_cfg, oi, ws, ws_n, -1, st_ptr))
+                    E.check(launch(xi, n_i, oi, ws, ws_n, st_ptr))
 
             # One host thread per side stream (the C call releases the interpreter lock; p2v_forward only reads the plan): the four launch
             # sequences reach their queues together instead of one after the other - a synchronous step (forward, then read the logits) takes

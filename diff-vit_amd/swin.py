@@ -340,6 +340,26 @@ class SwinTransformer(nn.Module):
         return self.act_out(self.head(self.forward_features(x)))
 
 
+    def forward_uint8(self, images, bits=8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), layout='NHWC'):
+        """``forward`` on uint8 images ([B, H, W, C] for 'NHWC', [B, C, H, W] for 'NCHW'; default statistics: data.MODEL_STATS['swin'])
+        normalised on the device: the logits of ``forward(data.normalize_uint8(images.cpu(), mean, std, layout).cuda(), bits)``, bit for
+        bit.  Quant state: the patch gather reads the bytes through a [C, 256] table of codes (p2v_u8_patchify); any other state expands
+        them through the fp32 table and runs ``forward``."""
+        from .data import expand_uint8, uint8_lut
+        if len(mean) != self.in_chans or len(std) != self.in_chans:
+            raise ValueError('mean / std have %d / %d entries, the model %d input channels' % (len(mean), len(std), self.in_chans))
+        lut = uint8_lut(mean, std, self.in_chans)
+        if self.quant and all(m.quant and not m.calibrate for m in self._q_modules()):
+            if self._plan is None or self._plan.bits != bits:
+                self.freeze(images.device if images.is_cuda else None, bits=bits)
+            cache = self._plan.__dict__.setdefault('_u8_luts', {})       # device tables: they go with the plan (input scale)
+            key = lut.numpy().tobytes()
+            if key not in cache:
+                cache[key] = self._plan.input_lut(lut)
+            return self._plan.forward_uint8(images, cache[key], layout)
+        return self.forward(expand_uint8(images, lut, layout), bits)
+
+
 def _factory(name, embed_dim, depths, num_heads, img_size=224):
     def make(pretrained=False, quant=False, calibrate=False, cfg=None, **kwargs):
         if cfg is None:

@@ -372,16 +372,61 @@ class SwinPlan:
             raise AssertionError("Input image size (%d*%d) doesn't match model (%d*%d)." % (images.shape[2], images.shape[3], a['img_size'], a['img_size']))
         return images
 
+    def input_lut(self, lut_f32):
+        """the int8 table [C, 256] ``forward_uint8`` reads: the codes of data.uint8_lut's values under qact_input (data.uint8_lut_i8)"""
+        from .data import uint8_lut_i8
+        return uint8_lut_i8(lut_f32.detach().float().cpu(), 1.0 / self.s_in).contiguous().to(self.device)
+
+    def _replay_u8(self, images, lut, layout, slot):
+        """the recorded sequence with its first launch replaced: p2v_u8_patchify writes the same patch matrix into the recorded buffer"""
+        with torch.cuda.device(self.device):
+            B = images.shape[0]
+            key = (B, slot, True)
+            if key not in self._recorded:
+                self._recorded[key] = self._record(B, fused=True)
+            r = self._recorded[key]
+            out = torch.empty(B, self.head['N'], dtype=torch.float32, device=self.device)
+            p = r['ops'][0]
+            L, st = E.lib(), E.stream_ptr(self.device)
+            E.check(L.p2v_u8_patchify(E.ptr(images), E.LAYOUTS[layout], E.ptr(lut), B, p.i1, p.i2, p.i3, p.i4, p.out, p.i5, st))
+            r['ops'][r['n'] - 1].out = E.ptr(out)
+            E.check(L.p2v_run_ops(C.cast(C.byref(r['ops'], C.sizeof(E.Op)), C.POINTER(E.Op)), r['n'] - 1, st))
+            return out
+
+    def forward_uint8(self, images, lut, layout='NHWC', n_streams=3, slices=None):
+        """``forward`` on uint8 images ([B, S, S, C] for 'NHWC', [B, C, S, S] for 'NCHW') read through ``lut`` (``input_lut``), single or
+        sliced like ``forward``: the logits equal ``forward`` on the images data.normalize_uint8 makes of them."""
+        a, S, Cin = self.arch, self.arch['img_size'], self.in_chans
+        if layout not in E.LAYOUTS:
+            raise AssertionError("layout must be 'NHWC' or 'NCHW', got %r" % (layout,))
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8:
+            raise AssertionError('forward_uint8 takes uint8 images, got %s (fp32 images go to forward)' % getattr(images, 'dtype', type(images)))
+        want = (S, S, Cin) if layout == 'NHWC' else (Cin, S, S)
+        if images.dim() != 4 or tuple(images.shape[1:]) != want or images.shape[0] < 1:
+            raise AssertionError('uint8 images in layout %s must be [B, %d, %d, %d], got %s' % ((layout,) + want + (tuple(images.shape),)))
+        if images.device != self.device:
+            raise RuntimeError('images must live on %s' % self.device)
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.int8 or tuple(lut.shape) != (Cin, 256) or lut.device != self.device or not lut.is_contiguous():
+            raise AssertionError('lut must be a contiguous int8 [%d, 256] tensor on %s (SwinPlan.input_lut)' % (Cin, self.device))
+        images = images.contiguous()
+        return self._sliced(images, n_streams, slices, lambda x, slot: self._replay_u8(x, lut, layout, slot))
+
     def forward(self, images, taps=None, n_streams=3, slices=None):
         """images fp32 [B, in_chans, S, S] on the plan's device -> logits fp32 [B, classes] (act_out grid).  One C call replays
         the recorded launch sequence; a large batch runs as ``n_streams`` contiguous slices on their own HIP streams (images are
         independent), like the ViT plan (three: Swin-B at 256 images 25.1 k img/s against 24.6 k on two, same call, profiles/r04_slices.txt).
         ``slices``: explicit slice sizes; slices beyond ``n_streams`` run on the caller's stream."""
         images = self._check_images(images)
+        if taps is not None:
+            return self._replay(images, 0, taps)
+        return self._sliced(images, n_streams, slices, self._replay)
+
+    def _sliced(self, images, n_streams, slices, replay):
+        """the batch slicing of ``forward``; ``replay(images, slot)`` runs one slice on the current stream"""
         B = images.shape[0]
         n_streams = min(n_streams, E.compute_side_streams(self.device))       # (one less while an input pipeline copies on engine.copy_stream)
-        if taps is not None or n_streams <= 1 or (slices is None and B < 16 * n_streams):
-            return self._replay(images, 0, taps)
+        if n_streams <= 1 or (slices is None and B < 16 * n_streams):
+            return replay(images, 0)
         if slices is None:
             step = (B + n_streams - 1) // n_streams
             slices = [min(step, B - i * step) for i in range(n_streams) if i * step < B]
@@ -400,7 +445,7 @@ class SwinPlan:
             if worker:
                 torch.cuda.set_device(self.device)     # (current device and current stream are per-thread settings)
             with torch.cuda.stream(self._streams[i]):
-                return self._replay(parts[i], i + 1)
+                return replay(parts[i], i + 1)
 
         # one host thread per side stream once the launch sequences are recorded (the replay is one C call of ~1 ms of host time per slice),
         # like FrozenPlan.forward_streams; slices beyond the side streams run on the caller's own stream (slot 0: its single-stream record)
@@ -408,10 +453,10 @@ class SwinPlan:
         recorded = all((parts[i].shape[0], i + 1, True) in self._recorded for i in range(n_side))
         if E.THREADED_ENQUEUE and recorded and not torch.cuda.is_current_stream_capturing():
             futs = [E.enqueue_pool().submit(on_side_stream, i, True) for i in range(n_side)]
-            tail = [self._replay(xi, 0) for xi in parts[n_side:]]
+            tail = [replay(xi, 0) for xi in parts[n_side:]]
             outs = [f.result() for f in futs] + tail
         else:
-            outs = [on_side_stream(i, False) for i in range(n_side)] + [self._replay(xi, 0) for xi in parts[n_side:]]
+            outs = [on_side_stream(i, False) for i in range(n_side)] + [replay(xi, 0) for xi in parts[n_side:]]
         for st in self._streams[:min(n_streams, len(slices))]:
             cur.wait_stream(st)
         for o in outs:

@@ -68,6 +68,20 @@ def images(seed: int, batch: int, img_size: int = 224, in_chans: int = 3, offset
     return torch.stack(out) if out else torch.zeros(0, in_chans, img_size, img_size)
 
 
+def images_uint8(seed: int, batch: int, img_size: int = 224, in_chans: int = 3, offset: int = 0) -> torch.Tensor:
+    """uint8 batch, NHWC [batch, img_size, img_size, in_chans] (what a loader of PIL crops collates to): every byte from the counter
+    stream with a per-image, per-channel brightness (the top byte of a word, scaled into [lo, lo + span)) so that images differ in their
+    channel means as photographs do.  Image i of the stream is independent of the batch size it is requested in."""
+    out = np.empty((batch, img_size, img_size, in_chans), dtype=np.uint8)
+    for i in range(batch):
+        tag = 'image_u8/%d' % (offset + i)
+        w = (_stream(seed, tag, img_size * img_size * in_chans) >> np.uint64(56)).astype(np.int64).reshape(img_size, img_size, in_chans)
+        lo = (_stream(seed, tag + '/lo', in_chans) >> np.uint64(58)).astype(np.int64)                  # 0 .. 63
+        span = 128 + (_stream(seed, tag + '/span', in_chans) >> np.uint64(57)).astype(np.int64)        # 128 .. 255
+        out[i] = np.minimum(lo + (w * span) // 256, 255).astype(np.uint8)
+    return torch.from_numpy(out)
+
+
 ARCHS = {
     # name: (img, patch, dim, depth, heads, classes, mlp_ratio)  -- vit_fquant.py:802-933
     'micro': dict(img_size=32, patch_size=8, embed_dim=64, depth=2, num_heads=2, num_classes=10, mlp_ratio=4.0),

@@ -508,6 +508,41 @@ class VisionTransformer(nn.Module):
         return x, FLOPs, global_distance
 
 
+    def forward_uint8(self, images, bit_config, mean, std, layout='NHWC'):
+        """``forward`` on uint8 images ([B, H, W, C] for layout 'NHWC', [B, C, H, W] for 'NCHW') that the device normalises with
+        ``mean`` / ``std``: the same (logits, FLOPs, distance) as ``forward(data.normalize_uint8(images.cpu(), mean, std, layout).cuda(),
+        bit_config)``, bit for bit.  The fused engine reads the bytes through a [C, 256] table of codes (p2v_forward_u8); every other
+        state (float, calibrating, -1 entries, forward hooks, capture_taps) expands them through the fp32 table and runs ``forward``."""
+        lut = self._uint8_lut(mean, std)
+        has_fp = bit_config is not None and any(int(b) == -1 for b in bit_config)
+        if self._fused() and not has_fp and not self.capture_taps and not any(m._forward_hooks for m in self.linear_modules()):
+            if bit_config is None:
+                raise ValueError('None is not in list')          # bit_pool.index(None), vit_fquant.py:282
+            if self._plan is None:
+                self.freeze(images.device if images.is_cuda else None)
+            cache = self._plan.__dict__.setdefault('_u8_luts', {})       # device tables: they go with the plan (input scale)
+            key = lut.numpy().tobytes()
+            if key not in cache:
+                cache[key] = self._plan.input_lut(lut)
+            bits = [int(b) for b in bit_config]
+            if images.shape[0] >= 64:       # the slices of forward (FrozenPlan.slice_sizes)
+                out = torch.empty(images.shape[0], self.num_classes, dtype=torch.float32, device=self._plan.device)
+                return self._plan.forward_uint8_streams(images, cache[key], bits, out, layout, 3), self.flops(), []
+            return self._plan.forward_uint8(images, cache[key], bits, layout), self.flops(), []
+        from .data import expand_uint8
+        return self.forward(expand_uint8(images, lut, layout), bit_config)
+
+    def _uint8_lut(self, mean, std):
+        """data.uint8_lut for these statistics, cached per (mean, std) (a pure function of them)"""
+        cache = self.__dict__.setdefault('_u8_tables', {})
+        key = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
+        if key not in cache:
+            from .data import uint8_lut
+            if len(key[0]) != self.in_chans or len(key[1]) != self.in_chans:
+                raise ValueError('mean / std have %d / %d entries, the model %d input channels' % (len(key[0]), len(key[1]), self.in_chans))
+            cache[key] = uint8_lut(mean, std, self.in_chans)
+        return cache[key]
+
     def linear_modules(self):
         """the QConv2d / QLinear modules in bit_config order (= named_modules order): patch_embed.proj, then qkv, proj, fc1, fc2 of
         every block, then head."""

@@ -278,6 +278,22 @@ int p2v_forward_taps(p2v_plan* plan, const float* images, int batch, const int8_
 int p2v_forward_linear_taps(p2v_plan* plan, const float* images, int batch, const int8_t* bit_config, int n_cfg,
                             float* logits, void* ws, size_t ws_bytes, float* const* taps, void* stream);
 
+/* ---- uint8 input (additive: no structure, existing entry point or P2V_ABI_VERSION changes; a binding finds it by its symbols) ----------
+ * A loader hands over the uint8 crop (what PIL / numpy collate to) instead of the ToTensor + Normalize output.  The normalised value of a
+ * pixel depends only on (channel, byte), so the caller passes a LOOKUP TABLE, dev [in_chans][256], built on the host with the loader's own
+ * fp32 operations: x = (v / 255.0f - mean[c]) / std[c], two IEEE divisions (data.normalize_uint8 / data.uint8_lut in the Python package).
+ *   - plan with an input QAct (inv_s_input > 0): int8 lut[c][v] = clamp(rne(x * inv_s_input), -128, 127), the code k_quantize_patchify
+ *     writes for x;
+ *   - plan with inv_s_input == 0 (input_quant = False): fp32 lut[c][v] = x, the value the fp32-image convolution reads.
+ * The kernels only gather through the table, so the logits equal p2v_forward's on the normalised fp32 batch, bit for bit.  `images`
+ * starts on a 4-byte boundary; the table may be anywhere. */
+enum { P2V_LAYOUT_NCHW = 0, P2V_LAYOUT_NHWC = 1 };   /* [B][C][H][W] / [B][H][W][C] uint8 */
+
+/* p2v_forward on uint8 images: same workspace (p2v_workspace_bytes), same launch sequence after the input stage, same stop_after
+ * numbering (stop_after = 1 leaves the patch matrix in the "patches" buffer).  P2V_E_ARG: null images / lut, unknown layout. */
+int p2v_forward_u8(p2v_plan* plan, const uint8_t* images, int layout, const void* lut, int batch, const int8_t* bit_config, int n_cfg,
+                   float* logits, void* workspace, size_t workspace_bytes, int stop_after, void* stream);
+
 /* Kernel kinds reported by p2v_forward_profile. */
 enum {
   P2V_K_PATCHIFY = 0, P2V_K_GEMM_EMBED = 1, P2V_K_FILL_CLS = 2, P2V_K_LAYERNORM = 3, P2V_K_GEMM_QKV = 4,
@@ -317,6 +333,12 @@ long long p2v_workspace_view(const p2v_plan* plan, int batch, const char* name);
  * columns [C*P*P, k_pad) are zeroed. */
 int p2v_quantize_patchify(const float* img, int batch, int chans, int height, int width, int patch,
                           float inv_s, int8_t* out, int k_pad, void* stream);
+
+/* p2v_quantize_patchify from uint8 images (layout P2V_LAYOUT_*) through lut_i8 (dev int8 [chans][256], see p2v_forward_u8): byte-equal to
+ * it on the normalised fp32 images, padding columns included.  One workgroup per (image, band of `patch` pixel rows); the band and the
+ * table are staged in LDS, so chans * 256 + chans * patch^2 bytes must fit 64 KB (P2V_E_UNSUPPORTED beyond). */
+int p2v_u8_patchify(const uint8_t* img, int layout, const void* lut_i8, int batch, int chans, int height, int width, int patch,
+                    int8_t* out, int k_pad, void* stream);
 
 /* out = epilogue(A[M][K] . W[N][K]^T): int8 MFMA (v_mfma_i32_32x32x32_i8), fp32 epilogue in the
  * reference's operation order.  lda/ldo in elements.  `out` is int8 [M][ldo] except HEAD (fp32 [M][ldo]);
