@@ -134,7 +134,7 @@ __global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 :
   // with the same single rounding; the NEGATED code is produced (round-half-even and the clamp are symmetric).
   const float nmm = -(a.at.qk_scale * (a.at.s_qkv_sq * a.at.inv_s_attn));
   const float avm = a.at.av_mul * P2V_PROB_SCALE;        // the probabilities enter the P.V product scaled by 2^-111 (lis_prob_pair); exact, checked by the launcher
-  const int nqb = (N + 15) >> 4;
+  const int nqb = ((a.nq > 0 && a.nq < N ? a.nq : N) + 15) >> 4;        // a.nq: only the first query rows are wanted (whole 16-row blocks)
   const int nwaves = (int)(blockDim.x >> 6);
   // the Q fragment of a wave's first query block is requested before the barrier and the one of its next block a block ahead: its
   // global-memory latency overlaps the staging wait / the arithmetic of the current block

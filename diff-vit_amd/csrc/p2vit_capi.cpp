@@ -119,6 +119,8 @@ extern int g_gemm_tile;
 extern int g_resid_pre;
 extern int g_attn_stream;
 extern int g_ln_pre;
+extern int g_gemm_rows;
+int g_cls_rows = 1;       // P2V_CLS_ROWS=0: the last block of p2v_forward computes every row, as the other blocks do (A/B and parity runs)
 // Tuning / A-B switches read once per process (first plan or first version query).  None of them changes results:
 // P2V_LN_GENERIC forces the generic LayerNorm chain (bit-identical to the fast one, both are tested).
 static void read_env_once() {
@@ -139,6 +141,10 @@ static void read_env_once() {
   if (e) g_ln_pre = atoi(e) != 0;
   e = getenv("P2V_RESID_PRE");
   if (e) g_resid_pre = atoi(e) != 0;
+  e = getenv("P2V_GEMM_ROWS");
+  if (e && atoi(e) >= 0 && atoi(e) <= 2) g_gemm_rows = atoi(e);
+  e = getenv("P2V_CLS_ROWS");
+  if (e) g_cls_rows = atoi(e) != 0;
   e = getenv("P2V_LN_ROWS");
   if (e && atoi(e) >= 1 && atoi(e) <= 64) g_ln_rows = atoi(e);
   e = getenv("P2V_LN_GENERIC");
@@ -161,6 +167,8 @@ int p2v_set_tuning(const char* name, int value) {
   if (!strcmp(name, "ln_pre")) { g_ln_pre = value != 0; return P2V_OK; }
   if (!strcmp(name, "attn_stream")) { g_attn_stream = value != 0; return P2V_OK; }
   if (!strcmp(name, "gemm_tile") && (value == 0 || value == 128 || value == 256)) { g_gemm_tile = value; return P2V_OK; }
+  if (!strcmp(name, "gemm_rows") && value >= 0 && value <= 2) { g_gemm_rows = value; return P2V_OK; }
+  if (!strcmp(name, "cls_rows") && (value == 0 || value == 1)) { g_cls_rows = value; return P2V_OK; }
   return fail(P2V_E_ARG, "p2v_set_tuning: unknown switch or value out of range: %s = %d", name, value);
 }
 const char* p2v_last_error(void) { return g_err; }
@@ -500,6 +508,19 @@ static int run_gemm(int epi, const int8_t* A, int lda, int M, int K, int N, cons
   return launch_rc(p2v_launch_gemm(epi, g, st), "gemm_i8");
 }
 
+// a layer GEMM over the few class-token rows: the row kernel unless the switches name the tiled one (gemm_rows = 2, or an explicit gemm_tile)
+static int run_gemm_few_rows(int epi, const int8_t* A, int lda, int M, int K, int N, const p2v_linear& lin, const p2v_epilogue& ep, void* out,
+                             int ldo, hipStream_t st) {
+  if (g_gemm_rows == 2 || g_gemm_tile != 0) return run_gemm(epi, A, lda, M, K, N, lin, ep, out, ldo, nullptr, st);
+  GemmArgs g;
+  g.A = A; g.lda = lda; g.M = M; g.W = lin.w_codes; g.K = K; g.N = N; g.w4 = lin.packed4 ? 1 : 0;
+  g.colscale = lin.colscale; g.bias = lin.bias; g.ep = ep; g.out = out; g.ldo = ldo; g.out_codes = nullptr; g.tiles_n = 0;
+#ifdef P2V_DIAG
+  g.stamps = nullptr;
+#endif
+  return launch_rc(p2v_launch_gemm_rows(epi, g, st), "gemm_rows");
+}
+
 // QIntLayerNorm -> /cs -> qact0 -> QLinear -> (GELU) -> QAct in one launch (k_ln_gemm); a.out may be null
 static int run_ln_gemm(int epi, const LnArgs& a, const p2v_linear& lin, const p2v_epilogue& ep, int N, int8_t* out, hipStream_t st) {
   GemmArgs g;
@@ -558,6 +579,8 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
   const int Dk = round_up(D, GBK_PAD), Hk = round_up(Hd, GBK_PAD);     // contraction depths in whole k-tiles (weights are zero-padded to them)
   int launched = 0, rc;
   const bool taps = stop_after >= 0;      // parity runs read the workspace buffers: the fused kernels then also write the LayerNorm codes
+  // the last block on the class-token rows only: when nothing but the logits is asked for, and T * D fits the int strides of a GEMM
+  const bool cls_only = g_cls_rows && stop_after < 0 && !qkv_tap && !fc1_tap && !lin_tap && (long long)T * D <= 0x7fffffffLL;
 #define STEP(kind_, call)                             \
   do {                                                \
     if (stop_after >= 0 && launched >= stop_after) return P2V_OK; \
@@ -629,11 +652,33 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
     }
     // scores -> qact_attn1 -> log-int-softmax -> @v -> qact2                vit_fquant.py:309-326
     AttnArgs at{bufQKV, batch, T, d.num_heads, b.attn, bufATT, nullptr};
-    STEP(P2V_K_ATTENTION, launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"));
     // proj -> qact3 -> + x -> Block.qact2                                   vit_fquant.py:334-338,431
     p2v_epilogue ep = b.proj_epi;
     ep.residual = bufX;
     ep.resid_tab = p->resid_tab[(size_t)i * 4 + bp];
+    if (i == d.depth - 1 && cls_only) {
+      // The logits read the last block's output through its class-token rows only (the final norm below takes [:, 0]) and everything
+      // behind the qkv GEMM is row-local but for the attention's keys and values: query row 0 of every (image, head), then proj, norm2,
+      // fc1 and fc2 on `batch` rows - proj and fc2 in place on the class rows of bufX (stride T * D), the rows between them compact at the
+      // start of bufLN / bufHID.  The patch rows of bufX / bufATT / bufHID keep what the launches before left there.
+      const long long TD = (long long)T * D;
+      at.nq = 1;
+      STEP(P2V_K_ATTENTION, launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"));
+      STEP(P2V_K_GEMM_PROJ, run_gemm_few_rows(P2V_EPI_RESID, bufATT, (int)TD, batch, Dk, D, p->lin[bp][2 + 4 * i], ep, bufX, (int)TD, st));
+      LnArgs lc{bufX, TD, batch, D, b.ln2[bq][b1], bufLN, D};
+      lc.pre = b.ln2[bq][b1].pre;
+      STEP(P2V_K_LAYERNORM, launch_rc(p2v_launch_layernorm(lc, st), "int_layernorm"));
+      p2v_epilogue e1{};
+      e1.inv_s_out = b.inv_s_fc1;
+      e1.gelu = b.gelu_fc1;
+      STEP(P2V_K_GEMM_FC1, run_gemm_few_rows(P2V_EPI_GELU, bufLN, D, batch, Dk, Hd, p->lin[b1][3 + 4 * i], e1, bufHID, Hd, st));
+      p2v_epilogue e2 = b.fc2_epi;
+      e2.residual = bufX;
+      e2.resid_tab = p->resid_tab[(size_t)i * 4 + 2 + b2];
+      STEP(P2V_K_GEMM_FC2, run_gemm_few_rows(P2V_EPI_RESID, bufHID, Hd, batch, Hk, D, p->lin[b2][4 + 4 * i], e2, bufX, (int)TD, st));
+      continue;
+    }
+    STEP(P2V_K_ATTENTION, launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"));
     STEP(P2V_K_GEMM_PROJ, run_gemm(P2V_EPI_RESID, bufATT, D, M, Dk, D, p->lin[bp][2 + 4 * i], ep, bufX, D, nullptr, st));
     LIN_TAP(2 + 4 * i, bufATT, D, M, Dk, D, p->lin[bp][2 + 4 * i]);
     // norm2 (attention's channel scale!) -> /mlp.channel_scale -> mlp.qact0 vit_fquant.py:464, layers_quant.py:305-311
@@ -871,6 +916,20 @@ int p2v_lis_attention(const int8_t* qkv, int batch, int tokens, int heads, int h
     if (rc != P2V_OK) return rc;
   }
   AttnArgs a{qkv, batch, tokens, heads, *at, out, probs_k};
+  return launch_rc(p2v_launch_attention(a, head_dim, (hipStream_t)stream), "lis_attention");
+}
+
+int p2v_lis_attention_rows(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int query_rows,
+                           int8_t* out, void* stream) {
+  if (!qkv || !at || !out) return fail(P2V_E_ARG, "p2v_lis_attention_rows: null argument");
+  if (batch <= 0 || tokens <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad attention shape");
+  if (query_rows < 1 || query_rows > tokens) return fail(P2V_E_SHAPE, "p2v_lis_attention_rows: query_rows %d outside 1 .. %d", query_rows, tokens);
+  {
+    const int rc = check_attn("p2v_lis_attention_rows", *at);
+    if (rc != P2V_OK) return rc;
+  }
+  AttnArgs a{qkv, batch, tokens, heads, *at, out, nullptr};
+  a.nq = query_rows;
   return launch_rc(p2v_launch_attention(a, head_dim, (hipStream_t)stream), "lis_attention");
 }
 

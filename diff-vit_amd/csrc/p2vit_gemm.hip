@@ -518,6 +518,7 @@ int p2v_launch_embed_u8(const uint8_t* img, int nhwc, const float* lut, int B, i
 
 int g_resid_pre = 1;      // P2V_RESID_PRE=0: ignore p2v_epilogue.resid_tab (A/B and parity runs of the generic RESID epilogue)
 int g_gemm_tile = 0;      // P2V_GEMM_TILE: 0 = by grid size, 128 / 256 = force the tile height of the layer GEMMs
+extern int g_gemm_rows;   // P2V_GEMM_ROWS (p2vit_gemm_rows.hip)
 static int device_cus() {
   static int cus[16] = {0};
   int dev = 0;
@@ -550,6 +551,8 @@ int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
 #endif
   g.tiles_n = (g.N + GBN - 1) / GBN;
   if (epi != P2V_EPI_HEAD && epi != P2V_EPI_EMBED && epi != P2V_EPI_F32) {
+    // "gemm_rows" = 1: the few-rows kernel wherever it applies (parity runs against this kernel); an explicit tile height means this kernel
+    if (g_gemm_rows == 1 && g_gemm_tile == 0) return p2v_launch_gemm_rows(epi, g0, st);
     // the tiled kernel addresses both matrices with 32-bit lane offsets
     if ((long long)g.M * g.lda + g.K >= (1LL << 32) || (long long)g.tiles_n * GBN * g.K >= (1LL << 32)) return -1;
     // 256-row tiles (8 waves, two workgroups per CU) when the grid still gives every CU its two workgroups; else 128-row tiles

@@ -50,6 +50,7 @@ struct AttnArgs {
   int8_t* out;
   int8_t* probs_k;
   int pshift;           // filled by the launcher: score multiplier = 2^-pshift (>= 1) -> integer requant path; 0 = fp32 path
+  int nq;               // query rows to compute, in whole 16-row blocks (0 = all): the resident kernel; the streaming kernel computes all rows
 #ifdef P2V_DIAG
   unsigned long long* stamps;   // diagnostic build only: 16 cycle stamps per workgroup (wave 0) or null
 #endif
@@ -76,6 +77,8 @@ int p2v_launch_u8_patchify(const uint8_t* img, int B, int C, int H, int W, int P
                            hipStream_t st);
 int p2v_launch_embed_u8(const uint8_t* img, int nhwc, const float* lut, int B, int C, int H, int W, int P, const GemmArgs& g, hipStream_t st);
 int p2v_launch_gemm(int epi, const GemmArgs& g, hipStream_t st);
+// the few-rows kernel (p2vit_gemm_rows.hip): REQUANT / GELU / RESID at any M, parallel over N and K; -3: not one of its epilogues
+int p2v_launch_gemm_rows(int epi, const GemmArgs& g, hipStream_t st);
 // table of the pre-folded RESID epilogue (p2v_epilogue.resid_tab): [ceil(N/128)][6][128] floats; flags: dev [2] preset to {1, 0}
 int p2v_launch_resid_prefold(const p2v_linear& lin, const p2v_epilogue& ep, int N, float* tab, unsigned* flags, hipStream_t st);
 int p2v_launch_layernorm(const LnArgs& a, hipStream_t st);

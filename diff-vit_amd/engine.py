@@ -141,6 +141,8 @@ def lib():
     L.p2v_gemm_i8.argtypes = [_i, _p, _i, _i, _i, _i, C.POINTER(Linear), C.POINTER(Epilogue), _p, _i, _p, _p]
     L.p2v_int_layernorm.argtypes = [_p, _ll, _i, _i, C.POINTER(Ln), _p, _ll, _p]
     L.p2v_lis_attention.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Attn), _p, _p, _p]
+    if hasattr(L, 'p2v_lis_attention_rows'):      # additive entry point, found by its symbol: side builds of older revisions (tools/abx.sh) lack it
+        L.p2v_lis_attention_rows.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Attn), _i, _p, _p]
     L.p2v_ln_gemm_i8.argtypes = [_i, _p, _ll, _i, _i, C.POINTER(Ln), _i, C.POINTER(Linear), C.POINTER(Epilogue), _p, _i, _p, _p]
     L.p2v_ln_gemm_fusable.argtypes = [_i, _i, _i, _i]
     L.p2v_set_tuning.argtypes = [C.c_char_p, _i]

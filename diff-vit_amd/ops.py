@@ -27,6 +27,8 @@ _LIB.define('linear_requant(Tensor x, Tensor w, Tensor colscale, Tensor bias, fl
 _LIB.define('linear_gelu_requant(Tensor x, Tensor w, Tensor colscale, Tensor bias, float inv_s_out) -> Tensor')
 _LIB.define('int_layernorm(Tensor x, float s1, Tensor mask, Tensor gamma, Tensor beta, Tensor inv_out, Tensor post_mul) -> Tensor')
 _LIB.define('lis_attention(Tensor qkv, int heads, float s_qkv_sq, float qk_scale, float inv_s_attn, float av_mul, int x0, int b, int c) -> Tensor')
+_LIB.define('lis_attention_rows(Tensor qkv, int heads, float s_qkv_sq, float qk_scale, float inv_s_attn, float av_mul, int x0, int b, int c, '
+            'int query_rows) -> Tensor')
 _LIB.define('forward(int plan, Tensor images, int[] bit_config) -> Tensor')
 _LIB.define('cka_grams(Tensor[] xs, Tensor[] ys) -> Tensor')
 _LIB.define('hsic_accumulate(Tensor g1, Tensor g2, Tensor(a!) acc, Tensor(b!)? self1, Tensor(c!)? self2) -> ()')
@@ -93,6 +95,17 @@ def _lis_attention(qkv, heads, s_qkv_sq, qk_scale, inv_s_attn, av_mul, x0, b, c)
     out = torch.empty(B, N, D, dtype=torch.int8, device=qkv.device)
     E.check(E.lib().p2v_lis_attention(E.ptr(qkv), B, N, heads, D // heads, C.byref(at), E.ptr(out), None, E.stream_ptr()))
     return out
+
+
+def _lis_attention_rows(qkv, heads, s_qkv_sq, qk_scale, inv_s_attn, av_mul, x0, b, c, query_rows):
+    """``lis_attention`` for the first ``query_rows`` query tokens of every image (all keys): [B, query_rows, D]."""
+    qkv = qkv.contiguous()
+    B, N, D3 = qkv.shape
+    D = D3 // 3
+    at = E.Attn(s_qkv_sq, qk_scale, inv_s_attn, av_mul, x0, b, c)
+    out = torch.zeros(B, N, D, dtype=torch.int8, device=qkv.device)     # the kernel works in 16-row blocks: rows past them stay untouched
+    E.check(E.lib().p2v_lis_attention_rows(E.ptr(qkv), B, N, heads, D // heads, C.byref(at), query_rows, E.ptr(out), E.stream_ptr()))
+    return out[:, :query_rows].contiguous()
 
 
 _PLANS = {}          # handle -> FrozenPlan, filled by plan.FrozenPlan (weak registry of live plans)
@@ -176,9 +189,10 @@ _LIB.impl('linear_requant', lambda x, w, cs, b, inv: _linear(E.EPI_REQUANT, x, w
 _LIB.impl('linear_gelu_requant', lambda x, w, cs, b, inv: _linear(E.EPI_GELU, x, w, cs, b, inv), 'CUDA')
 _LIB.impl('int_layernorm', _int_layernorm, 'CUDA')
 _LIB.impl('lis_attention', _lis_attention, 'CUDA')
+_LIB.impl('lis_attention_rows', _lis_attention_rows, 'CUDA')
 _LIB.impl('forward', _forward, 'CUDA')
 _LIB.impl('cka_grams', _cka_grams, 'CUDA')
 _LIB.impl('hsic_accumulate', _hsic_accumulate, 'CUDA')
 
-OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'forward', 'cka_grams',
+OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'lis_attention_rows', 'forward', 'cka_grams',
        'hsic_accumulate')

@@ -254,7 +254,10 @@ size_t p2v_workspace_bytes(const p2v_plan* plan, int batch);
 
 /* images: dev fp32 [batch][in_chans][img][img];  bit_config: HOST int8 [n_cfg], n_cfg = 4*depth+2;
  * logits: dev fp32 [batch][num_classes].  stop_after < 0 runs everything; otherwise execution stops after
- * that many kernel launches (parity tests read the workspace buffers, see p2v_workspace_view). */
+ * that many kernel launches (parity tests read the workspace buffers, see p2v_workspace_view).
+ * With stop_after < 0 the last block runs behind its qkv GEMM on the class-token rows only (the logits read nothing else): the views
+ * "x", "att", "hid" and "ln" then hold that block's values only where the logits need them; stop_after >= 0 is the way to read full
+ * buffers (switch "cls_rows" of p2v_set_tuning). */
 int p2v_forward(p2v_plan* plan, const float* images, int batch, const int8_t* bit_config, int n_cfg,
                 float* logits, void* workspace, size_t workspace_bytes, int stop_after, void* stream);
 
@@ -371,6 +374,14 @@ int p2v_ln_gemm_fusable(int epilogue_kind, int C, int N, int gelu_table_cells);
  * (16 = zero) for parity tests. */
 int p2v_lis_attention(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at,
                       int8_t* out, int8_t* probs_k, void* stream);
+/* (additive: no structure, existing entry point or P2V_ABI_VERSION changes; a binding finds it by its symbol)
+ * The same core for the first `query_rows` query tokens of every image only (1 <= query_rows <= tokens; all keys and values take
+ * part): what the last block of a ViT needs, whose output is read through the class token alone.  Same layouts and checks as
+ * p2v_lis_attention, no probs_k tap.  The kernel works in blocks of 16 query rows: rows 0 .. min(tokens, 16 * ceil(query_rows / 16)) - 1
+ * of every image in `out` are written (each with its own, correct values), the rows behind them are not touched.  Beyond the
+ * resident kernel's token count (p2v_resident_tokens) the streaming kernel computes and writes every row. */
+int p2v_lis_attention_rows(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int query_rows,
+                           int8_t* out, void* stream);
 
 /* Swin window attention core (WindowAttention.forward between qact1 and qact3, swin_quant.py:186-217; window partition /
  * cyclic shift / reverse of SwinTransformerBlock.forward, swin_quant.py:366-391, folded into the addressing):
@@ -502,12 +513,20 @@ const char* p2v_last_error(void);
 int p2v_abi_version(void);
 
 /* Scheduling / A-B switches of the process (also read once from the environment: P2V_LN_GEMM, P2V_LN_GEMM_V, P2V_LN_GENERIC,
- * P2V_LN_ROWS, P2V_ATTN_WAVES, P2V_GEMM_TILE, P2V_RESID_PRE, P2V_LN_PRE, P2V_ATTN_STREAM).  None of them changes a result - every variant is
+ * P2V_LN_ROWS, P2V_ATTN_WAVES, P2V_GEMM_TILE, P2V_RESID_PRE, P2V_LN_PRE, P2V_ATTN_STREAM, P2V_GEMM_ROWS, P2V_CLS_ROWS).  None of them changes a result - every variant is
  * bit-identical and is driven through this call by the parity tests (profiles/r04_alt_paths.txt: the whole GPU suite on the alternatives):
  *   "ln_gemm" 0/1 (fuse LayerNorm into qkv / fc1), "ln_gemm_version" 1/2/3 (round-2 4-wave / pipelined 4-wave (default) / 8-wave fused kernel),
  *   "ln_generic" 0/1 (generic LayerNorm chain), "ln_rows" 1..64, "attn_waves" 4..8,
  *   "gemm_tile" 0/128/256 (tile height of the layer GEMMs; 0 = 256 rows when the grid still fills the chip),
- *   "resid_pre" 0/1 (use p2v_epilogue.resid_tab), "ln_pre" 0/1 (use p2v_ln.pre), "attn_stream" 0/1 (streaming attention kernel everywhere). */
+ *   "resid_pre" 0/1 (use p2v_epilogue.resid_tab), "ln_pre" 0/1 (use p2v_ln.pre), "attn_stream" 0/1 (streaming attention kernel everywhere),
+ *   "cls_rows" 0/1 (default 1: p2v_forward / p2v_forward_u8 / p2v_forward_profile* with stop_after = -1 run the last block behind its qkv
+ *   GEMM on the class-token rows only - one query row per (image, head), then proj, norm2, fc1, fc2 on `batch` rows; the logits do not
+ *   depend on the other rows.  Consequence: after such a call the workspace views "x", "att", "hid" and "ln" hold the LAST block's values
+ *   only where the logits need them (class rows of "x" / "att", the first `batch` rows of "hid" / "ln"); stop_after >= 0, p2v_forward_taps
+ *   and p2v_forward_linear_taps compute every row as before and are the way to read full buffers),
+ *   "gemm_rows" 0/1/2 (the few-rows GEMM kernel, parallel over N and K instead of M: 0 = where the forward asks for it, i.e. the class rows
+ *   above; 1 = every REQUANT / GELU / RESID GEMM, also through p2v_gemm_i8 and p2v_run_ops; 2 = never.  An explicit "gemm_tile" of 128 or 256
+ *   always means the tiled kernel). */
 int p2v_set_tuning(const char* name, int value);
 
 #ifdef __cplusplus
