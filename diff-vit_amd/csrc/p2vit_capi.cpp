@@ -550,10 +550,38 @@ struct Prof {
 };
 static int prof_pool_size(const p2v_plan* p) { return p ? 7 * p->d.depth + 10 : 0; }
 
+// p2v_forward_ddv: the batch is n clean images followed by their n perturbed twins; after the launch that completes a stage its rows
+// [0, n * T) are reduced against rows [n * T, 2n * T) (p2vit_ddv.hip), stage k into sums[k][n][3]
+struct DdvCtx {
+  int n;
+  unsigned long long* partials;   // `slots` workgroup partials of 3 values, reused by every stage (one stream)
+  long long slots;
+  double* sums;
+  float* tap;                     // the one fp32 tap buffer of with_linear, or null
+  int stage;
+};
+static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st) {
+  const size_t esz = dtype == P2V_COS_I8 ? 1 : 4;
+  p2v_cos_layer l;
+  l.a = base;
+  l.b = reinterpret_cast<const char*>(base) + (size_t)c->n * rows * cols * esz;
+  l.scale = scale;
+  l.sample_stride = (long long)rows * cols;
+  l.row_stride = cols;
+  l.rows = rows; l.cols = cols; l.dtype = dtype;
+  const CosDesc d = p2v_cos_desc(l, c->n, 0);        // (logits / head rows of a class count that is no multiple of 4: d.vec = 0, scalar loads)
+  if ((long long)c->n * d.nsplit > c->slots)
+    return fail(P2V_E_WORKSPACE, "p2v_forward_ddv: a stage of %d x %d needs %lld partials, the workspace holds %lld", rows, cols,
+                (long long)c->n * d.nsplit, c->slots);
+  const int rc = launch_rc(p2v_launch_pair_cosine_one(d, c->n, c->partials, c->sums + (size_t)c->stage * c->n * 3, st), "pair_cosine");
+  ++c->stage;
+  return rc;
+}
+
 static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
                         size_t workspace_bytes, int stop_after, void* stream, Prof* prof, float* const* qkv_tap = nullptr,
                         float* const* fc1_tap = nullptr, float* const* lin_tap = nullptr, const uint8_t* u8 = nullptr, int layout = 0,
-                        const void* lut = nullptr) {
+                        const void* lut = nullptr, DdvCtx* ddv = nullptr) {
   // u8 != nullptr: p2v_forward_u8 (images == nullptr; the input stage reads the uint8 images through `lut`, the rest is shared)
   if (!p || !(images || u8) || !bit_config || !logits || !workspace) return fail(P2V_E_ARG, "p2v_forward: null argument");
   if (batch <= 0) return fail(P2V_E_SHAPE, "batch must be positive");
@@ -580,7 +608,7 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
   int launched = 0, rc;
   const bool taps = stop_after >= 0;      // parity runs read the workspace buffers: the fused kernels then also write the LayerNorm codes
   // the last block on the class-token rows only: when nothing but the logits is asked for, and T * D fits the int strides of a GEMM
-  const bool cls_only = g_cls_rows && stop_after < 0 && !qkv_tap && !fc1_tap && !lin_tap && (long long)T * D <= 0x7fffffffLL;
+  const bool cls_only = g_cls_rows && stop_after < 0 && !qkv_tap && !fc1_tap && !lin_tap && !ddv && (long long)T * D <= 0x7fffffffLL;
 #define STEP(kind_, call)                             \
   do {                                                \
     if (stop_after >= 0 && launched >= stop_after) return P2V_OK; \
@@ -601,6 +629,16 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
       rc = run_gemm(P2V_EPI_F32, A, lda, M_, K_, N_, lin, p2v_epilogue{}, lin_tap[idx], N_, nullptr, st);                 \
       if (rc) return rc;                                                                                                  \
     }                                                                                                                     \
+  } while (0)
+
+  // DDV stages (p2v_forward_ddv): the int8 codes a launch has just completed, and the fp32 tap that sits in the one tap buffer
+#define DDV_I8(buf, rows_, cols_, scale_)                                                \
+  do {                                                                                   \
+    if (ddv && (rc = ddv_reduce(ddv, buf, rows_, cols_, P2V_COS_I8, scale_, st))) return rc; \
+  } while (0)
+#define DDV_TAP(rows_, cols_)                                                            \
+  do {                                                                                   \
+    if (ddv && ddv->tap && (rc = ddv_reduce(ddv, ddv->tap, rows_, cols_, P2V_COS_F32, nullptr, st))) return rc; \
   } while (0)
 
   // qact_input + PatchEmbed + cls/pos/qact1                                 vit_fquant.py:705-733
@@ -631,6 +669,7 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
       STEP(P2V_K_GEMM_EMBED, launch_rc(p2v_launch_embed_fp32(images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, g, st), "embed_fp32"));
   }
   STEP(P2V_K_FILL_CLS, launch_rc(p2v_launch_fill_cls(bufX, batch, T, D, p->cls_codes, st), "fill_cls"));
+  DDV_I8(bufX, T, D, p->embed_epi.s_next);                                   // qact1
 
   for (int i = 0; i < d.depth; ++i) {
     const p2v_block& b = p->blocks[i];
@@ -650,6 +689,8 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
       STEP(P2V_K_LAYERNORM, launch_rc(p2v_launch_layernorm(ln, st), "int_layernorm"));
       STEP(P2V_K_GEMM_QKV, run_gemm(P2V_EPI_REQUANT, bufLN, D, M, Dk, 3 * D, p->lin[bq][1 + 4 * i], e, bufQKV, 3 * D, nullptr, st));
     }
+    DDV_TAP(T, 3 * D);                                                       // attn.qkv
+    DDV_I8(bufQKV, T, 3 * D, nullptr);                                       // attn.qact1
     // scores -> qact_attn1 -> log-int-softmax -> @v -> qact2                vit_fquant.py:309-326
     AttnArgs at{bufQKV, batch, T, d.num_heads, b.attn, bufATT, nullptr};
     // proj -> qact3 -> + x -> Block.qact2                                   vit_fquant.py:334-338,431
@@ -679,8 +720,11 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
       continue;
     }
     STEP(P2V_K_ATTENTION, launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"));
+    DDV_I8(bufATT, T, D, nullptr);                                           // attn.qact2
     STEP(P2V_K_GEMM_PROJ, run_gemm(P2V_EPI_RESID, bufATT, D, M, Dk, D, p->lin[bp][2 + 4 * i], ep, bufX, D, nullptr, st));
     LIN_TAP(2 + 4 * i, bufATT, D, M, Dk, D, p->lin[bp][2 + 4 * i]);
+    DDV_TAP(T, D);                                                           // attn.proj
+    DDV_I8(bufX, T, D, b.proj_epi.s_next);                                   // Block.qact2
     // norm2 (attention's channel scale!) -> /mlp.channel_scale -> mlp.qact0 vit_fquant.py:464, layers_quant.py:305-311
     LnArgs ln2{bufX, D, M, D, b.ln2[bq][b1], bufLN, D};
     ln2.pre = b.ln2[bq][b1].pre;
@@ -696,23 +740,32 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
       STEP(P2V_K_LAYERNORM, launch_rc(p2v_launch_layernorm(ln2, st), "int_layernorm"));
       STEP(P2V_K_GEMM_FC1, run_gemm(P2V_EPI_GELU, bufLN, D, M, Dk, Hd, p->lin[b1][3 + 4 * i], e1, bufHID, Hd, nullptr, st));
     }
+    DDV_TAP(T, Hd);                                                          // mlp.fc1
+    DDV_I8(bufHID, T, Hd, nullptr);                                          // mlp.qact1
     // fc2 -> qact2 -> + x -> Block.qact4                                    layers_quant.py:342-346, vit_fquant.py:468
     p2v_epilogue e2 = b.fc2_epi;
     e2.residual = bufX;
     e2.resid_tab = p->resid_tab[(size_t)i * 4 + 2 + b2];
     STEP(P2V_K_GEMM_FC2, run_gemm(P2V_EPI_RESID, bufHID, Hd, M, Hk, D, p->lin[b2][4 + 4 * i], e2, bufX, D, nullptr, st));
     LIN_TAP(4 + 4 * i, bufHID, Hd, M, Hk, D, p->lin[b2][4 + 4 * i]);
+    DDV_TAP(T, D);                                                           // mlp.fc2
+    DDV_I8(bufX, T, D, b.fc2_epi.s_next);                                    // Block.qact4
   }
   // norm over the cls rows only ([:,0]) -> qact2 -> head -> act_out         vit_fquant.py:766-796
   LnArgs lf{bufX, (long long)T * D, batch, D, p->final_ln, bufCLS, D};
   lf.pre = p->final_ln.pre;
   STEP(P2V_K_LAYERNORM, launch_rc(p2v_launch_layernorm(lf, st), "int_layernorm"));
+  DDV_I8(bufCLS, 1, D, nullptr);                                             // qact2
   p2v_epilogue eh{};
   eh.inv_s_out = p->head_inv_s;
   eh.s_out = p->head_s;
   STEP(P2V_K_GEMM_HEAD, run_gemm(P2V_EPI_HEAD, bufCLS, D, batch, Dk, d.num_classes, p->lin[bit_index(bit_config[n_cfg - 1])][n_cfg - 1], eh, logits,
                 d.num_classes, nullptr, st));
   LIN_TAP(n_cfg - 1, bufCLS, D, batch, Dk, d.num_classes, p->lin[bit_index(bit_config[n_cfg - 1])][n_cfg - 1]);
+  DDV_TAP(1, d.num_classes);                                                 // head
+  if (ddv && (rc = ddv_reduce(ddv, logits, 1, d.num_classes, P2V_COS_F32, nullptr, st))) return rc;   // act_out
+#undef DDV_TAP
+#undef DDV_I8
 #undef LIN_TAP
 #undef STEP
   if (prof) {
@@ -1137,4 +1190,88 @@ int p2v_hsic_accumulate(const float* g1, int l1, const float* g2, int l2, int n,
   if (n < P2V_CKA_MIN_N || n > P2V_CKA_MAX_N) return fail(P2V_E_SHAPE, "p2v_hsic_accumulate: n = %d images, the kernels take %d ... %d", n, P2V_CKA_MIN_N, P2V_CKA_MAX_N);
   if (dtype != 0 && dtype != 1) return fail(P2V_E_ARG, "p2v_hsic_accumulate: dtype %d (0 = fp32, 1 = fp64)", dtype);
   return launch_rc(p2v_launch_hsic(g1, l1, g2, l2, n, acc, self1, self2, dtype, (hipStream_t)stream), "hsic_accumulate");
+}
+
+// ---- DDV model diff (p2vit_ddv.hip) ------------------------------------------------------------------------------------------------
+static int cos_check(const p2v_cos_layer* layers, int n_layers, int n, const char* what) {
+  if (!layers || n_layers <= 0) return fail(P2V_E_ARG, "%s: no layers", what);
+  if (n < 1) return fail(P2V_E_SHAPE, "%s: n = %d samples", what, n);
+  for (int l = 0; l < n_layers; ++l) {
+    const p2v_cos_layer& a = layers[l];
+    if (!a.a || !a.b) return fail(P2V_E_ARG, "%s: layer %d has a null operand", what, l);
+    if (a.dtype != P2V_COS_I8 && a.dtype != P2V_COS_F32) return fail(P2V_E_ARG, "%s: layer %d: dtype %d (0 = int8, 1 = fp32)", what, l, a.dtype);
+    if (a.rows < 1 || a.cols < 1) return fail(P2V_E_SHAPE, "%s: layer %d: %d rows x %d cols", what, l, a.rows, a.cols);
+    if (a.row_stride < a.cols) return fail(P2V_E_ARG, "%s: layer %d: row_stride %lld < cols %d", what, l, a.row_stride, a.cols);
+    if (a.sample_stride < 0) return fail(P2V_E_ARG, "%s: layer %d: negative sample_stride %lld", what, l, a.sample_stride);
+    if (a.scale && a.dtype != P2V_COS_I8) return fail(P2V_E_UNSUPPORTED, "%s: layer %d: per-channel scales go with int8 codes", what, l);
+    const long long esz = a.dtype == P2V_COS_I8 ? 1 : 4;
+    if ((uintptr_t)a.a % 16 || (uintptr_t)a.b % 16 || a.sample_stride * esz % 16 || a.row_stride * esz % 16)
+      return fail(P2V_E_ARG, "%s: layer %d: pointers and strides must be multiples of 16 bytes", what, l);
+    if (a.dtype == P2V_COS_I8 && (long long)a.rows * a.cols >= (1LL << 39))
+      return fail(P2V_E_UNSUPPORTED, "%s: layer %d: %d x %d codes per sample leave the exact fp64 range", what, l, a.rows, a.cols);
+  }
+  return P2V_OK;
+}
+
+size_t p2v_pair_cosine_workspace_bytes(const p2v_cos_layer* layers, int n_layers, int n) {
+  if (cos_check(layers, n_layers, n, "p2v_pair_cosine_workspace_bytes") != P2V_OK) return 0;
+  return p2v_cos_layout(layers, n_layers, n, nullptr).total;
+}
+
+int p2v_pair_cosine(const p2v_cos_layer* layers, int n_layers, int n, double* sums, void* ws, size_t ws_bytes, void* stream) {
+  int rc = cos_check(layers, n_layers, n, "p2v_pair_cosine");
+  if (rc != P2V_OK) return rc;
+  if (!sums || !ws) return fail(P2V_E_ARG, "p2v_pair_cosine: null sums / workspace");
+  std::vector<CosDesc> descs;
+  descs.reserve(n_layers);
+  const CosLayout w = p2v_cos_layout(layers, n_layers, n, &descs);
+  if (ws_bytes < w.total) return fail(P2V_E_WORKSPACE, "p2v_pair_cosine: workspace %zu < %zu bytes", ws_bytes, w.total);
+  if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_pair_cosine: the workspace must be 256-byte aligned");
+  return launch_rc(p2v_launch_pair_cosine(descs, w, n, sums, ws, (hipStream_t)stream), "pair_cosine");
+}
+
+int p2v_ddv_stage_count(const p2v_plan* plan, int with_linear) {
+  if (!plan) return fail(P2V_E_ARG, "p2v_ddv_stage_count: null plan");
+  return 5 * plan->d.depth + 3 + (with_linear ? 4 * plan->d.depth + 1 : 0);
+}
+
+// workgroups of the largest stage: p2v_cos_desc gives a sample at most 2048 / n (>= 1) splits while its rows stay below 2^16 per split -
+// true of every stage here (at most 4096 tokens); ddv_reduce checks each stage against this count before it launches
+static long long ddv_partial_slots(int n) { return n > 2048 ? n : 2048; }
+static size_t ddv_partial_bytes(int n) { return (size_t)ddv_partial_slots(n) * 3 * sizeof(unsigned long long); }
+
+size_t p2v_ddv_workspace_bytes(const p2v_plan* plan, int n) {
+  if (!plan || n <= 0 || n > (1 << 29)) return 0;
+  return ws_layout(plan, 2 * n).total + ddv_partial_bytes(n);        // (the forward's part is a multiple of 256 bytes)
+}
+
+size_t p2v_ddv_tap_scratch_bytes(const p2v_plan* plan, int n) {
+  if (!plan || n <= 0 || n > (1 << 29)) return 0;
+  const size_t wide = (size_t)(3 * plan->d.embed_dim > plan->d.mlp_hidden ? 3 * plan->d.embed_dim : plan->d.mlp_hidden);
+  const size_t tok = (size_t)2 * n * plan->tokens * wide, head = (size_t)2 * n * plan->d.num_classes;
+  return (tok > head ? tok : head) * sizeof(float);
+}
+
+int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                    size_t ws_bytes, int with_linear, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream) {
+  if (!plan || !sums || !ws) return fail(P2V_E_ARG, "p2v_forward_ddv: null argument");
+  if (n <= 0 || n > (1 << 29)) return fail(P2V_E_SHAPE, "p2v_forward_ddv: n = %d pairs", n);
+  if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_forward_ddv: the workspace must be 256-byte aligned");
+  const size_t fwd = ws_layout(plan, 2 * n).total;
+  if (ws_bytes < fwd + ddv_partial_bytes(n)) return fail(P2V_E_WORKSPACE, "p2v_forward_ddv: workspace %zu < %zu bytes", ws_bytes, fwd + ddv_partial_bytes(n));
+  if (with_linear) {
+    if (!tap_scratch) return fail(P2V_E_ARG, "p2v_forward_ddv: with_linear needs tap_scratch");
+    if ((uintptr_t)tap_scratch % 16) return fail(P2V_E_ARG, "p2v_forward_ddv: tap_scratch must be 16-byte aligned");
+    if (tap_scratch_bytes < p2v_ddv_tap_scratch_bytes(plan, n))
+      return fail(P2V_E_WORKSPACE, "p2v_forward_ddv: tap_scratch %zu < %zu bytes", tap_scratch_bytes, p2v_ddv_tap_scratch_bytes(plan, n));
+  }
+  DdvCtx ctx{n, reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + fwd), ddv_partial_slots(n), sums,
+             with_linear ? tap_scratch : nullptr, 0};
+  std::vector<float*> taps;
+  if (with_linear) {
+    taps.assign(plan->n_layers, tap_scratch);      // every linear output goes through the one buffer; the patch embedding is no DDV stage
+    taps[0] = nullptr;
+  }
+  return forward_impl(plan, images, 2 * n, bit_config, n_cfg, logits, ws, fwd, -1, stream, nullptr, nullptr, nullptr,
+                      with_linear ? taps.data() : nullptr, nullptr, 0, nullptr, &ctx);
 }

@@ -118,3 +118,25 @@ struct CkaLayout {
 CkaLayout p2v_cka_layout(const p2v_cka_layer* layers, int L, int n, std::vector<CkaDesc>* descs);
 int p2v_launch_cka_grams(const std::vector<CkaDesc>& descs, const CkaLayout& w, int n, float* grams, void* ws, hipStream_t st);
 int p2v_launch_hsic(const float* g1, int l1, const float* g2, int l2, int n, void* acc, void* self1, void* self2, int dtype, hipStream_t st);
+
+// pair-cosine sums of the DDV model diff (p2vit_ddv.hip): one record per stage
+struct CosDesc {
+  const void* a;
+  const void* b;
+  const float* scale;    // per-channel fp32 [cols] (int8 only) or null
+  long long sample_stride, row_stride;   // in elements
+  long long item0;       // first workgroup of the stage in k_cos_partial's grid (0 for a stage launched alone)
+  int rows, cols;
+  int dtype;             // P2V_COS_I8 / P2V_COS_F32
+  int vec;               // pointers and strides are 16-byte aligned: whole column groups are read with one 16-byte load
+  int nsplit;            // workgroups per sample
+  int rows_per_split;
+};
+struct CosLayout {
+  long long items;       // workgroups of k_cos_partial
+  size_t desc_off, part_off, total;
+};
+CosDesc p2v_cos_desc(const p2v_cos_layer& a, int n, long long item0);
+CosLayout p2v_cos_layout(const p2v_cos_layer* layers, int L, int n, std::vector<CosDesc>* descs);
+int p2v_launch_pair_cosine(const std::vector<CosDesc>& descs, const CosLayout& w, int n, double* sums, void* ws, hipStream_t st);
+int p2v_launch_pair_cosine_one(const CosDesc& d, int n, unsigned long long* partials, double* sums, hipStream_t st);

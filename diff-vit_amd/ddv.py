@@ -1,0 +1,279 @@
+"""DDV model diff: ModelDiff's "decision distance vector" per layer (the reference's modeldiff_p2.py), on the fused engine.
+
+    compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True)     modeldiff_p2.py:84-116
+    similarity(ddv_a, ddv_b)                 per-stage cosine of two DDVs (ModelDiff's metric)
+    reference_similarity(ddv_a, ddv_b)       what calculate_and_print_similarities prints    modeldiff_p2.py:118-131
+    AttackPGD / gen_adv_inputs(model, inputs, epsilon=0.3, step_size=0.01, num_steps=50)     modeldiff_p2.py:152-194
+
+For every stage (a hooked module) and seed sample the DDV holds the cosine between the stage's activation on the clean input and on
+its perturbed twin; the vector over the samples is divided by its L2 norm.  All of it in fp64: cos = dot / (sqrt(aa) sqrt(bb)), 0/0
+stays NaN as in numpy.
+
+On a fused model (``model_quant()`` state on a GPU) ``compute_ddv`` makes ONE ``p2v_forward_ddv`` call on the batch [clean; perturbed]:
+the int8 codes of qact1, attn.qact1, attn.qact2, Block.qact2, mlp.qact1, Block.qact4 and the final qact2 are reduced in the workspace
+between the launches of the forward (exact integer sums; per-channel PTF scales applied in fp64), the logits as fp32, and with
+``with_linear`` the outputs of attn.qkv / attn.proj / mlp.fc1 / mlp.fc2 / head through one fp32 tap buffer.  Any other state (a float
+model, ``-1`` entries, ``model_dequant()``, a CPU model) runs the module graph with forward hooks on the same-named modules and reduces
+through ``torch.ops.p2vit.pair_cosine`` (GPU tensors) or ``pair_cosine_cpu`` (CPU tensors, the plain-torch twin).
+
+Not covered: Swin models (``NotImplementedError``); the reference's norm1 / norm2 / attn.qact3 / mlp.qact2 hook points, whose codes
+never leave LDS or registers in the fused kernels; and forward hooks of your own on QAct / QIntLayerNorm modules of a fused model - they
+never fire, because the engine bypasses the module graph (hooks on QLinear / QConv2d are served, see ``cka``).
+
+``python -m diff_vit_amd.ddv --model deit_small --bits 8 --n 50`` prints the float-vs-quantized similarity per stage on the synthetic
+data of ``harness`` and writes ``ddv_result/ddv.pkl``."""
+import argparse
+import copy
+import os
+import pickle
+
+import torch
+import torch.nn as nn
+
+from . import ops  # noqa: F401  (registers torch.ops.p2vit.*)
+
+
+def stage_names(depth, with_linear=True):
+    """the DDV stages in module order, the one list ``FrozenPlan.forward_ddv`` and the module-graph path share."""
+    names = ['qact1']
+    for i in range(depth):
+        p = 'blocks.%d.' % i
+        names += ([p + 'attn.qkv'] if with_linear else []) + [p + 'attn.qact1', p + 'attn.qact2']
+        names += ([p + 'attn.proj'] if with_linear else []) + [p + 'qact2']
+        names += ([p + 'mlp.fc1'] if with_linear else []) + [p + 'mlp.qact1']
+        names += ([p + 'mlp.fc2'] if with_linear else []) + [p + 'qact4']
+    return names + ['qact2'] + (['head'] if with_linear else []) + ['act_out']
+
+
+def reference_keys(depth):
+    """hook name of modeldiff_p2.add_hooks -> stage name, for the stages both sides have (pos_drop is the identity behind qact1)."""
+    keys = {'pos_drop': 'qact1', 'final_qact2': 'qact2', 'head': 'head', 'act_out': 'act_out'}
+    for i in range(depth):
+        for ref, ours in (('attn_qkv', 'attn.qkv'), ('attn_proj', 'attn.proj'), ('qact2', 'qact2'), ('mlp_fc1', 'mlp.fc1'),
+                          ('mlp_fc2', 'mlp.fc2'), ('qact4', 'qact4')):
+            keys['block_%d_%s' % (i, ref)] = 'blocks.%d.%s' % (i, ours)
+    return keys
+
+
+REFERENCE_KEYS = reference_keys(24)         # covers every ViT / DeiT depth of the factories; deeper models: reference_keys(depth)
+
+
+def pair_cosine_cpu(a, b, scales=None):
+    """the CPU twin of ``torch.ops.p2vit.pair_cosine``: fp64 [stages, n, 3] = (sum a.b, sum a.a, sum b.b) per stage and sample; integer
+    codes are summed as int64 (exact), per-channel scales of the last dimension applied as fp64 s_c^2 on per-channel sums."""
+    out = []
+    scales = scales if scales is not None else [None] * len(a)
+    for x, y, sc in zip(a, b, scales):
+        n = x.shape[0]
+        if not x.dtype.is_floating_point and sc is None:
+            x, y = x.reshape(n, -1).to(torch.int64), y.reshape(n, -1).to(torch.int64)
+            out.append(torch.stack([(x * y).sum(1), (x * x).sum(1), (y * y).sum(1)], 1).double())
+        elif sc is not None:
+            C = x.shape[-1]
+            x, y = x.reshape(n, -1, C).to(torch.int64), y.reshape(n, -1, C).to(torch.int64)
+            s2 = sc.reshape(-1).double() ** 2
+            out.append(torch.stack([((x * y).sum(1).double() * s2).sum(1), ((x * x).sum(1).double() * s2).sum(1),
+                                    ((y * y).sum(1).double() * s2).sum(1)], 1))
+        else:
+            x, y = x.reshape(n, -1).double(), y.reshape(n, -1).double()
+            out.append(torch.stack([(x * y).sum(1), (x * x).sum(1), (y * y).sum(1)], 1))
+    return torch.stack(out)
+
+
+def cosines(sums):
+    """fp64 [..., 3] sums -> cosines dot / (sqrt(aa) sqrt(bb)); an all-zero sample gives 0/0 = NaN, as numpy does in the reference."""
+    sums = sums.double()
+    return sums[..., 0] / (torch.sqrt(sums[..., 1]) * torch.sqrt(sums[..., 2]))
+
+
+def ddv_from_sums(sums):
+    """[stages, n, 3] -> [stages, n]: the cosines of a stage divided by their L2 norm when it is not zero (modeldiff_p2.py:110-113)."""
+    cos = cosines(sums)
+    norm = torch.sqrt((cos * cos).sum(-1, keepdim=True))
+    return torch.where(norm != 0, cos / norm, cos)
+
+
+def _device_of(model):
+    p = next(model.parameters(), None)
+    return p.device if p is not None else torch.device('cpu')
+
+
+def _graph_forward(model, x, bit_config):
+    """the module graph of ``VisionTransformer.forward`` (its branch behind the fused engine), whatever the model's state."""
+    FLOPs, gd = [], []
+    h = model.forward_features(x, FLOPs, gd, bit_config, False, False)
+    return model.act_out(model.head(h, gd, bit_config[-1] if bit_config else None))
+
+
+def _hooked_outputs(model, x, bit_config, names, fused_state):
+    mods = dict(model.named_modules())
+    got, hooks = {}, []
+    for nm in names:
+        hooks.append(mods[nm].register_forward_hook(lambda m, i, o, nm=nm: got.__setitem__(nm, o.detach())))
+    try:
+        with torch.no_grad():
+            if fused_state:
+                _graph_forward(model, x, bit_config)
+            else:
+                model(x, bit_config=bit_config, plot=False)
+    finally:
+        for h in hooks:
+            h.remove()
+    for nm in names:      # a float pass calls F.linear itself for qkv / fc1 (the SmoothQuant branch): their modules' hooks did not fire
+        if nm not in got:
+            parent, leaf = nm.rsplit('.', 1)
+            got[nm] = getattr(mods[parent], leaf + '_output')
+    return [got[nm] for nm in names]
+
+
+def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True):
+    """modeldiff_p2.compute_ddv:84-116 for ``model`` under ``bit_config``: dict stage name -> fp64 tensor [n] (on the model's device)."""
+    from .swin import SwinTransformer
+    from .vit import VisionTransformer
+    if isinstance(model, SwinTransformer) or not isinstance(model, VisionTransformer):
+        raise NotImplementedError('compute_ddv covers the ViT / DeiT models (the fused Swin engine has no DDV stages)')
+    if tuple(normal_inputs.shape) != tuple(adv_inputs.shape) or normal_inputs.dim() != 4 or normal_inputs.shape[0] < 1:
+        raise AssertionError('compute_ddv: clean and perturbed inputs must be two [n, C, H, W] batches of one shape')
+    dev = _device_of(model)
+    x, xa = normal_inputs.to(dev).float(), adv_inputs.to(dev).float()
+    has_fp = bit_config is not None and any(int(b) == -1 for b in bit_config)
+    fused_state = model._fused()
+    if fused_state and not has_fp and dev.type == 'cuda':
+        if bit_config is None:
+            raise ValueError('None is not in list')              # bit_pool.index(None), vit_fquant.py:282
+        if model._plan is None:
+            model.freeze(dev)
+        _, names, sums = model._plan.forward_ddv(torch.cat((x, xa), 0), [int(b) for b in bit_config], with_linear)
+    else:
+        names = stage_names(model.depth, with_linear)
+        a = _hooked_outputs(model, x, bit_config, names, fused_state)
+        b = _hooked_outputs(model, xa, bit_config, names, fused_state)
+        if dev.type == 'cuda':
+            sums = torch.ops.p2vit.pair_cosine(a, b, [None] * len(a))
+        else:
+            sums = pair_cosine_cpu(a, b)
+    d = ddv_from_sums(sums)
+    return {nm: d[k] for k, nm in enumerate(names)}
+
+
+def similarity(ddv_a, ddv_b):
+    """ModelDiff's metric: per stage both DDVs have, the cosine of the two vectors (fp64)."""
+    out = {}
+    for k in ddv_a:
+        if k in ddv_b:
+            a, b = ddv_a[k].double().cpu(), ddv_b[k].double().cpu()
+            out[k] = float((a * b).sum() / (torch.sqrt((a * a).sum()) * torch.sqrt((b * b).sum())))
+    return out
+
+
+def reference_similarity(ddv_a, ddv_b):
+    """what calculate_and_print_similarities:118-131 prints: it walks the two vectors ELEMENT by element, so each "cosine" is the
+    product of two signs; the printed number is the mean sign agreement x 100 (a zero entry gives NaN, as there)."""
+    out = {}
+    for k in ddv_a:
+        if k in ddv_b:
+            a, b = ddv_a[k].double().cpu(), ddv_b[k].double().cpu()
+            out[k] = float(((a / a.abs()) * (b / b.abs()) * 100).mean())
+    return out
+
+
+def _logits(model, x):
+    out = model(x)
+    return out[0] if isinstance(out, (tuple, list)) else out
+
+
+def pgd_objective(yhat, y):
+    """what the attack maximises: minus the batch mean of the squared error to ``y``, the first logit at full weight and the mean over
+    the remaining logits at a tenth (the objective of modeldiff_p2.py:163-164)."""
+    sq = (yhat - y).square()
+    return -(sq[:, 0] + 0.1 * sq[:, 1:].mean(dim=1)).mean()
+
+
+class AttackPGD(nn.Module):
+    """Projected gradient ascent on ``pgd_objective`` with the semantics of the reference's attack (modeldiff_p2.py:152-178): a uniform
+    random start inside the epsilon ball around the inputs, then ``num_steps`` steps of ``step_size`` along the sign of the input
+    gradient, each followed by the projection onto the ball and then onto the image range [0, 1].  Kept as a perturbation ``delta``
+    around the fixed inputs; torch autograd through the float module graph of ``basic_net``."""
+
+    def __init__(self, basic_net, epsilon, step_size, num_steps):
+        super().__init__()
+        self.basic_net = basic_net
+        self.epsilon, self.step_size, self.num_steps = float(epsilon), float(step_size), int(num_steps)
+
+    def random_start(self, inputs):
+        """the starting point: one uniform draw in [-epsilon, epsilon) per element, added to the inputs (not yet clipped to [0, 1])"""
+        noise = torch.empty_like(inputs).uniform_(-self.epsilon, self.epsilon)
+        return inputs.detach() + noise
+
+    def _project(self, x, inputs):
+        delta = (x - inputs).clamp_(-self.epsilon, self.epsilon)
+        return (inputs + delta).clamp_(0.0, 1.0)
+
+    def forward(self, inputs, targets):
+        inputs = inputs.detach()
+        x = self.random_start(inputs)
+        for _ in range(self.num_steps):
+            probe = x.clone().requires_grad_(True)
+            with torch.enable_grad():
+                value = pgd_objective(_logits(self.basic_net, probe), targets)
+                direction, = torch.autograd.grad(value, probe)
+            x = self._project(x.add(direction.sign(), alpha=self.step_size), inputs)
+        return x
+
+
+def pgd_targets(model, inputs):
+    """the targets of the attack (modeldiff_p2.py:182-192): every clean output pushed a thousandfold towards the batch mean."""
+    model.eval()
+    with torch.no_grad():
+        clean = _logits(model, inputs)
+    return 1000.0 * (clean.mean(dim=0, keepdim=True) - clean)
+
+
+def gen_adv_inputs(model, inputs, epsilon=0.3, step_size=0.01, num_steps=50):
+    """the perturbed twins of ``inputs`` (values in [0, 1]) for a float model: ``AttackPGD`` towards ``pgd_targets``."""
+    attack = AttackPGD(model, epsilon, step_size, num_steps)
+    return attack(inputs, pgd_targets(model, inputs)).detach()
+
+
+def main(argv=None):
+    from . import harness, synth
+    from .config import Config
+    p = argparse.ArgumentParser(description='float vs quantized DDV on synthetic data (modeldiff_p2.py)')
+    p.add_argument('--model', default='deit_small')
+    p.add_argument('--bits', default='8', choices=['8', '4', 'mixed'])
+    p.add_argument('--n', default=50, type=int, help='seed samples')
+    p.add_argument('--steps', default=50, type=int, help='PGD steps')
+    p.add_argument('--seed', default=0, type=int)
+    p.add_argument('--device', default='cuda')
+    p.add_argument('--result-name', default='ddv_result')
+    args = p.parse_args(argv)
+    device = torch.device(args.device)
+    fp = harness.str2model(args.model)(cfg=Config(True, True, 'minmax'))
+    if not hasattr(fp, 'arch') or not hasattr(fp, 'depth'):
+        raise NotImplementedError('the DDV tool covers the ViT / DeiT models')
+    fp.load_state_dict(synth.vit_state_dict(fp.arch, args.seed), strict=False)
+    fp = fp.to(device).eval()
+    q = copy.deepcopy(fp)
+    harness.calibrate_model(q, synth.images(args.seed + 1, 10, fp.arch['img_size']).to(device))
+    L = 4 * fp.depth + 2
+    bits = {'8': [8] * L, '4': [4] * L, 'mixed': [8 if (i * 7 + 3) % 5 < 3 else 4 for i in range(L)]}[args.bits]
+    x = synth.images(args.seed + 2, args.n, fp.arch['img_size']).to(device)
+    x = (x - x.amin()) / (x.amax() - x.amin())                      # the attack works on images in [0, 1]
+    torch.manual_seed(args.seed)
+    adv = gen_adv_inputs(fp, x, num_steps=args.steps)
+    d_fp = compute_ddv(fp, x, adv, None)
+    d_q = compute_ddv(q, x, adv, bits)
+    sim, ref = similarity(d_fp, d_q), reference_similarity(d_fp, d_q)
+    for k in d_fp:
+        print('%-24s cosine %+.6f   sign agreement %.2f%%' % (k, sim[k], ref[k]))
+    os.makedirs(args.result_name, exist_ok=True)
+    path = os.path.join(args.result_name, 'ddv.pkl')
+    with open(path, 'wb') as f:
+        pickle.dump({'float': {k: v.cpu().numpy() for k, v in d_fp.items()}, 'quantized': {k: v.cpu().numpy() for k, v in d_q.items()},
+                     'similarity': sim, 'reference_similarity': ref, 'bits': bits}, f)
+    print('%d stages, %d samples -> %s' % (len(d_fp), args.n, path))
+    return sim
+
+
+if __name__ == '__main__':
+    main()

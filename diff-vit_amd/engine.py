@@ -81,6 +81,15 @@ class CkaLayer(C.Structure):
     _fields_ = [('x', _p), ('y', _p), ('features', _ll), ('ldx', _ll), ('ldy', _ll)]
 
 
+COS_I8, COS_F32 = 0, 1
+
+
+class CosLayer(C.Structure):
+    """``p2v_cos_layer``: one stage of a pair-cosine reduction (n samples of rows x cols int8 codes or fp32 values in a and in b;
+    strides in elements; scale None or per-channel fp32 [cols])."""
+    _fields_ = [('a', _p), ('b', _p), ('scale', _p), ('sample_stride', _ll), ('row_stride', _ll), ('rows', _i), ('cols', _i), ('dtype', _i)]
+
+
 class P2VError(RuntimeError):
     pass
 
@@ -131,6 +140,16 @@ def lib():
     L.p2v_cka_workspace_bytes.restype = C.c_size_t
     L.p2v_cka_grams.argtypes = [C.POINTER(CkaLayer), _i, _i, _p, _p, C.c_size_t, _p]
     L.p2v_hsic_accumulate.argtypes = [_p, _i, _p, _i, _i, _p, _p, _p, _i, _p]
+    if hasattr(L, 'p2v_forward_ddv'):             # the DDV entry points are additive, found by their symbols (side builds of older revisions lack them)
+        L.p2v_pair_cosine_workspace_bytes.argtypes = [C.POINTER(CosLayer), _i, _i]
+        L.p2v_pair_cosine_workspace_bytes.restype = C.c_size_t
+        L.p2v_pair_cosine.argtypes = [C.POINTER(CosLayer), _i, _i, _p, _p, C.c_size_t, _p]
+        L.p2v_ddv_stage_count.argtypes = [_p, _i]
+        L.p2v_ddv_workspace_bytes.argtypes = [_p, _i]
+        L.p2v_ddv_workspace_bytes.restype = C.c_size_t
+        L.p2v_ddv_tap_scratch_bytes.argtypes = [_p, _i]
+        L.p2v_ddv_tap_scratch_bytes.restype = C.c_size_t
+        L.p2v_forward_ddv.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _p, C.c_size_t, _p, _p]
     L.p2v_forward_profile.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_int32), _i]
     L.p2v_forward_profile_begin.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(_p)]

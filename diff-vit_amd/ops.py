@@ -13,6 +13,7 @@ one without the built library raises ``RuntimeError`` from ``engine.lib()``.
     torch.ops.p2vit.forward(plan_handle, images, bit_config)                    VisionTransformer.forward  vit_fquant.py:780-799
     torch.ops.p2vit.cka_grams(xs, ys)                                           _generate_gram_matrix      efficient_CKA.py:23-39
     torch.ops.p2vit.hsic_accumulate(g1, g2, acc, self1, self2)                  update_state*              efficient_CKA.py:41-58
+    torch.ops.p2vit.pair_cosine(a, b, scales)                                   per-sample cosine sums     modeldiff_p2.py:101-108
 """
 import ctypes as C
 
@@ -32,6 +33,7 @@ _LIB.define('lis_attention_rows(Tensor qkv, int heads, float s_qkv_sq, float qk_
 _LIB.define('forward(int plan, Tensor images, int[] bit_config) -> Tensor')
 _LIB.define('cka_grams(Tensor[] xs, Tensor[] ys) -> Tensor')
 _LIB.define('hsic_accumulate(Tensor g1, Tensor g2, Tensor(a!) acc, Tensor(b!)? self1, Tensor(c!)? self2) -> ()')
+_LIB.define('pair_cosine(Tensor[] a, Tensor[] b, Tensor?[] scales) -> Tensor')
 
 
 def _f32(t):
@@ -183,6 +185,76 @@ def _hsic_accumulate(g1, g2, acc, self1, self2):
                                             E.stream_ptr(g1.device)))
 
 
+def _cos_view(t, n):
+    """(tensor kept alive, rows, cols, sample stride, row stride) of ``t`` as n samples of rows x cols int8 codes / fp32 values with
+    16-byte aligned strides.  A [n, rows, cols] view whose strides already fit is taken as it is; anything else is made contiguous,
+    padded with zeros to whole 16-byte groups (they add nothing to a sum) and cut into rows of its last dimension, which gives the
+    kernel workgroups to split a sample over (a sample's sums do not depend on how its elements are arranged in rows)."""
+    if t.dim() == 0 or t.shape[0] != n:
+        raise AssertionError('pair_cosine: every operand needs %d samples (got shape %s)' % (n, tuple(t.shape)))
+    if t.dtype != torch.int8:
+        t = t.float()
+    vec = 16 // t.element_size()
+    if t.dim() == 3 and t.stride(2) == 1 and t.stride(1) % vec == 0 and t.stride(0) % vec == 0 and t.stride(1) >= t.shape[2] \
+            and t.data_ptr() % 16 == 0:
+        return t, t.shape[1], t.shape[2], t.stride(0), t.stride(1)
+    cols = t.shape[-1] if t.dim() >= 3 and t.shape[-1] % vec == 0 else 0
+    flat = t.reshape(n, -1)
+    Fn = flat.shape[1]
+    if not flat.is_contiguous() or Fn % vec or flat.data_ptr() % 16:
+        buf = torch.zeros(n, (Fn + vec - 1) // vec * vec, dtype=flat.dtype, device=flat.device)
+        buf[:, :Fn] = flat
+        flat = buf
+    Fp = flat.shape[1]
+    if not cols or Fp != Fn:
+        cols = next((c for c in (4096, 1024, 256, 64, 16, 4) if c % vec == 0 and Fp % c == 0 and Fp > c), Fp)
+    return flat, Fp // cols, cols, Fp, cols
+
+
+def _pair_cosine(a, b, scales):
+    """sums [stages, n, 3] fp64 = (sum a.b, sum a.a, sum b.b) per stage and sample (p2v_pair_cosine): a[k], b[k] hold n samples each,
+    int8 codes (scales[k]: None or the per-channel fp32 scales of the LAST dimension) or floats."""
+    if not a or len(a) != len(b) or len(scales) != len(a):
+        raise AssertionError('pair_cosine: %d a, %d b, %d scales' % (len(a), len(b), len(scales)))
+    n, dev = a[0].shape[0] if a[0].dim() else 0, a[0].device
+    keep, descs = [], (E.CosLayer * len(a))()
+    for k, (x, y, sc) in enumerate(zip(a, b, scales)):
+        if x.shape != y.shape or (x.dtype == torch.int8) != (y.dtype == torch.int8) or x.device != dev or y.device != dev:
+            raise AssertionError('pair_cosine: stage %d: a %s %s on %s, b %s %s on %s' % (k, tuple(x.shape), x.dtype, x.device,
+                                                                                        tuple(y.shape), y.dtype, y.device))
+        if sc is not None:
+            if x.dtype != torch.int8 or x.dim() < 2 or sc.numel() != x.shape[-1]:
+                raise AssertionError('pair_cosine: stage %d: scales go with int8 codes, one per element of the last dimension' % k)
+            if x.dim() != 3:
+                x, y = x.reshape(n, -1, x.shape[-1]), y.reshape(n, -1, y.shape[-1])
+            if x.shape[-1] % 16:                                                 # rows padded to whole 16-byte groups, cols stay
+                Cp = (x.shape[-1] + 15) // 16 * 16
+                xp, yp = (torch.zeros(n, x.shape[1], Cp, dtype=torch.int8, device=dev) for _ in range(2))
+                xp[..., :x.shape[-1]], yp[..., :x.shape[-1]] = x, y
+                x, y = xp[..., :x.shape[-1]], yp[..., :x.shape[-1]]
+            sc = _f32(sc.reshape(-1)).to(dev)
+            keep.append(sc)
+        xv, yv = _cos_view(x, n), _cos_view(y, n)
+        if xv[1:] != yv[1:]:                                                     # two different views of equal shapes: plain copies
+            if sc is not None:
+                raise AssertionError('pair_cosine: stage %d: scaled operands must share their strides' % k)
+            xv, yv = _cos_view(x.contiguous(), n), _cos_view(y.contiguous(), n)
+        keep += [xv[0], yv[0]]
+        d = descs[k]
+        d.a, d.b, d.scale = xv[0].data_ptr(), yv[0].data_ptr(), None if sc is None else sc.data_ptr()
+        d.rows, d.cols, d.sample_stride, d.row_stride = xv[1], xv[2], xv[3], xv[4]
+        d.dtype = E.COS_I8 if xv[0].dtype == torch.int8 else E.COS_F32
+    L = E.lib()
+    with torch.cuda.device(dev):
+        nbytes = L.p2v_pair_cosine_workspace_bytes(descs, len(a), n)
+        if nbytes == 0:
+            E.check(L.p2v_pair_cosine(descs, len(a), n, None, None, 0, None))       # raises with the validation message
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(len(a), n, 3, dtype=torch.float64, device=dev)
+        E.check(L.p2v_pair_cosine(descs, len(a), n, E.ptr(out), E.ptr(ws), nbytes, E.stream_ptr(dev)))
+    return out
+
+
 _LIB.impl('fake_quant', _fake_quant, 'CUDA')
 _LIB.impl('quantize_patchify', _quantize_patchify, 'CUDA')
 _LIB.impl('linear_requant', lambda x, w, cs, b, inv: _linear(E.EPI_REQUANT, x, w, cs, b, inv), 'CUDA')
@@ -193,6 +265,7 @@ _LIB.impl('lis_attention_rows', _lis_attention_rows, 'CUDA')
 _LIB.impl('forward', _forward, 'CUDA')
 _LIB.impl('cka_grams', _cka_grams, 'CUDA')
 _LIB.impl('hsic_accumulate', _hsic_accumulate, 'CUDA')
+_LIB.impl('pair_cosine', _pair_cosine, 'CUDA')
 
 OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'lis_attention_rows', 'forward', 'cka_grams',
-       'hsic_accumulate')
+       'hsic_accumulate', 'pair_cosine')

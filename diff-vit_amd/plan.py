@@ -406,6 +406,42 @@ class FrozenPlan:
             bufs[0] = bufs[0].view(B, g, g, self.D).permute(0, 3, 1, 2)
         return out, bufs
 
+    def ddv_stage_names(self, with_linear=False):
+        """names of the ``forward_ddv`` stages in module order (``ddv.stage_names``: the oracle's tap names, plus the QLinear outputs)."""
+        from .ddv import stage_names
+        return stage_names(self.depth, with_linear)
+
+    def ddv_tap_bytes(self, n):
+        """bytes of the one fp32 buffer ``forward_ddv(with_linear=True)`` needs for n pairs: the largest single tap of 2n images."""
+        return int(E.lib().p2v_ddv_tap_scratch_bytes(self._handle, n))
+
+    def forward_ddv(self, images_2n, bit_config, with_linear=False):
+        """p2v_forward_ddv: ``images_2n`` holds n clean images followed by their n perturbed twins.  Returns (logits [2n, classes],
+        stage names, sums): sums is fp64 [stages, n, 3] = (sum a.b, sum a.a, sum b.b) of every stage's activation on image i and on
+        image n + i, reduced from the int8 codes between the launches of the ONE forward (``ddv.ddv_from_sums`` turns them into a
+        DDV).  The only fp32 activation memory is one tap of 2n images (``ddv_tap_bytes``), and only with ``with_linear``."""
+        images, cfg = self._check(images_2n, bit_config)
+        B = images.shape[0]
+        if B % 2:
+            raise AssertionError('forward_ddv takes n clean images followed by their n perturbed twins: %d images' % B)
+        n = B // 2
+        L = E.lib()
+        names = self.ddv_stage_names(with_linear)
+        assert len(names) == L.p2v_ddv_stage_count(self._handle, int(with_linear))
+        with torch.cuda.device(self.device):
+            nbytes = L.p2v_ddv_workspace_bytes(self._handle, n)
+            if self._ws is None or self._ws.numel() < nbytes:
+                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                self._ws_batch = max(self._ws_batch, B)
+            ws = self._ws
+            out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
+            sums = torch.empty(len(names), n, 3, dtype=torch.float64, device=self.device)
+            tap = torch.empty(self.ddv_tap_bytes(n), dtype=torch.uint8, device=self.device) if with_linear else None
+            E.check(L.p2v_forward_ddv(self._handle, E.ptr(images), n, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(),
+                                      int(with_linear), E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(sums),
+                                      E.stream_ptr(self.device)))
+        return out, names, sums
+
     def slice_sizes(self, batch, n_streams=3):
         """Batch slices of ``forward_streams`` for up to ``n_streams`` side streams plus the caller's own stream (256 -> 68 + 68 + 68 + 52).
         Four kernels in flight on four hardware queues is what the device sustains - a fourth SIDE stream (five streams with the caller's)

@@ -509,6 +509,50 @@ int p2v_cka_grams(const p2v_cka_layer* layers, int n_layers, int n, float* grams
 int p2v_hsic_accumulate(const float* g1, int l1, const float* g2, int l2, int n, void* acc, void* self1, void* self2, int dtype,
                         void* stream);
 
+/* ---- DDV model diff (additive: no structure, existing entry point or P2V_ABI_VERSION changes; a binding finds it by its symbols) -----
+ * modeldiff_p2.compute_ddv:84-116 takes, per hooked layer and seed sample, the cosine between the layer's activation on a clean input
+ * and on its perturbed twin.  One stage of that: n samples of rows x cols elements in `a` and in `b`, sample i at + i * sample_stride,
+ * row r at + r * row_stride (both in ELEMENTS); int8 codes or fp32 values.  `scale` (int8 only): per-channel fp32 [cols], the value of an
+ * element is scale[c] * code - the PTF scales of the residual stream; NULL: one scale for the tensor, which a cosine does not see.
+ * Pointers and strides (in bytes) must be multiples of 16: P2V_E_ARG otherwise. */
+enum { P2V_COS_I8 = 0, P2V_COS_F32 = 1 };
+typedef struct p2v_cos_layer {
+  const void* a;       /* dev, n samples */
+  const void* b;       /* dev, n samples */
+  const float* scale;  /* dev fp32 [cols] or NULL */
+  long long sample_stride, row_stride;   /* elements; row_stride >= cols */
+  int32_t rows, cols;  /* >= 1 each */
+  int32_t dtype;       /* P2V_COS_I8 / P2V_COS_F32 */
+} p2v_cos_layer;
+size_t p2v_pair_cosine_workspace_bytes(const p2v_cos_layer* layers, int n_layers, int n);
+/* sums: dev fp64 [n_layers][n][3] = sum a.b, sum a.a, sum b.b over the dequantised values of sample i.  int8 without scale: the exact
+ * integer sums of the codes (v_dot4_i32_i8 into int64, converted once; rows * cols < 2^39).  int8 with scale: per-channel integer sums,
+ * then sum_c (double)s_c^2 * S_c in fp64.  fp32: fp64 products (exact) and sums.  A sample is split over workgroups by (n, rows, cols,
+ * dtype) only and the partials are combined in a fixed order, no atomics: bitwise repeatable.  layers: HOST array (copied to the
+ * workspace before the call returns); ws 256-byte aligned.  Two launches on `stream`. */
+int p2v_pair_cosine(const p2v_cos_layer* layers, int n_layers, int n, double* sums, void* ws, size_t ws_bytes, void* stream);
+
+/* The quantized model's DDV inside the fused forward.  images: dev fp32 [2n][in_chans][img][img], n clean images then their n perturbed
+ * twins; logits: dev fp32 [2n][num_classes], equal to p2v_forward's.  Right after the launch that completes a stage, two small launches
+ * reduce rows [0, n*tokens) of the live int8 buffer against rows [n*tokens, 2n*tokens).  Stages, in module order (sums: dev fp64
+ * [p2v_ddv_stage_count][n][3]):
+ *   qact1                                          "x" after the class-token fill, per-channel scales
+ *   blocks.i.attn.qact1 / attn.qact2                "qkv" / "att", one scale each (exact integer sums)
+ *   blocks.i.qact2                                  "x" after proj + residual, per-channel scales
+ *   blocks.i.mlp.qact1                              "hid" (exact)
+ *   blocks.i.qact4                                  "x" after fc2 + residual, per-channel scales
+ *   qact2, act_out                                  the class rows after the final norm (exact), the logits (fp32)
+ * = 5 * depth + 3.  with_linear != 0 adds the fp32 outputs of blocks.i.attn.qkv / attn.proj / mlp.fc1 / mlp.fc2 (each in front of the
+ * QAct that follows it) and of `head` (in front of act_out), 4 * depth + 1 more: every one is written to the ONE buffer tap_scratch
+ * (p2v_ddv_tap_scratch_bytes: the largest single tap of 2n images) by the mechanisms of p2v_forward_linear_taps and reduced before the
+ * next one overwrites it.  tap_scratch may be NULL when with_linear == 0.  ws: p2v_ddv_workspace_bytes(plan, n) (the forward's
+ * workspace of 2n images plus the reduction's partials).  Every row of the last block is computed, as in the tap entry points. */
+int p2v_ddv_stage_count(const p2v_plan* plan, int with_linear);
+size_t p2v_ddv_workspace_bytes(const p2v_plan* plan, int n);
+size_t p2v_ddv_tap_scratch_bytes(const p2v_plan* plan, int n);
+int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                    size_t ws_bytes, int with_linear, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream);
+
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
 
