@@ -18,6 +18,14 @@
  *   - activations between kernels are int8 codes, row-major [rows][channels]; "rows" = batch*tokens.
  *   - all scales named *_pot are exact powers of two (the reference's PoT observers, minmax.py:247-251);
  *     per-channel PTF scales (ptf.py:51,133) are arbitrary fp32 and are divided by, as the reference does.
+ *   - output footprint: an entry point writes the elements of its result and nothing else - no byte in front of the first or behind the
+ *     last row, and where rows are strided (ldo, out_stride, p2v_winattn.out_stride) no byte of the padding between them, which keeps what
+ *     the caller put there.  Particulars, stated at the entry points: the patchify entry points write zeros to the columns [C*P*P, k_pad);
+ *     P2V_EPI_EMBED leaves the class-token rows alone; optional side outputs (tap_out, out_codes, ln_out, probs_k) are dense results with
+ *     the same rule.  Input padding - the bytes between rows when lda / row_stride / qkv_stride exceed the row, and the columns [width, K) a
+ *     contraction walks through zero weight columns - may hold anything: it never reaches a result.
+ *     (tests/test_kernel_edges_gpu.py runs the per-operator entry points listed below into sentinel-filled buffers, and the class-token
+ *     fill of p2v_forward on a sentinel-filled workspace.)
  *
  * Limits of what is instantiated (everything else returns P2V_E_UNSUPPORTED, at plan creation where the geometry is known):
  *   - ViT attention: head_dim 32, 48, 64, 80, 96 or 128 (round 4; before: 32 / 64); up to P2V_MAX_TOKENS_STREAMED = 4096 tokens per image.  The
@@ -347,12 +355,15 @@ int p2v_u8_patchify(const uint8_t* img, int layout, const void* lut_i8, int batc
  * reference's operation order.  lda/ldo in elements.  `out` is int8 [M][ldo] except HEAD (fp32 [M][ldo]);
  * when out_codes != NULL the HEAD epilogue also writes the int8 logit codes there ([M][ldo]).
  * K is a multiple of 64 and MAY exceed lda (a width that is not a multiple of 64: the weight columns [width, K) are zero): the
- * contraction then walks into the next row, so (M-1)*lda + K bytes of A must be readable.  ldo >= N.  P2V_E_SHAPE otherwise. */
+ * contraction then walks into the next row, so (M-1)*lda + K bytes of A must be readable.  ldo >= N.  P2V_E_SHAPE otherwise.
+ * Written: columns [0, N) of rows [0, M) of `out` (and of out_codes, same ldo) - never the columns [N, ldo) - and tap_out as a dense
+ * [M][N]; P2V_EPI_EMBED: columns [0, N) of the rows b*(patches+1) + 1 + p, never a class-token row b*(patches+1). */
 int p2v_gemm_i8(int epilogue_kind, const int8_t* A, int lda, int M, int K, int N, const p2v_linear* lin,
                 const p2v_epilogue* epi, void* out, int ldo, int8_t* out_codes, void* stream);
 
 /* rows x C int8 -> rows x C int8; row r of the input starts at x + r*row_stride (lets the final norm
- * touch only the cls rows, vit_fquant.py:766-767).  C: a multiple of 4 up to 2048; out_stride >= C. */
+ * touch only the cls rows, vit_fquant.py:766-767).  C: a multiple of 4 up to 2048; out_stride >= C; bytes [C, out_stride) of an
+ * output row are not written. */
 int p2v_int_layernorm(const int8_t* x, long long row_stride, int rows, int C, const p2v_ln* ln,
                       int8_t* out, long long out_stride, void* stream);
 
@@ -402,7 +413,9 @@ typedef struct p2v_winattn {
                                  * regions get -100 (swin_quant.py:325-349)                                                   */
   int32_t ws, n_windows;
   int32_t qkv_stride;           /* bytes between qkv rows (0 = dense: 3*heads*head_dim)                  */
-  int32_t out_stride;           /* bytes between out rows (0 = dense: heads*head_dim); lets the next GEMM read K padded to 64 */
+  int32_t out_stride;           /* bytes between out rows (0 = dense: heads*head_dim); lets the next GEMM read K padded to 64.  The kernel writes
+                                 * the heads*head_dim codes of a row and NEVER the padding behind them: it keeps the caller's bytes, which
+                                 * that GEMM meets with zero weight columns */
 } p2v_winattn;
 
 /* qkv int8 [batch][tokens_per_image][3*heads*head_dim] (qact1 codes, natural token order); out int8
