@@ -1230,6 +1230,28 @@ int p2v_pair_cosine(const p2v_cos_layer* layers, int n_layers, int n, double* su
   return launch_rc(p2v_launch_pair_cosine(descs, w, n, sums, ws, (hipStream_t)stream), "pair_cosine");
 }
 
+// ---- scoring of the logits (p2vit_score.hip) -------------------------------------------------------------------------------------------
+int p2v_score_logits(const float* logits, long long ld, int rows, int classes, const long long* labels, int32_t* ranks, double* loss,
+                     void* stream) {
+  if (!logits || !labels || !ranks || !loss) return fail(P2V_E_ARG, "p2v_score_logits: null argument");
+  if (rows < 0 || classes < 1 || ld < classes) return fail(P2V_E_ARG, "p2v_score_logits: rows %d, classes %d, ld %lld", rows, classes, ld);
+  if (rows == 0) return P2V_OK;
+  return launch_rc(p2v_launch_score_rows(logits, ld, rows, classes, labels, ranks, loss, (hipStream_t)stream), "score_logits");
+}
+
+size_t p2v_score_totals_bytes(int n_k) { return n_k < 1 || n_k > P2V_SCORE_MAX_K ? 0 : (size_t)(3 + 3 * n_k) * 8; }
+
+int p2v_score_accumulate(const int32_t* ranks, const double* loss, int rows, const int* ks, int n_k, void* totals_slot, void* stream) {
+  if (!ranks || !loss || !ks || !totals_slot) return fail(P2V_E_ARG, "p2v_score_accumulate: null argument");
+  if (rows < 0) return fail(P2V_E_ARG, "p2v_score_accumulate: rows %d", rows);
+  if (n_k < 1 || n_k > P2V_SCORE_MAX_K) return fail(P2V_E_ARG, "p2v_score_accumulate: %d values of k (1 ... %d)", n_k, P2V_SCORE_MAX_K);
+  for (int q = 0; q < n_k; ++q)
+    if (ks[q] < 1) return fail(P2V_E_ARG, "p2v_score_accumulate: k = %d", ks[q]);
+  if ((uintptr_t)totals_slot % 8) return fail(P2V_E_ARG, "p2v_score_accumulate: the totals slot must be 8-byte aligned");
+  if (rows == 0) return P2V_OK;
+  return launch_rc(p2v_launch_score_accumulate(ranks, loss, rows, ks, n_k, totals_slot, (hipStream_t)stream), "score_accumulate");
+}
+
 int p2v_ddv_stage_count(const p2v_plan* plan, int with_linear) {
   if (!plan) return fail(P2V_E_ARG, "p2v_ddv_stage_count: null plan");
   return 5 * plan->d.depth + 3 + (with_linear ? 4 * plan->d.depth + 1 : 0);

@@ -82,6 +82,7 @@ class CkaLayer(C.Structure):
 
 
 COS_I8, COS_F32 = 0, 1
+SCORE_MAX_K = 8                                  # P2V_SCORE_MAX_K: values of k per totals slot
 
 
 class CosLayer(C.Structure):
@@ -150,6 +151,11 @@ def lib():
         L.p2v_ddv_tap_scratch_bytes.argtypes = [_p, _i]
         L.p2v_ddv_tap_scratch_bytes.restype = C.c_size_t
         L.p2v_forward_ddv.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _p, C.c_size_t, _p, _p]
+    if hasattr(L, 'p2v_score_logits'):            # the scoring entry points are additive, found by their symbols
+        L.p2v_score_logits.argtypes = [_p, _ll, _i, _i, _p, _p, _p, _p]
+        L.p2v_score_totals_bytes.argtypes = [_i]
+        L.p2v_score_totals_bytes.restype = C.c_size_t
+        L.p2v_score_accumulate.argtypes = [_p, _p, _i, C.POINTER(C.c_int), _i, _p, _p]
     L.p2v_forward_profile.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_int32), _i]
     L.p2v_forward_profile_begin.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(_p)]

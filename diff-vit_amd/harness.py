@@ -54,6 +54,9 @@ def build_parser():
     p.add_argument('--uint8-input', default=False, action='store_true',
                    help='loaders yield uint8 NHWC crops (a quarter of the bytes to copy) and the model normalises them on the device '
                         '(forward_uint8 with the family\'s MODEL_STATS; logits identical to the fp32 loaders)')
+    p.add_argument('--device-metrics', default=False, action='store_true',
+                   help='score on the device (score.DeviceMeter): Prec@k with the lower-index-first tie rule and the fp64 loss, no host '
+                        'synchronisation per batch; with --mixed the search scores whole populations batch-major (validate_many)')
     p.add_argument('--search-pop', default=25, type=int, help='--mixed: population size (test_quant.py:340)')
     p.add_argument('--search-iter', default=8, type=int, help='--mixed: evolutionary iterations (test_quant.py:343)')
     p.add_argument('--search-max-configs', default=50, type=int, help='--mixed: Pareto candidates kept (test_quant.py:281)')
@@ -244,8 +247,11 @@ class DevicePrefetcher:
         return d, t
 
 
-def validate(args, val_loader, model, criterion, device, bit_config=None):
-    """test_quant.py:418-466; additionally returns images/sec of the forward calls."""
+def validate(args, val_loader, model, criterion, device, bit_config=None, device_metrics=False):
+    """test_quant.py:418-466; additionally returns images/sec of the forward calls.  ``device_metrics=True``: the same pass scored by
+    ``score.DeviceMeter`` (``_validate_device_metrics``); ``criterion`` is not used then."""
+    if device_metrics:
+        return _validate_device_metrics(args, val_loader, model, device, bit_config)
     batch_time, losses, top1, top5 = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
     model.eval()
     val_start_time = end = time.time()
@@ -278,6 +284,65 @@ def validate(args, val_loader, model, criterion, device, bit_config=None):
                                                                               time=val_end_time - val_start_time))
     print(' * forward throughput %.1f images/sec' % (n_img / max(fwd, 1e-9)))
     return losses.avg, top1.avg, top5.avg
+
+
+def _validate_device_metrics(args, val_loader, model, device, bit_config=None):
+    """``validate`` without a host synchronisation per batch: every batch enqueues the forward and the two score kernels, the meter is
+    read at ``print_freq`` batches and at the end.  Prec@k follows the defined tie rule (among equal logits the lower class index ranks
+    first) and the loss is the fp64 cross-entropy; one more line reports the bracket [sure, possible] any tie order lands in.  The
+    printed running values are the averages so far (there is no per-batch value without a read per batch)."""
+    from .score import DeviceMeter
+    meter = DeviceMeter((1, 5), device=device)
+    model.eval()
+    val_start_time = time.time()
+    n_img = 0
+    stats = uint8_stats(args)
+    for i, (data, target) in enumerate(DevicePrefetcher(val_loader, device)):
+        with torch.no_grad():
+            output, FLOPs, distance = _forward(model, data, bit_config, stats)
+        meter.update(output, target)
+        n_img += data.size(0)
+        if i % args.print_freq == 0:
+            r = meter.result()
+            t = (time.time() - val_start_time) / (i + 1)
+            print('Test: [{0}/{1}]\t'
+                  'Time {t:.3f} ({t:.3f})\t'
+                  'Loss {loss:.4f} ({loss:.4f})\t'
+                  'Prec@1 {top1:.3f} ({top1:.3f})\t'
+                  'Prec@5 {top5:.3f} ({top5:.3f})'.format(i, len(val_loader), t=t, loss=r['loss'], top1=r['prec'][1], top5=r['prec'][5]))
+    r = meter.result()
+    val_end_time = time.time()
+    print(' * Prec@1 {top1:.3f} Prec@5 {top5:.3f} Time {time:.3f}'.format(top1=r['prec'][1], top5=r['prec'][5],
+                                                                              time=val_end_time - val_start_time))
+    print(' * ties: Prec@1 in [{0:.3f}, {1:.3f}] Prec@5 in [{2:.3f}, {3:.3f}] (sure / possible under any tie order; {4} rows, {5} invalid labels)'
+          .format(r['sure'][1], r['possible'][1], r['sure'][5], r['possible'][5], r['n'], r['invalid']))
+    print(' * throughput %.1f images/sec (whole pass, scoring included)' % (n_img / max(val_end_time - val_start_time, 1e-9)))
+    return r['loss'], r['prec'][1], r['prec'][5]
+
+
+def validate_many(args, val_loader, model, device, bit_configs):
+    """[(loss, top1, top5), ...] of ``validate(..., device_metrics=True)`` for every entry of ``bit_configs``, in input order, from ONE
+    pass over the loader: batch-major, each batch is brought to the device once and forwarded under every distinct configuration into
+    a meter slot of its own (duplicates are scored once).  The mixed-precision search scores a population this way instead of
+    re-reading the validation set per candidate."""
+    from .score import DeviceMeter
+    keys = [None if bc is None else tuple(int(b) for b in bc) for bc in bit_configs]
+    distinct = list(dict.fromkeys(keys))
+    if not distinct:
+        return []
+    meter = DeviceMeter((1, 5), slots=len(distinct), device=device)
+    model.eval()
+    stats = uint8_stats(args)
+    for data, target in DevicePrefetcher(val_loader, device):
+        for s, bc in enumerate(distinct):
+            with torch.no_grad():
+                output, FLOPs, distance = _forward(model, data, None if bc is None else list(bc), stats)
+            meter.update(output, target, slot=s)
+    res = {}
+    for s, bc in enumerate(distinct):
+        r = meter.result(s)
+        res[bc] = (r['loss'], r['prec'][1], r['prec'][5])
+    return [res[k] for k in keys]
 
 
 def main(argv=None):
@@ -331,14 +396,18 @@ def main(argv=None):
             def score(bc):
                 with contextlib.redirect_stdout(io.StringIO()):
                     return validate(quiet, loader, model, criterion, device, bc)[1]
+            score_many = None
+            if args.device_metrics:
+                score_many = lambda cfgs: [r[1] for r in validate_many(quiet, loader, model, device, cfgs)]
             ranked, pop = mixed_precision_search(score, FLOPs, global_distance, seed=args.seed, pop_size=args.search_pop,
-                                                 evo_iter=args.search_iter, max_configs=args.search_max_configs, slack=args.search_slack)
+                                                 evo_iter=args.search_iter, max_configs=args.search_max_configs, slack=args.search_slack,
+                                                 score_many=score_many)
             print('best mixed-precision configuration: Prec@1 %.3f' % pop[0][1])
             print(pop[0][0])
-            return validate(args, loader, model, criterion, device, pop[0][0]) + (pop[0][0],)
+            return validate(args, loader, model, criterion, device, pop[0][0], device_metrics=args.device_metrics) + (pop[0][0],)
         bit_config = [args.bits] * ((4 * arch['depth'] + 2) if 'depth' in arch else 1)
         print(bit_config)
-    return validate(args, loader, model, criterion, device, bit_config)
+    return validate(args, loader, model, criterion, device, bit_config, device_metrics=args.device_metrics)
 
 
 if __name__ == '__main__':

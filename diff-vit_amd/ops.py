@@ -14,6 +14,8 @@ one without the built library raises ``RuntimeError`` from ``engine.lib()``.
     torch.ops.p2vit.cka_grams(xs, ys)                                           _generate_gram_matrix      efficient_CKA.py:23-39
     torch.ops.p2vit.hsic_accumulate(g1, g2, acc, self1, self2)                  update_state*              efficient_CKA.py:41-58
     torch.ops.p2vit.pair_cosine(a, b, scales)                                   per-sample cosine sums     modeldiff_p2.py:101-108
+    torch.ops.p2vit.score_logits(logits, labels)                                tie-aware ranks + fp64 loss  test_quant.py:430-436, 488-501
+    torch.ops.p2vit.score_accumulate(ranks, loss, ks, totals)                   running totals of a pass   test_quant.py:437-439
 """
 import ctypes as C
 
@@ -34,6 +36,8 @@ _LIB.define('forward(int plan, Tensor images, int[] bit_config) -> Tensor')
 _LIB.define('cka_grams(Tensor[] xs, Tensor[] ys) -> Tensor')
 _LIB.define('hsic_accumulate(Tensor g1, Tensor g2, Tensor(a!) acc, Tensor(b!)? self1, Tensor(c!)? self2) -> ()')
 _LIB.define('pair_cosine(Tensor[] a, Tensor[] b, Tensor?[] scales) -> Tensor')
+_LIB.define('score_logits(Tensor logits, Tensor labels) -> (Tensor ranks, Tensor loss)')
+_LIB.define('score_accumulate(Tensor ranks, Tensor loss, int[] ks, Tensor(a!) totals) -> ()')
 
 
 def _f32(t):
@@ -255,6 +259,42 @@ def _pair_cosine(a, b, scales):
     return out
 
 
+def _score_logits(logits, labels):
+    """(ranks int32 [rows, 4] = gt, eq_lo, eq_hi, argmax; loss fp64 [rows]) of fp32 logits [rows, classes] against int64 labels [rows]
+    (p2v_score_logits).  A row-strided view (``stride(1) == 1``) is read in place: the columns between the rows are never touched."""
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0] or logits.shape[1] < 1:
+        raise AssertionError('score_logits: logits [rows, classes] and labels [rows] (got %s, %s)' % (tuple(logits.shape), tuple(labels.shape)))
+    if labels.device != logits.device:
+        raise AssertionError('score_logits: labels on %s, logits on %s' % (labels.device, logits.device))
+    rows, classes = logits.shape
+    if logits.dtype != torch.float32 or logits.stride(1) != 1 or (rows > 1 and logits.stride(0) < classes):
+        logits = _f32(logits)
+    ld = logits.stride(0) if rows > 1 else classes
+    labels = labels.contiguous().long()
+    ranks = torch.empty(rows, 4, dtype=torch.int32, device=logits.device)
+    loss = torch.empty(rows, dtype=torch.float64, device=logits.device)
+    with torch.cuda.device(logits.device):
+        E.check(E.lib().p2v_score_logits(E.ptr(logits), ld, rows, classes, E.ptr(labels), E.ptr(ranks), E.ptr(loss),
+                                         E.stream_ptr(logits.device)))
+    return ranks, loss
+
+
+def _score_accumulate(ranks, loss, ks, totals):
+    """fold the records of ``score_logits`` into one totals slot: int64 [3 + 3 * len(ks)] = n, invalid, hit[], sure[], possible[], and
+    the bits of the fp64 loss sum (p2v_score_accumulate)"""
+    ks = [int(k) for k in ks]
+    rows = ranks.shape[0]
+    if ranks.dtype != torch.int32 or tuple(ranks.shape) != (rows, 4) or loss.dtype != torch.float64 or tuple(loss.shape) != (rows,) \
+            or not ranks.is_contiguous() or not loss.is_contiguous():
+        raise AssertionError('score_accumulate: ranks int32 [rows, 4] and loss fp64 [rows], contiguous')
+    if totals.dtype != torch.int64 or totals.numel() != 3 + 3 * len(ks) or not totals.is_contiguous() or totals.device != ranks.device \
+            or loss.device != ranks.device:
+        raise AssertionError('score_accumulate: totals int64 [%d], contiguous, on %s' % (3 + 3 * len(ks), ranks.device))
+    with torch.cuda.device(ranks.device):
+        E.check(E.lib().p2v_score_accumulate(E.ptr(ranks), E.ptr(loss), rows, (C.c_int * max(1, len(ks)))(*ks), len(ks), E.ptr(totals),
+                                             E.stream_ptr(ranks.device)))
+
+
 _LIB.impl('fake_quant', _fake_quant, 'CUDA')
 _LIB.impl('quantize_patchify', _quantize_patchify, 'CUDA')
 _LIB.impl('linear_requant', lambda x, w, cs, b, inv: _linear(E.EPI_REQUANT, x, w, cs, b, inv), 'CUDA')
@@ -266,6 +306,8 @@ _LIB.impl('forward', _forward, 'CUDA')
 _LIB.impl('cka_grams', _cka_grams, 'CUDA')
 _LIB.impl('hsic_accumulate', _hsic_accumulate, 'CUDA')
 _LIB.impl('pair_cosine', _pair_cosine, 'CUDA')
+_LIB.impl('score_logits', _score_logits, 'CUDA')
+_LIB.impl('score_accumulate', _score_accumulate, 'CUDA')
 
 OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'lis_attention_rows', 'forward', 'cka_grams',
-       'hsic_accumulate', 'pair_cosine')
+       'hsic_accumulate', 'pair_cosine', 'score_logits', 'score_accumulate')

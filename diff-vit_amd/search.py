@@ -55,11 +55,43 @@ def omega_rank(bit_list, global_distance, mean_hessian, bit_choice=(4, 8)):
     return out
 
 
+class _Pending:
+    """scores of one phase: ``score_fn`` at once, or (``score_many``) collected and resolved by one call in ``resolve``"""
+
+    def __init__(self, score_fn, score_many):
+        self.score_fn, self.score_many, self.cfgs = score_fn, score_many, []
+
+    def __call__(self, cfg):
+        if self.score_many is None:
+            return self.score_fn(cfg)
+        self.cfgs.append(cfg)
+        return self                                    # placeholder: replaced in resolve()
+
+    def resolve(self, entries, val):
+        """``entries``: [config, score or placeholder or None] in generation order; None = rejected child, which carries the score
+        in force before it (test_quant.py:355-361).  Returns the score in force after the last entry."""
+        scores = iter(self.score_many(self.cfgs) if self.score_many is not None else ())
+        for e in entries:
+            if e[1] is self:
+                e[1] = next(scores)
+            elif e[1] is None:
+                e[1] = val
+            val = e[1]
+        self.cfgs = []
+        return val
+
+
 def evolutionary_search(score_fn, omega_list, FLOPs, constraint, rng, bit_choice=(4, 8), pop_size=25, evo_iter=8,
-                        mutate_size=10, mutate_prob=0.5, crossover_size=10, crossover_prob=0.5, log=print):
-    """test_quant.py:340-408.  ``score_fn(bit_config) -> top-1``."""
+                        mutate_size=10, mutate_prob=0.5, crossover_size=10, crossover_prob=0.5, log=print, score_many=None):
+    """test_quant.py:340-408.  ``score_fn(bit_config) -> top-1``.  ``score_many(list of bit_configs) -> list of scores`` (optional):
+    the initial population, and then each iteration's mutation and crossover children together, are scored by ONE call.  Within such a
+    phase nothing the ``random`` walk consumes depends on a score (the parents stay as they are until all children of the iteration
+    exist), so the configurations are generated first, scored together, and the scores assigned afterwards: same seed and same score
+    function give the same population as the sequential path."""
     bit_choice = list(bit_choice)
-    parent = [[omega_list[i][0], score_fn(omega_list[i][0])] for i in range(min(pop_size, len(omega_list)))]
+    score = _Pending(score_fn, score_many)
+    parent = [[omega_list[i][0], score(omega_list[i][0])] for i in range(min(pop_size, len(omega_list)))]
+    score.resolve(parent, 0.0)
     parent.sort(key=lambda x: x[-1], reverse=True)
     val = parent[0][1] if parent else 0.0
     for evo in range(evo_iter):
@@ -67,10 +99,8 @@ def evolutionary_search(score_fn, omega_list, FLOPs, constraint, rng, bit_choice
         while True:
             old = rng.choice(parent)[0]
             new = [b if rng.random() < mutate_prob else rng.choice(bit_choice) for b in old]
-            if not model_size(FLOPs, new) > constraint and new not in seen:
-                val = score_fn(new)
+            children.append([new, score(new) if not model_size(FLOPs, new) > constraint and new not in seen else None])
             seen.append(new)
-            children.append([new, val])
             if len(seen) > mutate_size:
                 break
         seen = []
@@ -81,12 +111,11 @@ def evolutionary_search(score_fn, omega_list, FLOPs, constraint, rng, bit_choice
                     break
                 continue
             new = [x if rng.random() < crossover_prob else y for x, y in zip(a, b)]
-            if not model_size(FLOPs, new) > constraint and new not in seen:
-                val = score_fn(new)
+            children.append([new, score(new) if not model_size(FLOPs, new) > constraint and new not in seen else None])
             seen.append(new)
-            children.append([new, val])
             if len(seen) > crossover_size:
                 break
+        val = score.resolve(children, val)
         for child in children:
             if child[1] > parent[-1][1]:
                 parent.append(child)
@@ -96,8 +125,9 @@ def evolutionary_search(score_fn, omega_list, FLOPs, constraint, rng, bit_choice
     return parent
 
 
-def mixed_precision_search(score_fn, FLOPs, global_distance, mean_hessian=None, seed=0, log=print, **kw):
-    """the whole block test_quant.py:253-408; returns (pareto-ranked list, final population)."""
+def mixed_precision_search(score_fn, FLOPs, global_distance, mean_hessian=None, seed=0, log=print, score_many=None, **kw):
+    """the whole block test_quant.py:253-408; returns (pareto-ranked list, final population).  ``score_many``: see
+    ``evolutionary_search``; the top-5 validation is one call of it as well."""
     assert len(FLOPs) - 1 == len(global_distance)
     if mean_hessian is None:
         mean_hessian = [1.0] * len(global_distance)
@@ -110,7 +140,10 @@ def mixed_precision_search(score_fn, FLOPs, global_distance, mean_hessian=None, 
     log('Hessien-Based Validating...')
     for i in range(min(5, len(ranked))):
         log(ranked[i][0])
-        score_fn(ranked[i][0])
+        if score_many is None:
+            score_fn(ranked[i][0])
+    if score_many is not None:
+        score_many([ranked[i][0] for i in range(min(5, len(ranked)))])
     log('Start Evolutionary.......')
     evo = {k: v for k, v in kw.items() if k in ('pop_size', 'evo_iter', 'mutate_size', 'mutate_prob', 'crossover_size', 'crossover_prob')}
-    return ranked, evolutionary_search(score_fn, ranked, FLOPs, constraint, rng, log=log, **evo)
+    return ranked, evolutionary_search(score_fn, ranked, FLOPs, constraint, rng, log=log, score_many=score_many, **evo)

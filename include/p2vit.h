@@ -566,6 +566,41 @@ size_t p2v_ddv_tap_scratch_bytes(const p2v_plan* plan, int n);
 int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
                     size_t ws_bytes, int with_linear, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream);
 
+/* ---- Scoring of the logits (additive: no structure, existing entry point or P2V_ABI_VERSION changes; a binding finds it by its symbols) --
+ * Precision@k and the cross-entropy loss on the device, with a DEFINED tie rule.  The logits are 8-bit codes times a power of two, so the
+ * classes of an image share few distinct values and ties at the top-1 / top-5 boundary are common; topk implementations order them
+ * differently.  Here: AMONG EQUAL LOGITS THE LOWER CLASS INDEX RANKS FIRST, and the records carry what a result owes to ties.
+ *
+ * p2v_score_logits: one record per row of logits (dev fp32 [rows][ld], ld >= classes; columns [classes, ld) are padding, never read)
+ * against labels (dev int64 [rows]).  With y = labels[r], x = logits[r], j over [0, classes):
+ *   ranks[r] = { gt, eq_lo, eq_hi, argmax }  (dev int32 [rows][4])
+ *       gt     = #{ j : x_j > x_y }
+ *       eq_lo  = #{ j < y : x_j == x_y }        eq_hi = #{ j > y : x_j == x_y }
+ *       argmax = the lowest index at which the row maximum occurs
+ *   loss[r] = log(sum_j exp((double)x_j - m)) + m - (double)x_y, m the row maximum, all in fp64  (dev fp64 [rows])
+ * Invalid labels: a label outside [0, classes) (torch's ignore_index = -100 included) is never used as an index; the row reports
+ * gt = -1, eq_lo = eq_hi = 0, its real argmax and loss = 0.  Nothing asserts or traps.
+ * One wave per row, fixed reduction order, no atomics: bitwise repeatable.  One launch on `stream`; rows == 0 launches nothing.
+ * P2V_E_ARG: null pointer, rows < 0, classes < 1, ld < classes. */
+#define P2V_SCORE_MAX_K 8
+int p2v_score_logits(const float* logits, long long ld, int rows, int classes, const long long* labels, int32_t* ranks, double* loss,
+                     void* stream);
+/* Running totals of a validation pass, one SLOT of p2v_score_totals_bytes(n_k) = 8 * (3 + 3 * n_k) bytes in device memory, zeroed by the
+ * caller (8-byte aligned; slots may lie back to back).  0: n_k outside 1 ... P2V_SCORE_MAX_K.
+ *   int64 n, invalid;  int64 hit[n_k], sure[n_k], possible[n_k];  double loss_sum
+ * p2v_score_accumulate folds `rows` records into the slot.  A row with gt < 0 counts in `invalid` only.  A valid row counts in n, adds
+ * its loss to loss_sum, and for each k = ks[q] (HOST array, n_k values >= 1):
+ *   hit      += gt + eq_lo < k              the defined rule (lower index first among equal logits)
+ *   sure     += gt + eq_lo + eq_hi < k      a hit under every tie order
+ *   possible += gt < k                      a hit under some tie order
+ * so any topk implementation lands in [sure, possible], and sure == possible means that ties decide nothing.
+ * One workgroup: thread t adds the losses of rows t, t + 256, ... in ascending order, the 256 partials go through a fixed tree and the
+ * result is added to loss_sum; counters are integer sums.  No atomics: the same sequence of batches gives the same bits.  Launches on one
+ * stream into one slot are ordered by the stream; the host reads the slot once, at the end of the pass.  rows == 0 launches nothing.
+ * P2V_E_ARG: null pointer, rows < 0, n_k outside 1 ... 8, a k < 1, misaligned slot. */
+size_t p2v_score_totals_bytes(int n_k);
+int p2v_score_accumulate(const int32_t* ranks, const double* loss, int rows, const int* ks, int n_k, void* totals_slot, void* stream);
+
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
 
