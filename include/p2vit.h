@@ -26,6 +26,22 @@
  *     contraction walks through zero weight columns - may hold anything: it never reaches a result.
  *     (tests/test_kernel_edges_gpu.py runs the per-operator entry points listed below into sentinel-filled buffers, and the class-token
  *     fill of p2v_forward on a sentinel-filled workspace.)
+ *     The whole-model entry points (p2v_forward, p2v_forward_u8, p2v_forward_taps, p2v_forward_linear_taps, p2v_forward_ddv) compose
+ *     these launches inside the caller's workspace, and two statements hold for them:
+ *       (1) a forward's result - logits, taps, sums - does not depend on what the workspace holds on entry: it may be uninitialised, or
+ *           left over from another batch size, bit list or entry point.  Every byte a launch reads was written by an earlier launch of the
+ *           same call or meets a zero weight column (the k-tile tail of a width that is no multiple of 64; the rows the class-row branch
+ *           of the last block leaves stale are not read);
+ *       (2) a forward writes nothing outside [workspace, workspace + p2v_workspace_bytes) - p2v_ddv_workspace_bytes for p2v_forward_ddv -
+ *           and outside its dense outputs (logits [batch][classes], each tap at its stated extent, sums, tap_scratch up to
+ *           p2v_ddv_tap_scratch_bytes).  Inside the workspace the alignment gaps between the seven buffers and the trailing 256 bytes are
+ *           never written.  Each launch of a stop_after >= 0 run, where the last block computes every row, writes exactly the
+ *           rows x cols extent of its target buffer(s) (p2v_workspace_view).  The class-row launches of a stop_after = -1 run write less
+ *           ("cls_rows": `batch` compact rows of ln / hid, the class rows of x / att); for them the statement is the weaker one that
+ *           they stay out of the gaps and the tail and change nothing outside the patch rows of x / att and the hid / ln buffers,
+ *           against a cls_rows = 0 run.
+ *     (tests/test_forward_state_gpu.py: workspace, logits, taps, sums and tap scratch in sentinel arenas under three fills, the write
+ *     map launch by launch, one workspace through a history of calls, 2 / 5 / 10 tokens per image against the oracle.)
  *
  * Limits of what is instantiated (everything else returns P2V_E_UNSUPPORTED, at plan creation where the geometry is known):
  *   - ViT attention: head_dim 32, 48, 64, 80, 96 or 128 (round 4; before: 32 / 64); up to P2V_MAX_TOKENS_STREAMED = 4096 tokens per image.  The

@@ -1,4 +1,5 @@
-"""Sentinel arenas for the GPU operator tests (tests/test_kernel_edges_gpu.py): one device allocation per operand,
+"""Sentinel arenas for the GPU footprint tests (tests/test_kernel_edges_gpu.py: the operator kernels; tests/test_forward_state_gpu.py: the
+whole-model entry points; tests/test_modeldiff_edges_gpu.py: CKA, HSIC, pair cosine): one device allocation per operand,
 
     | guard | rows of the operand, `stride` apart, padding between them | guard |
 
@@ -15,9 +16,11 @@ OFFSET = 80
 
 
 class Arena:
-    def __init__(self, rows, width, stride=None, dtype=torch.int8, sentinel=SENTINELS[0], init=None):
+    def __init__(self, rows, width, stride=None, dtype=torch.int8, sentinel=SENTINELS[0], init=None, offset=OFFSET):
         """rows x width elements of `dtype`, `stride` elements between row starts (default: dense).  init: tensor [rows][width] or None
-        (the operand region keeps the sentinel: an output)."""
+        (the operand region keeps the sentinel: an output).  offset: bytes between a 256-byte boundary and the operand - 0 for a workspace
+        (the entry points that take one ask for 256-byte alignment), 84 for a start that is 4-byte but not 16-byte aligned (the scalar
+        load paths)."""
         self.dtype, self.rows, self.width = dtype, int(rows), int(width)
         self.item = torch.empty((), dtype=dtype).element_size()
         self.stride = self.width if stride is None else int(stride)
@@ -26,7 +29,8 @@ class Arena:
         row_b, stride_b = self.width * self.item, self.stride * self.item
         # a flat operand (one row) has no rows to count: 1 MB, the reach of 4096 threads that each store 256 bytes too far
         guard = (max(65536, 256 * stride_b if self.rows > 1 else 1 << 20) + 255) // 256 * 256
-        self.start = guard + OFFSET
+        assert 0 <= int(offset) < 256
+        self.start = guard + int(offset)
         self.total = self.start + (self.rows - 1) * stride_b + row_b + guard
         host = np.full(self.total, self.sentinel, dtype=np.uint8)
         self.inside = np.zeros(self.total, dtype=bool)
@@ -59,7 +63,8 @@ class Arena:
         return torch.from_numpy(got[self.inside].copy().view(_NP[self.dtype]).reshape(self.rows, self.width))
 
 
-_NP = {torch.int8: np.int8, torch.uint8: np.uint8, torch.float32: np.float32, torch.int32: np.int32}
+_NP = {torch.int8: np.int8, torch.uint8: np.uint8, torch.float32: np.float32, torch.int32: np.int32, torch.float64: np.float64,
+       torch.int64: np.int64}
 
 
 def twice(run):

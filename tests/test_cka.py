@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from _cka_ref import centre_restatement, small_integers
 from conftest import ROOT, load_golden
 
 
@@ -131,3 +132,18 @@ def test_new_prototypes_declared_and_exported():
         assert hasattr(torch.ops.p2vit, op)
     with pytest.raises(NotImplementedError):
         torch.ops.p2vit.cka_grams([torch.zeros(4, 8)], [])               # no CPU kernel behind the op
+
+
+@pytest.mark.parametrize('n,F', [(4, 1), (5, 33), (33, 1025), (65, 4097), (256, 8193)])
+def test_centre_restatement_against_gram_matrix(n, F):
+    """the reference of the exact GPU test is itself checked: against cka.gram_matrix in fp64 (torch's own summation orders) cast to fp32,
+    within one fp32 ulp of the entry - the two differ at most in the last fp64 bits of the means, which the cast can turn into one fp32 step"""
+    import diff_vit_amd as dva
+    x, y = small_integers(n * 31 + F, (n, F)), small_integers(n * 37 + F, (n, F))
+    assert float((x.abs() @ y.abs().t()).max()) < 2.0 ** 24 and float((x.abs() @ x.abs().t()).max()) < 2.0 ** 24
+    for yy in (None, y):
+        got = centre_restatement(x, yy).numpy()
+        ref = dva.cka.gram_matrix(x.double(), None if yy is None else yy.double(), torch.float64).reshape(n, n).float().numpy()
+        assert np.all(np.abs(got.astype(np.float64) - ref.astype(np.float64)) <= np.spacing(np.abs(ref)).astype(np.float64)), (n, F, yy is None)
+        if yy is None:
+            assert np.array_equal(got, got.T)
