@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <vector>
 
 #include "p2vit_kernels.h"
@@ -25,6 +26,12 @@ static int fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
+// a best-effort plan-time step (building tables a forward can do without) must not disturb p2v_last_error(): restored on the way out
+struct KeepLastError {
+  char keep[sizeof g_err];
+  KeepLastError() { memcpy(keep, g_err, sizeof keep); }
+  ~KeepLastError() { memcpy(g_err, keep, sizeof keep); }
+};
 static int launch_rc(int rc, const char* what) {
   if (rc == 0) return 0;
   if (rc == -2) return fail(P2V_E_UNSUPPORTED, "%s: s_qkv_sq * inv_s_attn must be a power of two", what);
@@ -107,6 +114,12 @@ struct p2v_plan {
 
 static void build_resid_tables(p2v_plan* plan, int block);
 static int bit_index(int bits) { return bits == 4 ? 0 : (bits == 8 ? 1 : -1); }
+// LayerNorm i of a block's six: ln1[0 .. 1], then ln2[0 .. 1][0 .. 1]
+template <class Block>
+static auto& block_ln(Block& b, int i) { return i < 2 ? b.ln1[i] : b.ln2[(i - 2) >> 1][(i - 2) & 1]; }
+static bool ln_constants_present(const p2v_ln& l, bool with_mask = true) {
+  return (l.mask || !with_mask) && l.gamma && l.beta && l.inv_out && l.post_mul;
+}
 
 extern "C" {
 
@@ -120,35 +133,42 @@ extern int g_resid_pre;
 extern int g_attn_stream;
 extern int g_ln_pre;
 extern int g_gemm_rows;
-int g_cls_rows = 1;       // P2V_CLS_ROWS=0: the last block of p2v_forward computes every row, as the other blocks do (A/B and parity runs)
-// Tuning / A-B switches read once per process (first plan or first version query).  None of them changes results:
-// P2V_LN_GENERIC forces the generic LayerNorm chain (bit-identical to the fast one, both are tested).
+int g_cls_rows = 1;       // 0: the last block of p2v_forward computes every row, as the other blocks do (A/B and parity runs)
+
+// The tuning / A-B switches: the name p2v_set_tuning knows, the environment variable read once per process (first plan or first version
+// query), and the accepted values lo, lo + step ... hi.  None of them changes results (ln_generic forces the generic LayerNorm chain:
+// bit-identical to the fast one, both are tested).  An on / off switch (0 .. 1) may take ANY integer as "not zero", separately for the two
+// ways in: all of them do through p2v_set_tuning except cls_rows, all of them do from the environment except ln_generic (whose only
+// effective setting there is 1: the variable starts at 0).
+enum { ANY_ENV = 1, ANY_API = 2 };
+static const struct Switch {
+  const char *name, *env;
+  int* var;
+  int lo, hi, step, any;
+  bool takes(int v, int how) const { return (any & how) || (v >= lo && v <= hi && (v - lo) % step == 0); }
+  void set(int v) const { *var = (hi == 1 && lo == 0) ? v != 0 : v; }
+} kSwitches[] = {
+    {"attn_waves", "P2V_ATTN_WAVES", &g_attn_waves, 4, 8, 1, 0},
+    {"ln_gemm", "P2V_LN_GEMM", &g_ln_gemm, 0, 1, 1, ANY_ENV | ANY_API},
+    {"ln_gemm_version", "P2V_LN_GEMM_V", &g_ln_gemm_ver, 1, 3, 1, 0},
+    {"gemm_tile", "P2V_GEMM_TILE", &g_gemm_tile, 0, 256, 128, 0},
+    {"attn_stream", "P2V_ATTN_STREAM", &g_attn_stream, 0, 1, 1, ANY_ENV | ANY_API},
+    {"ln_pre", "P2V_LN_PRE", &g_ln_pre, 0, 1, 1, ANY_ENV | ANY_API},
+    {"resid_pre", "P2V_RESID_PRE", &g_resid_pre, 0, 1, 1, ANY_ENV | ANY_API},
+    {"gemm_rows", "P2V_GEMM_ROWS", &g_gemm_rows, 0, 2, 1, 0},
+    {"cls_rows", "P2V_CLS_ROWS", &g_cls_rows, 0, 1, 1, ANY_ENV},
+    {"ln_rows", "P2V_LN_ROWS", &g_ln_rows, 1, 64, 1, 0},
+    {"ln_generic", "P2V_LN_GENERIC", &g_ln_generic, 0, 1, 1, ANY_API},
+};
+
 static void read_env_once() {
   static bool done = false;
   if (done) return;
   done = true;
-  const char* e = getenv("P2V_ATTN_WAVES");
-  if (e && atoi(e) >= 4 && atoi(e) <= 8) g_attn_waves = atoi(e);
-  e = getenv("P2V_LN_GEMM");
-  if (e) g_ln_gemm = atoi(e) != 0;
-  e = getenv("P2V_LN_GEMM_V");
-  if (e && atoi(e) >= 1 && atoi(e) <= 3) g_ln_gemm_ver = atoi(e);
-  e = getenv("P2V_GEMM_TILE");
-  if (e && (atoi(e) == 0 || atoi(e) == 128 || atoi(e) == 256)) g_gemm_tile = atoi(e);
-  e = getenv("P2V_ATTN_STREAM");
-  if (e) g_attn_stream = atoi(e) != 0;
-  e = getenv("P2V_LN_PRE");
-  if (e) g_ln_pre = atoi(e) != 0;
-  e = getenv("P2V_RESID_PRE");
-  if (e) g_resid_pre = atoi(e) != 0;
-  e = getenv("P2V_GEMM_ROWS");
-  if (e && atoi(e) >= 0 && atoi(e) <= 2) g_gemm_rows = atoi(e);
-  e = getenv("P2V_CLS_ROWS");
-  if (e) g_cls_rows = atoi(e) != 0;
-  e = getenv("P2V_LN_ROWS");
-  if (e && atoi(e) >= 1 && atoi(e) <= 64) g_ln_rows = atoi(e);
-  e = getenv("P2V_LN_GENERIC");
-  if (e && atoi(e) == 1) g_ln_generic = 1;
+  for (const Switch& s : kSwitches) {
+    const char* e = getenv(s.env);
+    if (e && s.takes(atoi(e), ANY_ENV)) s.set(atoi(e));          // a value out of range is ignored
+  }
 }
 int p2v_abi_version(void) { read_env_once(); return P2V_ABI_VERSION; }
 
@@ -158,17 +178,11 @@ int p2v_max_tokens(int head_dim) { return p2v_resident_tokens_of(head_dim) ? P2V
 int p2v_set_tuning(const char* name, int value) {
   if (!name) return fail(P2V_E_ARG, "p2v_set_tuning: null name");
   read_env_once();                      // an explicit setting wins over the environment
-  if (!strcmp(name, "ln_gemm")) { g_ln_gemm = value != 0; return P2V_OK; }
-  if (!strcmp(name, "ln_gemm_version") && value >= 1 && value <= 3) { g_ln_gemm_ver = value; return P2V_OK; }
-  if (!strcmp(name, "ln_generic")) { g_ln_generic = value != 0; return P2V_OK; }
-  if (!strcmp(name, "ln_rows") && value >= 1 && value <= 64) { g_ln_rows = value; return P2V_OK; }
-  if (!strcmp(name, "attn_waves") && value >= 4 && value <= 8) { g_attn_waves = value; return P2V_OK; }
-  if (!strcmp(name, "resid_pre")) { g_resid_pre = value != 0; return P2V_OK; }
-  if (!strcmp(name, "ln_pre")) { g_ln_pre = value != 0; return P2V_OK; }
-  if (!strcmp(name, "attn_stream")) { g_attn_stream = value != 0; return P2V_OK; }
-  if (!strcmp(name, "gemm_tile") && (value == 0 || value == 128 || value == 256)) { g_gemm_tile = value; return P2V_OK; }
-  if (!strcmp(name, "gemm_rows") && value >= 0 && value <= 2) { g_gemm_rows = value; return P2V_OK; }
-  if (!strcmp(name, "cls_rows") && (value == 0 || value == 1)) { g_cls_rows = value; return P2V_OK; }
+  for (const Switch& s : kSwitches)
+    if (!strcmp(name, s.name) && s.takes(value, ANY_API)) {
+      s.set(value);
+      return P2V_OK;
+    }
   return fail(P2V_E_ARG, "p2v_set_tuning: unknown switch or value out of range: %s = %d", name, value);
 }
 const char* p2v_last_error(void) { return g_err; }
@@ -230,12 +244,7 @@ int p2v_plan_set_linear(p2v_plan* plan, int layer, int bits, const p2v_linear* l
   plan->lin_set[bi][layer] = 1;
   if (layer >= 1 && layer < plan->n_layers - 1 && ((layer - 1) & 1)) {         // proj / fc2 of block (layer - 1) / 4: their RESID tables depend on these constants
     const int block = (layer - 1) / 4;
-    if (plan->block_set[block]) {
-      char keep[sizeof g_err];
-      memcpy(keep, g_err, sizeof keep);
-      build_resid_tables(plan, block);        // unusable tables simply leave the generic RESID epilogue in place
-      memcpy(g_err, keep, sizeof keep);
-    }
+    if (plan->block_set[block]) build_resid_tables(plan, block);
   }
   return P2V_OK;
 }
@@ -293,7 +302,9 @@ static int resid_prefold_impl(const p2v_linear& lin, const p2v_epilogue& ep, int
 }
 
 // (Re)build the RESID tables of a block for every bit width whose weights are set; called from both setters, whichever comes last.
+// Best effort: unusable tables simply leave the generic RESID epilogue in place.
 static void build_resid_tables(p2v_plan* plan, int block) {
+  KeepLastError keep;
   for (int j = 0; j < 4; ++j) plan->resid_tab[(size_t)block * 4 + j] = nullptr;
   if (!plan->block_set[block]) return;
   const p2v_block& blk = plan->blocks[block];
@@ -359,9 +370,8 @@ static const p2v_ln_pre kNoPre = {nullptr, nullptr, 0.f, 0.f, 0.f, 0, 0};
 static bool fold_ln_constants(p2v_plan* plan, int block) {
   const int C = plan->d.embed_dim, Cp = round_up(C, 256);
   p2v_block& blk = plan->blocks[block];
-  auto ln_at = [&](int i) -> p2v_ln& { return i < 2 ? blk.ln1[i] : blk.ln2[(i - 2) >> 1][(i - 2) & 1]; };
   // stale state first: a second p2v_plan_set_block on this block must never leave the constants of the previous arrays behind
-  for (int i = 0; i < 6; ++i) ln_at(i).pre = kNoPre;
+  for (int i = 0; i < 6; ++i) block_ln(blk, i).pre = kNoPre;
   OwnerDevice own(blk.ln1[0].gamma);
   if (!own.ok()) {
     fail(P2V_OK, "p2v_plan_set_block: LayerNorm constants of block %d not folded at plan time (cannot locate the device of gamma)", block);
@@ -378,14 +388,14 @@ static bool fold_ln_constants(p2v_plan* plan, int block) {
   if (e == hipSuccess) {
     plan->ln_pre_buf[block] = dev;
     plan->device = own.own;
-    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = fold_one_ln(ln_at(i), C, dev + (size_t)(2 * i) * Cp, &pre[i]);
+    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = fold_one_ln(block_ln(blk, i), C, dev + (size_t)(2 * i) * Cp, &pre[i]);
   }
   if (e != hipSuccess) {
     (void)hipGetLastError();                                    // do not leave the error for an unrelated CHECK_LAUNCH
     fail(P2V_OK, "p2v_plan_set_block: LayerNorm constants of block %d not folded at plan time (%s)", block, hipGetErrorString(e));
     return false;
   }
-  for (int i = 0; i < 6; ++i) ln_at(i).pre = pre[i];
+  for (int i = 0; i < 6; ++i) block_ln(blk, i).pre = pre[i];
   return true;
 }
 
@@ -401,10 +411,8 @@ int p2v_plan_set_block(p2v_plan* plan, int block, const p2v_block* blk) {
   if (rc == P2V_OK && (!blk->proj_epi.s_mid || !blk->proj_epi.s_res || !blk->proj_epi.s_next || !blk->fc2_epi.s_mid || !blk->fc2_epi.s_res ||
                        !blk->fc2_epi.s_next))
     rc = fail(P2V_E_ARG, "p2v_plan_set_block: RESID epilogues need s_mid/s_res/s_next");
-  for (int i = 0; i < 6 && rc == P2V_OK; ++i) {
-    const p2v_ln& l = i < 2 ? blk->ln1[i] : blk->ln2[(i - 2) >> 1][(i - 2) & 1];
-    if (!l.mask || !l.gamma || !l.beta || !l.inv_out || !l.post_mul) rc = fail(P2V_E_ARG, "p2v_plan_set_block: LayerNorm constants missing");
-  }
+  for (int i = 0; i < 6 && rc == P2V_OK; ++i)
+    if (!ln_constants_present(block_ln(*blk, i))) rc = fail(P2V_E_ARG, "p2v_plan_set_block: LayerNorm constants missing");
   if (rc != P2V_OK) return rc;
   plan->blocks[block] = *blk;
   plan->block_set[block] = 1;
@@ -412,12 +420,7 @@ int p2v_plan_set_block(p2v_plan* plan, int block, const p2v_block* blk) {
   // is left in p2v_last_error() and p2v_plan_block_prefolded() tells
   g_err[0] = 0;
   plan->block_folded[block] = fold_ln_constants(plan, block) ? 1 : 0;
-  {
-    char keep[sizeof g_err];
-    memcpy(keep, g_err, sizeof keep);
-    build_resid_tables(plan, block);        // unusable tables simply leave the generic RESID epilogue in place
-    memcpy(g_err, keep, sizeof keep);
-  }
+  build_resid_tables(plan, block);
   return P2V_OK;
 }
 
@@ -435,7 +438,7 @@ int p2v_plan_resid_prefolded(const p2v_plan* plan, int block) {
 
 int p2v_plan_set_head(p2v_plan* plan, const p2v_ln* final_ln, float inv_s_out, float s_out) {
   if (!plan || !final_ln) return fail(P2V_E_ARG, "p2v_plan_set_head: null argument");
-  if (!final_ln->mask || !final_ln->gamma || !final_ln->beta || !final_ln->inv_out || !final_ln->post_mul)
+  if (!ln_constants_present(*final_ln))
     return fail(P2V_E_ARG, "p2v_plan_set_head: LayerNorm constants missing");
   if (!(inv_s_out > 0.f) || !(s_out > 0.f)) return fail(P2V_E_ARG, "p2v_plan_set_head: act_out scale must be positive");
   plan->final_ln = *final_ln;
@@ -486,51 +489,41 @@ size_t p2v_workspace_bytes(const p2v_plan* plan, int batch) {
 
 long long p2v_workspace_view(const p2v_plan* plan, int batch, const char* name) {
   if (!plan || !name || batch <= 0) return -1;
-  WsLayout w = ws_layout(plan, batch);
-  if (!strcmp(name, "patches")) return (long long)w.patches;
-  if (!strcmp(name, "x")) return (long long)w.x;
-  if (!strcmp(name, "ln")) return (long long)w.ln;
-  if (!strcmp(name, "qkv")) return (long long)w.qkv;
-  if (!strcmp(name, "att")) return (long long)w.att;
-  if (!strcmp(name, "hid")) return (long long)w.hid;
-  if (!strcmp(name, "cls")) return (long long)w.cls;
+  const WsLayout w = ws_layout(plan, batch);
+  const struct { const char* name; size_t off; } views[] = {{"patches", w.patches}, {"x", w.x}, {"ln", w.ln}, {"qkv", w.qkv}, {"att", w.att}, {"hid", w.hid}, {"cls", w.cls}};
+  for (const auto& v : views)
+    if (!strcmp(name, v.name)) return (long long)v.off;
   return -1;
 }
 
-static int run_gemm(int epi, const int8_t* A, int lda, int M, int K, int N, const p2v_linear& lin, const p2v_epilogue& ep, void* out,
-                    int ldo, int8_t* out_codes, hipStream_t st) {
+}  // extern "C"
+
+// ---- the whole-model forward ------------------------------------------------------------------------------------------------------------
+// The one place a GemmArgs is filled.  W: the layer's weights in the layout the kernel reads (lin.w_codes, or lin.w_frag for the fused
+// LayerNorm+GEMM kernels); K in whole k-tiles
+static GemmArgs gemm_args(const int8_t* A, int lda, int M, const int8_t* W, int K, int N, const p2v_linear& lin, const p2v_epilogue& ep,
+                          void* out, int ldo, int8_t* out_codes) {
   GemmArgs g;
-  g.A = A; g.lda = lda; g.M = M; g.W = lin.w_codes; g.K = K; g.N = N; g.w4 = lin.packed4 ? 1 : 0;
+  g.A = A; g.lda = lda; g.M = M; g.W = W; g.K = K; g.N = N; g.w4 = lin.packed4 ? 1 : 0;
   g.colscale = lin.colscale; g.bias = lin.bias; g.ep = ep; g.out = out; g.ldo = ldo; g.out_codes = out_codes; g.tiles_n = 0;
 #ifdef P2V_DIAG
   g.stamps = nullptr;
 #endif
-  return launch_rc(p2v_launch_gemm(epi, g, st), "gemm_i8");
+  return g;
 }
 
-// a layer GEMM over the few class-token rows: the row kernel unless the switches name the tiled one (gemm_rows = 2, or an explicit gemm_tile)
-static int run_gemm_few_rows(int epi, const int8_t* A, int lda, int M, int K, int N, const p2v_linear& lin, const p2v_epilogue& ep, void* out,
-                             int ldo, hipStream_t st) {
-  if (g_gemm_rows == 2 || g_gemm_tile != 0) return run_gemm(epi, A, lda, M, K, N, lin, ep, out, ldo, nullptr, st);
-  GemmArgs g;
-  g.A = A; g.lda = lda; g.M = M; g.W = lin.w_codes; g.K = K; g.N = N; g.w4 = lin.packed4 ? 1 : 0;
-  g.colscale = lin.colscale; g.bias = lin.bias; g.ep = ep; g.out = out; g.ldo = ldo; g.out_codes = nullptr; g.tiles_n = 0;
-#ifdef P2V_DIAG
-  g.stamps = nullptr;
-#endif
-  return launch_rc(p2v_launch_gemm_rows(epi, g, st), "gemm_rows");
+// few_rows: a layer GEMM over the few class-token rows - the row kernel unless the switches name the tiled one (gemm_rows = 2, or an explicit gemm_tile)
+static int run_gemm(int epi, const int8_t* A, int lda, int M, int K, int N, const p2v_linear& lin, const p2v_epilogue& ep, void* out,
+                    int ldo, int8_t* out_codes, hipStream_t st, bool few_rows = false) {
+  const GemmArgs g = gemm_args(A, lda, M, lin.w_codes, K, N, lin, ep, out, ldo, out_codes);
+  if (few_rows && g_gemm_rows != 2 && g_gemm_tile == 0) return launch_rc(p2v_launch_gemm_rows(epi, g, st), "gemm_rows");
+  return launch_rc(p2v_launch_gemm(epi, g, st), "gemm_i8");
 }
 
 // QIntLayerNorm -> /cs -> qact0 -> QLinear -> (GELU) -> QAct in one launch (k_ln_gemm); a.out may be null
 static int run_ln_gemm(int epi, const LnArgs& a, const p2v_linear& lin, const p2v_epilogue& ep, int N, int8_t* out, hipStream_t st) {
-  GemmArgs g;
   if (!lin.w_frag) return fail(P2V_E_UNSUPPORTED, "ln_gemm: the layer has no fragment-order weights (p2v_linear.w_frag)");
-  g.A = nullptr; g.lda = a.C; g.M = (int)a.rows; g.W = lin.w_frag; g.K = round_up(a.C, GBK_PAD); g.N = N; g.w4 = lin.packed4 ? 1 : 0;
-  g.colscale = lin.colscale; g.bias = lin.bias; g.ep = ep; g.out = out; g.ldo = N; g.out_codes = nullptr; g.tiles_n = 0;
-#ifdef P2V_DIAG
-  g.stamps = nullptr;
-#endif
-  const int rc = p2v_launch_ln_gemm(epi, a, g, st);
+  const int rc = p2v_launch_ln_gemm(epi, a, gemm_args(nullptr, a.C, (int)a.rows, lin.w_frag, round_up(a.C, GBK_PAD), N, lin, ep, out, N, nullptr), st);
   if (rc == -3) return fail(P2V_E_UNSUPPORTED, "ln_gemm: shape C=%d N=%d is not fused", a.C, N);
   return launch_rc(rc, "ln_gemm");
 }
@@ -542,6 +535,7 @@ struct Prof {
   int used = 0;
   bool make_pool(int n) {
     ev.resize(n);
+    kind.reserve(n);
     for (int i = 0; i < n; ++i)
       if (hipEventCreate(&ev[i]) != hipSuccess) { ev.resize(i); return false; }
     return true;
@@ -562,13 +556,7 @@ struct DdvCtx {
 };
 static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st) {
   const size_t esz = dtype == P2V_COS_I8 ? 1 : 4;
-  p2v_cos_layer l;
-  l.a = base;
-  l.b = reinterpret_cast<const char*>(base) + (size_t)c->n * rows * cols * esz;
-  l.scale = scale;
-  l.sample_stride = (long long)rows * cols;
-  l.row_stride = cols;
-  l.rows = rows; l.cols = cols; l.dtype = dtype;
+  const p2v_cos_layer l{base, reinterpret_cast<const char*>(base) + (size_t)c->n * rows * cols * esz, scale, (long long)rows * cols, cols, rows, cols, dtype};
   const CosDesc d = p2v_cos_desc(l, c->n, 0);        // (logits / head rows of a class count that is no multiple of 4: d.vec = 0, scalar loads)
   if ((long long)c->n * d.nsplit > c->slots)
     return fail(P2V_E_WORKSPACE, "p2v_forward_ddv: a stage of %d x %d needs %lld partials, the workspace holds %lld", rows, cols,
@@ -578,12 +566,132 @@ static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype
   return rc;
 }
 
-static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
-                        size_t workspace_bytes, int stop_after, void* stream, Prof* prof, float* const* qkv_tap = nullptr,
-                        float* const* fc1_tap = nullptr, float* const* lin_tap = nullptr, const uint8_t* u8 = nullptr, int layout = 0,
-                        const void* lut = nullptr, DdvCtx* ddv = nullptr) {
-  // u8 != nullptr: p2v_forward_u8 (images == nullptr; the input stage reads the uint8 images through `lut`, the rest is shared)
-  if (!p || !(images || u8) || !bit_config || !logits || !workspace) return fail(P2V_E_ARG, "p2v_forward: null argument");
+// What distinguishes the whole-model entry points: each extern "C" wrapper fills its own fields and leaves the rest
+struct FwdOpts {
+  const float* images = nullptr;      // fp32 images, or
+  const uint8_t* u8 = nullptr;        // p2v_forward_u8: uint8 images in `layout`, which the input stage reads through `lut` (the rest is shared)
+  int layout = 0;
+  const void* lut = nullptr;
+  int stop_after = -1;                // >= 0: end once that many slots of the launch numbering are filled (parity runs read the workspace)
+  Prof* prof = nullptr;               // p2v_forward_profile / _begin: an event before every launch
+  float *const *qkv_tap = nullptr, *const *fc1_tap = nullptr;      // p2v_forward_taps: fp32 qkv / fc1 outputs [block]
+  float* const* lin_tap = nullptr;    // p2v_forward_linear_taps: fp32 output of linear layer [layer]
+  DdvCtx* ddv = nullptr;              // p2v_forward_ddv
+};
+
+// The rows a block's launches behind the qkv GEMM run on.  ln and hid hold them compact from their start (strides D and hidden) either way.
+struct RowSet {
+  int rows;             // of proj, norm2, fc1 and fc2
+  long long stride;     // between those rows in x and att
+  int nq;               // query rows per image the attention computes (0 = all)
+  bool few;             // run_gemm's few_rows, and norm2 as a launch of its own (the fused kernel is tiled over many rows)
+};
+
+// One forward in flight: what every launch needs, and the bookkeeping between launches (stop_after, profile events, taps, DDV stages)
+struct Fwd {
+  const p2v_plan* p;
+  const FwdOpts& o;
+  hipStream_t st;
+  int batch, D, T, M, Hd, hd, Dk, Hk;                       // Dk, Hk: contraction depths in whole k-tiles (weights are zero-padded to them)
+  int8_t *P, *X, *LN, *QKV, *ATT, *HID, *CLS;               // the workspace buffers (ws_layout)
+  int launched = 0;                                         // slots of the stop_after numbering filled so far
+  bool done = false;                                        // stop_after reached: a normal early end - every member is a no-op from then on
+
+  Fwd(const p2v_plan* plan, const FwdOpts& opts, int batch_, const WsLayout& w, void* workspace, hipStream_t stream)
+      : p(plan), o(opts), st(stream), batch(batch_) {
+    int8_t* ws = reinterpret_cast<int8_t*>(workspace);
+    P = ws + w.patches; X = ws + w.x; LN = ws + w.ln; QKV = ws + w.qkv; ATT = ws + w.att; HID = ws + w.hid; CLS = ws + w.cls;
+    D = p->d.embed_dim; T = p->tokens; M = batch * T; Hd = p->d.mlp_hidden; hd = D / p->d.num_heads; Dk = round_up(D, GBK_PAD); Hk = round_up(Hd, GBK_PAD);
+  }
+
+  // One launch of kind P2V_K_*: the stop_after cut, the profile's event and kind, the launch itself, its slots
+  template <class Launch>
+  int step(int kind, Launch&& launch) {
+    done = done || (o.stop_after >= 0 && launched >= o.stop_after);
+    if (done) return P2V_OK;
+    if (Prof* prof = o.prof) {
+      if (prof->used + 1 >= (int)prof->ev.size()) return fail(P2V_E_LAUNCH, "profile: event pool exhausted");
+      hipEventRecord(prof->ev[prof->used++], st);
+      prof->kind.push_back(kind);
+    }
+    const int rc = launch();
+    if (rc == P2V_OK) launched += (kind == P2V_K_LN_GEMM_QKV || kind == P2V_K_LN_GEMM_FC1) ? 2 : 1;   // a fused launch fills two slots
+    return rc;
+  }
+  // layer-output tap of p2v_forward_linear_taps: a P2V_EPI_F32 GEMM over the layer's int8 input, still in the workspace right after the
+  // layer's own launch (not counted by stop_after: the entry point that passes lin_tap runs everything)
+  int lin_tap(int layer, const int8_t* A, int lda, int rows, int K, int N, const p2v_linear& lin) {
+    if (done || !o.lin_tap || !o.lin_tap[layer]) return P2V_OK;
+    return run_gemm(P2V_EPI_F32, A, lda, rows, K, N, lin, p2v_epilogue{}, o.lin_tap[layer], N, nullptr, st);
+  }
+  // DDV stages (p2v_forward_ddv): the int8 codes a launch has just completed, fp32 values, and the fp32 tap that sits in the one tap buffer
+  int ddv_i8(const void* buf, int rows, int cols, const float* scale) { return (done || !o.ddv) ? P2V_OK : ddv_reduce(o.ddv, buf, rows, cols, P2V_COS_I8, scale, st); }
+  int ddv_f32(const void* buf, int rows, int cols) { return (done || !o.ddv) ? P2V_OK : ddv_reduce(o.ddv, buf, rows, cols, P2V_COS_F32, nullptr, st); }
+  int ddv_tap(int rows, int cols) { return (o.ddv && o.ddv->tap) ? ddv_f32(o.ddv->tap, rows, cols) : P2V_OK; }
+  int layernorm(const LnArgs& a) { return step(P2V_K_LAYERNORM, [&] { return launch_rc(p2v_launch_layernorm(a, st), "int_layernorm"); }); }
+  int gemm(int kind, bool few, int epi, const int8_t* A, int lda, int rows, int K, int N, const p2v_linear& lin, const p2v_epilogue& ep, void* out, int ldo) {
+    return step(kind, [&] { return run_gemm(epi, A, lda, rows, K, N, lin, ep, out, ldo, nullptr, st, few); });
+  }
+  // QIntLayerNorm of `rows` rows of x -> QLinear -> `out`: one fused launch where the kernel covers the shape and the layer has fragment-order
+  // weights (the LayerNorm codes then stay in LDS; parity runs read the workspace, so for them the kernel writes them too), else the
+  // LayerNorm into LN and the GEMM from there
+  int ln_linear(int k_fused, int k_gemm, int epi, long long stride, int rows, const p2v_ln& norm, const p2v_linear& lin, const p2v_epilogue& e, int N,
+                int8_t* out, bool few) {
+    LnArgs ln{X, stride, rows, D, norm, LN, D};
+    ln.pre = norm.pre;
+    if (!few && lin.w_frag && p2v_ln_gemm_supported(epi, D, N, e.gelu.table ? e.gelu.cells : 0)) {
+      if (o.stop_after < 0) ln.out = nullptr;
+      return step(k_fused, [&] { return run_ln_gemm(epi, ln, lin, e, N, out, st); });
+    }
+    const int rc = layernorm(ln);
+    return rc ? rc : gemm(k_gemm, few, epi, LN, D, rows, Dk, N, lin, e, out, N);
+  }
+
+  // Block i on the rows `rs` names; bc: its four bit widths (qkv, proj, fc1, fc2).  The taps and DDV stages name whole [T][..] samples: the
+  // entry points that ask for them run every block on all rows.
+  int block(int i, const int8_t* bc, const RowSet& rs) {
+    const p2v_block& b = p->blocks[i];
+    const int bq = bit_index(bc[0]), bp = bit_index(bc[1]), b1 = bit_index(bc[2]), b2 = bit_index(bc[3]);
+    const p2v_linear &qkv = p->lin[bq][1 + 4 * i], &proj = p->lin[bp][2 + 4 * i], &fc1 = p->lin[b1][3 + 4 * i], &fc2 = p->lin[b2][4 + 4 * i];
+    const int ldx = (int)rs.stride;
+    int rc;
+    // norm1 -> /channel_scale -> qact0 -> qkv -> qact1, every row (the keys and values)       vit_fquant.py:431-434,284-293,307
+    p2v_epilogue eq{};
+    eq.inv_s_out = b.inv_s_qkv[bq];
+    eq.tap_out = o.qkv_tap ? o.qkv_tap[i] : (o.lin_tap ? o.lin_tap[1 + 4 * i] : nullptr);
+    if ((rc = ln_linear(P2V_K_LN_GEMM_QKV, P2V_K_GEMM_QKV, P2V_EPI_REQUANT, D, M, b.ln1[bq], qkv, eq, 3 * D, QKV, false))) return rc;
+    if ((rc = ddv_tap(T, 3 * D)) || (rc = ddv_i8(QKV, T, 3 * D, nullptr))) return rc;                           // attn.qkv, attn.qact1
+    // scores -> qact_attn1 -> log-int-softmax -> @v -> qact2                  vit_fquant.py:309-326
+    AttnArgs at{QKV, batch, T, p->d.num_heads, b.attn, ATT, nullptr};
+    at.nq = rs.nq;
+    if ((rc = step(P2V_K_ATTENTION, [&] { return launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"); }))) return rc;
+    if ((rc = ddv_i8(ATT, T, D, nullptr))) return rc;                                                            // attn.qact2
+    // proj -> qact3 -> + x -> Block.qact2, in place on x                      vit_fquant.py:334-338,431
+    p2v_epilogue ep = b.proj_epi;
+    ep.residual = X;
+    ep.resid_tab = p->resid_tab[(size_t)i * 4 + bp];
+    if ((rc = gemm(P2V_K_GEMM_PROJ, rs.few, P2V_EPI_RESID, ATT, ldx, rs.rows, Dk, D, proj, ep, X, ldx))) return rc;
+    if ((rc = lin_tap(2 + 4 * i, ATT, ldx, rs.rows, Dk, D, proj)) || (rc = ddv_tap(T, D)) || (rc = ddv_i8(X, T, D, b.proj_epi.s_next))) return rc;   // attn.proj, Block.qact2
+    // norm2 (attention's channel scale!) -> /mlp.channel_scale -> mlp.qact0 -> fc1 -> GELU -> qact1     vit_fquant.py:464, layers_quant.py:305-316,331-333
+    p2v_epilogue e1{};
+    e1.inv_s_out = b.inv_s_fc1;
+    e1.gelu = b.gelu_fc1;
+    e1.tap_out = o.fc1_tap ? o.fc1_tap[i] : (o.lin_tap ? o.lin_tap[3 + 4 * i] : nullptr);
+    if ((rc = ln_linear(P2V_K_LN_GEMM_FC1, P2V_K_GEMM_FC1, P2V_EPI_GELU, rs.stride, rs.rows, b.ln2[bq][b1], fc1, e1, Hd, HID, rs.few))) return rc;
+    if ((rc = ddv_tap(T, Hd)) || (rc = ddv_i8(HID, T, Hd, nullptr))) return rc;                                 // mlp.fc1, mlp.qact1
+    // fc2 -> qact2 -> + x -> Block.qact4, in place on x                       layers_quant.py:342-346, vit_fquant.py:468
+    p2v_epilogue e2 = b.fc2_epi;
+    e2.residual = X;
+    e2.resid_tab = p->resid_tab[(size_t)i * 4 + 2 + b2];
+    if ((rc = gemm(P2V_K_GEMM_FC2, rs.few, P2V_EPI_RESID, HID, Hd, rs.rows, Hk, D, fc2, e2, X, ldx))) return rc;
+    if ((rc = lin_tap(4 + 4 * i, HID, Hd, rs.rows, Hk, D, fc2)) || (rc = ddv_tap(T, D))) return rc;             // mlp.fc2
+    return ddv_i8(X, T, D, b.fc2_epi.s_next);                                                                    // Block.qact4
+  }
+};
+
+static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace, size_t workspace_bytes,
+                        void* stream, const FwdOpts& o) {
+  if (!p || !(o.images || o.u8) || !bit_config || !logits || !workspace) return fail(P2V_E_ARG, "p2v_forward: null argument");
   if (batch <= 0) return fail(P2V_E_SHAPE, "batch must be positive");
   if (n_cfg != p->n_layers) return fail(P2V_E_BITS, "bit_config has %d entries, model needs %d", n_cfg, p->n_layers);
   for (int i = 0; i < n_cfg; ++i) {
@@ -596,179 +704,62 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
     if (!p->block_set[i]) return fail(P2V_E_STATE, "plan incomplete (block %d)", i);
   const WsLayout w = ws_layout(p, batch);
   if (workspace_bytes < w.total) return fail(P2V_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, w.total);
-  if (lin_tap && lin_tap[0] && !(p->inv_s_input > 0.f))
+  if (o.lin_tap && o.lin_tap[0] && !(p->inv_s_input > 0.f))
     return fail(P2V_E_UNSUPPORTED, "p2v_forward_linear_taps: no patch-embed tap for input_quant = False (the fp32-image convolution); pass NULL for taps[0]");
-  hipStream_t st = (hipStream_t)stream;
-  int8_t* ws = reinterpret_cast<int8_t*>(workspace);
-  int8_t *bufP = ws + w.patches, *bufX = ws + w.x, *bufLN = ws + w.ln, *bufQKV = ws + w.qkv, *bufATT = ws + w.att,
-         *bufHID = ws + w.hid, *bufCLS = ws + w.cls;
   const p2v_model_desc& d = p->d;
-  const int D = d.embed_dim, T = p->tokens, M = batch * T, Hd = d.mlp_hidden, hd = D / d.num_heads;
-  const int Dk = round_up(D, GBK_PAD), Hk = round_up(Hd, GBK_PAD);     // contraction depths in whole k-tiles (weights are zero-padded to them)
-  int launched = 0, rc;
-  const bool taps = stop_after >= 0;      // parity runs read the workspace buffers: the fused kernels then also write the LayerNorm codes
-  // the last block on the class-token rows only: when nothing but the logits is asked for, and T * D fits the int strides of a GEMM
-  const bool cls_only = g_cls_rows && stop_after < 0 && !qkv_tap && !fc1_tap && !lin_tap && !ddv && (long long)T * D <= 0x7fffffffLL;
-#define STEP(kind_, call)                             \
-  do {                                                \
-    if (stop_after >= 0 && launched >= stop_after) return P2V_OK; \
-    if (prof) {                                       \
-      if (prof->used + 1 >= (int)prof->ev.size()) return fail(P2V_E_LAUNCH, "profile: event pool exhausted"); \
-      hipEventRecord(prof->ev[prof->used++], st);     \
-      prof->kind.push_back(kind_);                    \
-    }                                                 \
-    rc = (call);                                      \
-    if (rc) return rc;                                \
-    launched += (kind_ == P2V_K_LN_GEMM_QKV || kind_ == P2V_K_LN_GEMM_FC1) ? 2 : 1;   /* a fused launch fills two slots of the stop_after numbering */ \
-  } while (0)
-  // layer-output tap of p2v_forward_linear_taps: a P2V_EPI_F32 GEMM over the layer's int8 input, still in the workspace right after the
-  // layer's own launch (not counted by stop_after: the entry point that passes lin_tap runs everything)
-#define LIN_TAP(idx, A, lda, M_, K_, N_, lin)                                                                              \
-  do {                                                                                                                    \
-    if (lin_tap && lin_tap[idx]) {                                                                                        \
-      rc = run_gemm(P2V_EPI_F32, A, lda, M_, K_, N_, lin, p2v_epilogue{}, lin_tap[idx], N_, nullptr, st);                 \
-      if (rc) return rc;                                                                                                  \
-    }                                                                                                                     \
-  } while (0)
-
-  // DDV stages (p2v_forward_ddv): the int8 codes a launch has just completed, and the fp32 tap that sits in the one tap buffer
-#define DDV_I8(buf, rows_, cols_, scale_)                                                \
-  do {                                                                                   \
-    if (ddv && (rc = ddv_reduce(ddv, buf, rows_, cols_, P2V_COS_I8, scale_, st))) return rc; \
-  } while (0)
-#define DDV_TAP(rows_, cols_)                                                            \
-  do {                                                                                   \
-    if (ddv && ddv->tap && (rc = ddv_reduce(ddv, ddv->tap, rows_, cols_, P2V_COS_F32, nullptr, st))) return rc; \
-  } while (0)
+  Fwd f(p, o, batch, w, workspace, (hipStream_t)stream);
+  const hipStream_t st = f.st;
+  const int D = f.D, T = f.T, Kp = p->k_patch_pad, rows_p = batch * p->patches;
+  int rc;
 
   // qact_input + PatchEmbed + cls/pos/qact1                                 vit_fquant.py:705-733
+  const p2v_linear& embed = p->lin[bit_index(bit_config[0])][0];
   if (p->inv_s_input > 0.f) {
-    if (u8)
-      STEP(P2V_K_PATCHIFY, launch_rc(p2v_launch_u8_patchify(u8, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, layout,
-                                                            (const int8_t*)lut, bufP, p->k_patch_pad, st), "u8_patchify"));
-    else
-      STEP(P2V_K_PATCHIFY, launch_rc(p2v_launch_patchify(images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, p->inv_s_input, bufP,
-                                         p->k_patch_pad, st), "quantize_patchify"));
-    const p2v_linear& l = p->lin[bit_index(bit_config[0])][0];
-    STEP(P2V_K_GEMM_EMBED, run_gemm(P2V_EPI_EMBED, bufP, p->k_patch_pad, batch * p->patches, p->k_patch_pad, D, l, p->embed_epi, bufX, D, nullptr, st));
-    LIN_TAP(0, bufP, p->k_patch_pad, batch * p->patches, p->k_patch_pad, D, l);
+    rc = f.step(P2V_K_PATCHIFY, [&] {
+      return o.u8 ? launch_rc(p2v_launch_u8_patchify(o.u8, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, o.layout, (const int8_t*)o.lut, f.P, Kp, st), "u8_patchify")
+                  : launch_rc(p2v_launch_patchify(o.images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, p->inv_s_input, f.P, Kp, st), "quantize_patchify");
+    });
+    if (rc || (rc = f.gemm(P2V_K_GEMM_EMBED, false, P2V_EPI_EMBED, f.P, Kp, rows_p, Kp, D, embed, p->embed_epi, f.X, D)) ||
+        (rc = f.lin_tap(0, f.P, Kp, rows_p, Kp, D, embed)))
+      return rc;
   } else {
     // input_quant = False (vit_fquant.py:705, the vit_large factory :925): the fp32 image feeds the fake-quantised convolution
-    const p2v_linear& l = p->lin[bit_index(bit_config[0])][0];
-    if (l.packed4) return fail(P2V_E_UNSUPPORTED, "input_quant = False: the patch-embed weights must be unpacked codes (packed4 = 0)");
-    GemmArgs g;
-    g.A = nullptr; g.lda = 0; g.M = batch * p->patches; g.W = l.w_codes; g.K = p->k_patch_pad; g.N = D; g.w4 = 0;
-    g.colscale = l.colscale; g.bias = l.bias; g.ep = p->embed_epi; g.out = bufX; g.ldo = D; g.out_codes = nullptr; g.tiles_n = 0;
-#ifdef P2V_DIAG
-    g.stamps = nullptr;
-#endif
-    if (u8)
-      STEP(P2V_K_GEMM_EMBED, launch_rc(p2v_launch_embed_u8(u8, layout, (const float*)lut, batch, d.in_chans, d.img_size, d.img_size, d.patch_size,
-                                                           g, st), "embed_u8"));
-    else
-      STEP(P2V_K_GEMM_EMBED, launch_rc(p2v_launch_embed_fp32(images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, g, st), "embed_fp32"));
+    if (embed.packed4) return fail(P2V_E_UNSUPPORTED, "input_quant = False: the patch-embed weights must be unpacked codes (packed4 = 0)");
+    const GemmArgs g = gemm_args(nullptr, 0, rows_p, embed.w_codes, Kp, D, embed, p->embed_epi, f.X, D, nullptr);
+    rc = f.step(P2V_K_GEMM_EMBED, [&] {
+      return o.u8 ? launch_rc(p2v_launch_embed_u8(o.u8, o.layout, (const float*)o.lut, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, g, st), "embed_u8")
+                  : launch_rc(p2v_launch_embed_fp32(o.images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, g, st), "embed_fp32");
+    });
+    if (rc) return rc;
   }
-  STEP(P2V_K_FILL_CLS, launch_rc(p2v_launch_fill_cls(bufX, batch, T, D, p->cls_codes, st), "fill_cls"));
-  DDV_I8(bufX, T, D, p->embed_epi.s_next);                                   // qact1
+  if ((rc = f.step(P2V_K_FILL_CLS, [&] { return launch_rc(p2v_launch_fill_cls(f.X, batch, T, D, p->cls_codes, st), "fill_cls"); })) ||
+      (rc = f.ddv_i8(f.X, T, D, p->embed_epi.s_next)))                                                           // qact1
+    return rc;
 
-  for (int i = 0; i < d.depth; ++i) {
-    const p2v_block& b = p->blocks[i];
-    const int8_t* bc = bit_config + 1 + 4 * i;
-    const int bq = bit_index(bc[0]), bp = bit_index(bc[1]), b1 = bit_index(bc[2]), b2 = bit_index(bc[3]);
-    // norm1 -> /channel_scale -> qact0                                     vit_fquant.py:431-434,284-289
-    LnArgs ln{bufX, D, M, D, b.ln1[bq], bufLN, D};
-    ln.pre = b.ln1[bq].pre;
-    // qkv -> qact1                                                          vit_fquant.py:293,307
-    p2v_epilogue e{};
-    e.inv_s_out = b.inv_s_qkv[bq];
-    e.tap_out = qkv_tap ? qkv_tap[i] : (lin_tap ? lin_tap[1 + 4 * i] : nullptr);
-    if (p->lin[bq][1 + 4 * i].w_frag && p2v_ln_gemm_supported(P2V_EPI_REQUANT, D, 3 * D, 0)) {              // one launch: the LayerNorm output stays in LDS
-      if (!taps) ln.out = nullptr;
-      STEP(P2V_K_LN_GEMM_QKV, run_ln_gemm(P2V_EPI_REQUANT, ln, p->lin[bq][1 + 4 * i], e, 3 * D, bufQKV, st));
-    } else {
-      STEP(P2V_K_LAYERNORM, launch_rc(p2v_launch_layernorm(ln, st), "int_layernorm"));
-      STEP(P2V_K_GEMM_QKV, run_gemm(P2V_EPI_REQUANT, bufLN, D, M, Dk, 3 * D, p->lin[bq][1 + 4 * i], e, bufQKV, 3 * D, nullptr, st));
-    }
-    DDV_TAP(T, 3 * D);                                                       // attn.qkv
-    DDV_I8(bufQKV, T, 3 * D, nullptr);                                       // attn.qact1
-    // scores -> qact_attn1 -> log-int-softmax -> @v -> qact2                vit_fquant.py:309-326
-    AttnArgs at{bufQKV, batch, T, d.num_heads, b.attn, bufATT, nullptr};
-    // proj -> qact3 -> + x -> Block.qact2                                   vit_fquant.py:334-338,431
-    p2v_epilogue ep = b.proj_epi;
-    ep.residual = bufX;
-    ep.resid_tab = p->resid_tab[(size_t)i * 4 + bp];
-    if (i == d.depth - 1 && cls_only) {
-      // The logits read the last block's output through its class-token rows only (the final norm below takes [:, 0]) and everything
-      // behind the qkv GEMM is row-local but for the attention's keys and values: query row 0 of every (image, head), then proj, norm2,
-      // fc1 and fc2 on `batch` rows - proj and fc2 in place on the class rows of bufX (stride T * D), the rows between them compact at the
-      // start of bufLN / bufHID.  The patch rows of bufX / bufATT / bufHID keep what the launches before left there.
-      const long long TD = (long long)T * D;
-      at.nq = 1;
-      STEP(P2V_K_ATTENTION, launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"));
-      STEP(P2V_K_GEMM_PROJ, run_gemm_few_rows(P2V_EPI_RESID, bufATT, (int)TD, batch, Dk, D, p->lin[bp][2 + 4 * i], ep, bufX, (int)TD, st));
-      LnArgs lc{bufX, TD, batch, D, b.ln2[bq][b1], bufLN, D};
-      lc.pre = b.ln2[bq][b1].pre;
-      STEP(P2V_K_LAYERNORM, launch_rc(p2v_launch_layernorm(lc, st), "int_layernorm"));
-      p2v_epilogue e1{};
-      e1.inv_s_out = b.inv_s_fc1;
-      e1.gelu = b.gelu_fc1;
-      STEP(P2V_K_GEMM_FC1, run_gemm_few_rows(P2V_EPI_GELU, bufLN, D, batch, Dk, Hd, p->lin[b1][3 + 4 * i], e1, bufHID, Hd, st));
-      p2v_epilogue e2 = b.fc2_epi;
-      e2.residual = bufX;
-      e2.resid_tab = p->resid_tab[(size_t)i * 4 + 2 + b2];
-      STEP(P2V_K_GEMM_FC2, run_gemm_few_rows(P2V_EPI_RESID, bufHID, Hd, batch, Hk, D, p->lin[b2][4 + 4 * i], e2, bufX, (int)TD, st));
-      continue;
-    }
-    STEP(P2V_K_ATTENTION, launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"));
-    DDV_I8(bufATT, T, D, nullptr);                                           // attn.qact2
-    STEP(P2V_K_GEMM_PROJ, run_gemm(P2V_EPI_RESID, bufATT, D, M, Dk, D, p->lin[bp][2 + 4 * i], ep, bufX, D, nullptr, st));
-    LIN_TAP(2 + 4 * i, bufATT, D, M, Dk, D, p->lin[bp][2 + 4 * i]);
-    DDV_TAP(T, D);                                                           // attn.proj
-    DDV_I8(bufX, T, D, b.proj_epi.s_next);                                   // Block.qact2
-    // norm2 (attention's channel scale!) -> /mlp.channel_scale -> mlp.qact0 vit_fquant.py:464, layers_quant.py:305-311
-    LnArgs ln2{bufX, D, M, D, b.ln2[bq][b1], bufLN, D};
-    ln2.pre = b.ln2[bq][b1].pre;
-    // fc1 -> GELU -> qact1                                                  layers_quant.py:316,331-333
-    p2v_epilogue e1{};
-    e1.inv_s_out = b.inv_s_fc1;
-    e1.gelu = b.gelu_fc1;
-    e1.tap_out = fc1_tap ? fc1_tap[i] : (lin_tap ? lin_tap[3 + 4 * i] : nullptr);
-    if (p->lin[b1][3 + 4 * i].w_frag && p2v_ln_gemm_supported(P2V_EPI_GELU, D, Hd, e1.gelu.table ? e1.gelu.cells : 0)) {
-      if (!taps) ln2.out = nullptr;
-      STEP(P2V_K_LN_GEMM_FC1, run_ln_gemm(P2V_EPI_GELU, ln2, p->lin[b1][3 + 4 * i], e1, Hd, bufHID, st));
-    } else {
-      STEP(P2V_K_LAYERNORM, launch_rc(p2v_launch_layernorm(ln2, st), "int_layernorm"));
-      STEP(P2V_K_GEMM_FC1, run_gemm(P2V_EPI_GELU, bufLN, D, M, Dk, Hd, p->lin[b1][3 + 4 * i], e1, bufHID, Hd, nullptr, st));
-    }
-    DDV_TAP(T, Hd);                                                          // mlp.fc1
-    DDV_I8(bufHID, T, Hd, nullptr);                                          // mlp.qact1
-    // fc2 -> qact2 -> + x -> Block.qact4                                    layers_quant.py:342-346, vit_fquant.py:468
-    p2v_epilogue e2 = b.fc2_epi;
-    e2.residual = bufX;
-    e2.resid_tab = p->resid_tab[(size_t)i * 4 + 2 + b2];
-    STEP(P2V_K_GEMM_FC2, run_gemm(P2V_EPI_RESID, bufHID, Hd, M, Hk, D, p->lin[b2][4 + 4 * i], e2, bufX, D, nullptr, st));
-    LIN_TAP(4 + 4 * i, bufHID, Hd, M, Hk, D, p->lin[b2][4 + 4 * i]);
-    DDV_TAP(T, D);                                                           // mlp.fc2
-    DDV_I8(bufX, T, D, b.fc2_epi.s_next);                                    // Block.qact4
-  }
+  // The logits read the last block's output through its class-token rows only (the final norm below takes [:, 0]) and everything
+  // behind the qkv GEMM is row-local but for the attention's keys and values: query row 0 of every (image, head), then proj, norm2,
+  // fc1 and fc2 on `batch` rows - proj and fc2 in place on the class rows of x (stride T * D), the rows between them compact at the
+  // start of ln / hid.  The patch rows of x / att / hid keep what the launches before left there.  So the last block runs on the class
+  // rows when nothing but the logits is asked for (parity runs read the workspace), and T * D fits the int strides of a GEMM.
+  const bool cls_only = g_cls_rows && o.stop_after < 0 && !o.qkv_tap && !o.fc1_tap && !o.lin_tap && !o.ddv && (long long)T * D <= 0x7fffffffLL;
+  const RowSet all_rows{f.M, D, 0, false}, cls_rows{batch, (long long)T * D, 1, true};
+  for (int i = 0; i < d.depth && !f.done; ++i)
+    if ((rc = f.block(i, bit_config + 1 + 4 * i, (cls_only && i == d.depth - 1) ? cls_rows : all_rows))) return rc;
+
   // norm over the cls rows only ([:,0]) -> qact2 -> head -> act_out         vit_fquant.py:766-796
-  LnArgs lf{bufX, (long long)T * D, batch, D, p->final_ln, bufCLS, D};
+  LnArgs lf{f.X, (long long)T * D, batch, D, p->final_ln, f.CLS, D};
   lf.pre = p->final_ln.pre;
-  STEP(P2V_K_LAYERNORM, launch_rc(p2v_launch_layernorm(lf, st), "int_layernorm"));
-  DDV_I8(bufCLS, 1, D, nullptr);                                             // qact2
+  if ((rc = f.layernorm(lf)) || (rc = f.ddv_i8(f.CLS, 1, D, nullptr))) return rc;                               // qact2
+  const p2v_linear& head = p->lin[bit_index(bit_config[n_cfg - 1])][n_cfg - 1];
   p2v_epilogue eh{};
   eh.inv_s_out = p->head_inv_s;
   eh.s_out = p->head_s;
-  STEP(P2V_K_GEMM_HEAD, run_gemm(P2V_EPI_HEAD, bufCLS, D, batch, Dk, d.num_classes, p->lin[bit_index(bit_config[n_cfg - 1])][n_cfg - 1], eh, logits,
-                d.num_classes, nullptr, st));
-  LIN_TAP(n_cfg - 1, bufCLS, D, batch, Dk, d.num_classes, p->lin[bit_index(bit_config[n_cfg - 1])][n_cfg - 1]);
-  DDV_TAP(1, d.num_classes);                                                 // head
-  if (ddv && (rc = ddv_reduce(ddv, logits, 1, d.num_classes, P2V_COS_F32, nullptr, st))) return rc;   // act_out
-#undef DDV_TAP
-#undef DDV_I8
-#undef LIN_TAP
-#undef STEP
-  if (prof) {
+  if ((rc = f.gemm(P2V_K_GEMM_HEAD, false, P2V_EPI_HEAD, f.CLS, D, batch, f.Dk, d.num_classes, head, eh, logits, d.num_classes))) return rc;
+  if ((rc = f.lin_tap(n_cfg - 1, f.CLS, D, batch, f.Dk, d.num_classes, head)) || (rc = f.ddv_tap(1, d.num_classes)) ||
+      (rc = f.ddv_f32(logits, 1, d.num_classes)))                                                                // head, act_out
+    return rc;
+  if (f.done) return P2V_OK;
+  if (Prof* prof = o.prof) {
     if (prof->used + 2 > (int)prof->ev.size()) return fail(P2V_E_LAUNCH, "profile: event pool exhausted");
     hipEventRecord(prof->ev[prof->used++], st);
     hipEventRecord(prof->ev[prof->used++], st);      // an empty interval: the cost of the event pair itself (P2V_K_EVENT_GAP)
@@ -777,9 +768,13 @@ static int forward_impl(p2v_plan* p, const float* images, int batch, const int8_
   return P2V_OK;
 }
 
+extern "C" {
+
 int p2v_forward(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
                 size_t workspace_bytes, int stop_after, void* stream) {
-  return forward_impl(p, images, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stop_after, stream, nullptr);
+  FwdOpts o;
+  o.images = images; o.stop_after = stop_after;
+  return forward_impl(p, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stream, o);
 }
 
 // uint8 input (p2v_forward_u8, p2v_u8_patchify): images and table present, a known layout, images 4-byte aligned (the kernels read dwords)
@@ -794,19 +789,24 @@ int p2v_forward_u8(p2v_plan* p, const uint8_t* images, int layout, const void* l
                    float* logits, void* workspace, size_t workspace_bytes, int stop_after, void* stream) {
   const int rc = check_u8_input("p2v_forward_u8", images, layout, lut);
   if (rc) return rc;
-  return forward_impl(p, nullptr, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stop_after, stream, nullptr, nullptr, nullptr,
-                      nullptr, images, layout, lut);
+  FwdOpts o;
+  o.u8 = images; o.layout = layout; o.lut = lut; o.stop_after = stop_after;
+  return forward_impl(p, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stream, o);
 }
 
 int p2v_forward_taps(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
                      size_t workspace_bytes, float* const* qkv_out, float* const* fc1_out, void* stream) {
-  return forward_impl(p, images, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, -1, stream, nullptr, qkv_out, fc1_out);
+  FwdOpts o;
+  o.images = images; o.qkv_tap = qkv_out; o.fc1_tap = fc1_out;
+  return forward_impl(p, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stream, o);
 }
 
 int p2v_forward_linear_taps(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
                             size_t ws_bytes, float* const* taps, void* stream) {
   if (!taps) return fail(P2V_E_ARG, "p2v_forward_linear_taps: null taps array");
-  return forward_impl(p, images, batch, bit_config, n_cfg, logits, ws, ws_bytes, -1, stream, nullptr, nullptr, nullptr, taps);
+  FwdOpts o;
+  o.images = images; o.lin_tap = taps;
+  return forward_impl(p, batch, bit_config, n_cfg, logits, ws, ws_bytes, stream, o);
 }
 
 static int prof_collect(Prof& prof, float* ms_out, int32_t* kind_out, int max_launches) {
@@ -822,31 +822,17 @@ static int prof_collect(Prof& prof, float* ms_out, int32_t* kind_out, int max_la
   return n;
 }
 
-int p2v_forward_profile(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
-                        size_t workspace_bytes, void* stream, float* ms_out, int32_t* kind_out, int max_launches) {
-  if (!p || !ms_out || !kind_out || max_launches <= 0) return fail(P2V_E_ARG, "p2v_forward_profile: null argument");
-  Prof prof;
-  if (!prof.make_pool(prof_pool_size(p))) return fail(P2V_E_LAUNCH, "hipEventCreate failed");
-  const int rc = forward_impl(p, images, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, -1, stream, &prof);
-  return rc == P2V_OK ? prof_collect(prof, ms_out, kind_out, max_launches) : rc;
-}
-
 int p2v_forward_profile_begin(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
                               size_t workspace_bytes, void* stream, void** token) {
   if (!p || !token) return fail(P2V_E_ARG, "p2v_forward_profile_begin: null argument");
   *token = nullptr;
-  Prof* prof = new Prof();
-  if (!prof->make_pool(prof_pool_size(p))) {
-    delete prof;
-    return fail(P2V_E_LAUNCH, "hipEventCreate failed");
-  }
-  const int rc = forward_impl(p, images, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, -1, stream, prof);
-  if (rc != P2V_OK) {
-    delete prof;
-    return rc;
-  }
-  *token = prof;
-  return P2V_OK;
+  std::unique_ptr<Prof> prof(new Prof());
+  if (!prof->make_pool(prof_pool_size(p))) return fail(P2V_E_LAUNCH, "hipEventCreate failed");
+  FwdOpts o;
+  o.images = images; o.prof = prof.get();
+  const int rc = forward_impl(p, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stream, o);
+  if (rc == P2V_OK) *token = prof.release();        // the caller's, until p2v_forward_profile_end
+  return rc;
 }
 
 int p2v_forward_profile_end(void* token, float* ms_out, int32_t* kind_out, int max_launches) {
@@ -859,12 +845,26 @@ int p2v_forward_profile_end(void* token, float* ms_out, int32_t* kind_out, int m
   return n;
 }
 
+int p2v_forward_profile(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
+                        size_t workspace_bytes, void* stream, float* ms_out, int32_t* kind_out, int max_launches) {
+  if (!p || !ms_out || !kind_out || max_launches <= 0) return fail(P2V_E_ARG, "p2v_forward_profile: null argument");
+  void* token;
+  const int rc = p2v_forward_profile_begin(p, images, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stream, &token);
+  return rc == P2V_OK ? p2v_forward_profile_end(token, ms_out, kind_out, max_launches) : rc;
+}
+
 // ---- per-operator entry points ------------------------------------------------------------------------
+// what both patchify entry points ask of the image and of the patch matrix's row
+static int check_patchify_shape(int chans, int height, int width, int patch, int k_pad) {
+  if (patch <= 0 || patch % 4 || height % patch || width % patch) return fail(P2V_E_SHAPE, "image %dx%d not divisible into %d-patches", height, width, patch);
+  if (k_pad % 4 || k_pad < chans * patch * patch) return fail(P2V_E_ARG, "k_pad %d too small / unaligned", k_pad);
+  return P2V_OK;
+}
+
 int p2v_quantize_patchify(const float* img, int batch, int chans, int height, int width, int patch, float inv_s, int8_t* out,
                           int k_pad, void* stream) {
   if (!img || !out) return fail(P2V_E_ARG, "p2v_quantize_patchify: null argument");
-  if (patch <= 0 || patch % 4 || height % patch || width % patch) return fail(P2V_E_SHAPE, "image %dx%d not divisible into %d-patches", height, width, patch);
-  if (k_pad % 4 || k_pad < chans * patch * patch) return fail(P2V_E_ARG, "k_pad %d too small / unaligned", k_pad);
+  if (const int rc = check_patchify_shape(chans, height, width, patch, k_pad)) return rc;
   return launch_rc(p2v_launch_patchify(img, batch, chans, height, width, patch, inv_s, out, k_pad, (hipStream_t)stream), "quantize_patchify");
 }
 
@@ -874,8 +874,7 @@ int p2v_u8_patchify(const uint8_t* img, int layout, const void* lut_i8, int batc
   if (rc) return rc;
   if (!out) return fail(P2V_E_ARG, "p2v_u8_patchify: null argument");
   if (batch <= 0 || chans <= 0) return fail(P2V_E_SHAPE, "p2v_u8_patchify: batch %d, %d channels", batch, chans);
-  if (patch <= 0 || patch % 4 || height % patch || width % patch) return fail(P2V_E_SHAPE, "image %dx%d not divisible into %d-patches", height, width, patch);
-  if (k_pad % 4 || k_pad < chans * patch * patch) return fail(P2V_E_ARG, "k_pad %d too small / unaligned", k_pad);
+  if ((rc = check_patchify_shape(chans, height, width, patch, k_pad))) return rc;
   return launch_rc(p2v_launch_u8_patchify(img, batch, chans, height, width, patch, layout, (const int8_t*)lut_i8, out, k_pad, (hipStream_t)stream),
                    "u8_patchify");
 }
@@ -901,7 +900,7 @@ int p2v_ln_prefold(p2v_ln* ln, int C, float* buf, size_t buf_bytes) {
   if (!ln || !buf) return fail(P2V_E_ARG, "p2v_ln_prefold: null argument");
   ln->pre = kNoPre;
   if (C <= 0 || C % 4 || C > 2048) return fail(P2V_E_SHAPE, "p2v_ln_prefold: C must be a positive multiple of 4 up to 2048");
-  if (!ln->gamma || !ln->beta || !ln->inv_out || !ln->post_mul) return fail(P2V_E_ARG, "p2v_ln_prefold: LayerNorm constants missing");
+  if (!ln_constants_present(*ln, false)) return fail(P2V_E_ARG, "p2v_ln_prefold: LayerNorm constants missing");      // (the fold does not read the mask)
   if (buf_bytes < p2v_ln_prefold_bytes(C)) return fail(P2V_E_WORKSPACE, "p2v_ln_prefold: buffer %zu < %zu bytes", buf_bytes, p2v_ln_prefold_bytes(C));
   OwnerDevice own(buf);
   if (!own.ok()) return fail(P2V_E_ARG, "p2v_ln_prefold: buf is not a device pointer");
@@ -960,30 +959,27 @@ int p2v_ln_gemm_fusable(int kind, int C, int N, int cells) {
   return (C > 0 && N > 0 && cells >= 0 && cells <= 4096 && p2v_ln_gemm_supported(kind, C, N, cells)) ? 1 : 0;
 }
 
+// both attention entry points; query_rows 0 (below min_rows for the entry point that takes a count): every row
+static int lis_attention(const char* who, const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int min_rows,
+                         int query_rows, int8_t* out, int8_t* probs_k, void* stream) {
+  if (!qkv || !at || !out) return fail(P2V_E_ARG, "%s: null argument", who);
+  if (batch <= 0 || tokens <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad attention shape");
+  if (query_rows < min_rows || query_rows > tokens) return fail(P2V_E_SHAPE, "%s: query_rows %d outside 1 .. %d", who, query_rows, tokens);
+  const int rc = check_attn(who, *at);
+  if (rc != P2V_OK) return rc;
+  AttnArgs a{qkv, batch, tokens, heads, *at, out, probs_k};
+  a.nq = query_rows;
+  return launch_rc(p2v_launch_attention(a, head_dim, (hipStream_t)stream), "lis_attention");
+}
+
 int p2v_lis_attention(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int8_t* out,
                       int8_t* probs_k, void* stream) {
-  if (!qkv || !at || !out) return fail(P2V_E_ARG, "p2v_lis_attention: null argument");
-  if (batch <= 0 || tokens <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad attention shape");
-  {
-    const int rc = check_attn("p2v_lis_attention", *at);
-    if (rc != P2V_OK) return rc;
-  }
-  AttnArgs a{qkv, batch, tokens, heads, *at, out, probs_k};
-  return launch_rc(p2v_launch_attention(a, head_dim, (hipStream_t)stream), "lis_attention");
+  return lis_attention("p2v_lis_attention", qkv, batch, tokens, heads, head_dim, at, 0, 0, out, probs_k, stream);
 }
 
 int p2v_lis_attention_rows(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int query_rows,
                            int8_t* out, void* stream) {
-  if (!qkv || !at || !out) return fail(P2V_E_ARG, "p2v_lis_attention_rows: null argument");
-  if (batch <= 0 || tokens <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad attention shape");
-  if (query_rows < 1 || query_rows > tokens) return fail(P2V_E_SHAPE, "p2v_lis_attention_rows: query_rows %d outside 1 .. %d", query_rows, tokens);
-  {
-    const int rc = check_attn("p2v_lis_attention_rows", *at);
-    if (rc != P2V_OK) return rc;
-  }
-  AttnArgs a{qkv, batch, tokens, heads, *at, out, nullptr};
-  a.nq = query_rows;
-  return launch_rc(p2v_launch_attention(a, head_dim, (hipStream_t)stream), "lis_attention");
+  return lis_attention("p2v_lis_attention_rows", qkv, batch, tokens, heads, head_dim, at, 1, query_rows, out, nullptr, stream);
 }
 
 int p2v_patch_merge_gather(const int8_t* x, int batch, int H, int W, int C, int8_t* out, void* stream) {
@@ -1294,6 +1290,7 @@ int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bi
     taps.assign(plan->n_layers, tap_scratch);      // every linear output goes through the one buffer; the patch embedding is no DDV stage
     taps[0] = nullptr;
   }
-  return forward_impl(plan, images, 2 * n, bit_config, n_cfg, logits, ws, fwd, -1, stream, nullptr, nullptr, nullptr,
-                      with_linear ? taps.data() : nullptr, nullptr, 0, nullptr, &ctx);
+  FwdOpts o;
+  o.images = images; o.ddv = &ctx; o.lin_tap = with_linear ? taps.data() : nullptr;
+  return forward_impl(plan, 2 * n, bit_config, n_cfg, logits, ws, fwd, stream, o);
 }

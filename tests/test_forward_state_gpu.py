@@ -16,30 +16,12 @@ import pytest
 import torch
 
 from _arena import SENTINELS, Arena
+from _tuning import tuning
 from conftest import gpu_ok
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_ok(), reason='needs a GPU')]
 
 FILLS = SENTINELS + (0x80,)
-
-# what the switches are restored to: the table of test_kernel_edges_gpu.py (the initialisers in diff-vit_amd/csrc) plus ln_gemm = 1 (LayerNorm
-# fused into qkv / fc1) and cls_rows = 1 (the last block on the class rows).  p2v_set_tuning has no getter; a changed initialiser has to be mirrored here
-DEFAULTS = dict(gemm_tile=0, gemm_rows=0, resid_pre=1, ln_pre=1, ln_rows=4, ln_gemm_version=2, attn_stream=0, ln_gemm=1, cls_rows=1)
-
-
-class tuning:
-    """p2v_set_tuning switches for the duration of a block, restored on the way out"""
-
-    def __init__(self, L, **kw):
-        self.L, self.kw = L, kw
-
-    def __enter__(self):
-        for k, v in self.kw.items():
-            assert self.L.p2v_set_tuning(k.encode(), v) == 0, (k, v)
-
-    def __exit__(self, *exc):
-        rcs = [self.L.p2v_set_tuning(k.encode(), DEFAULTS[k]) for k in self.kw]           # every switch first, then the verdict
-        assert rcs == [0] * len(rcs), (list(self.kw), rcs)
 
 
 @pytest.fixture(scope='module')
