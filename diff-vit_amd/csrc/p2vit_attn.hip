@@ -323,6 +323,17 @@ int p2v_launch_window_attention(const WinAttnArgs& a, hipStream_t st) {
 int p2v_launch_attention_wide(const AttnArgs& a, int head_dim, int nkb, hipStream_t st);      // p2vit_attn_wide.hip
 
 int g_attn_stream = 0;    // P2V_ATTN_STREAM=1: every launch takes the streaming kernel (parity runs against the resident one; same codes)
+int g_attn_packed = 1;    // P2V_ATTN_PACKED=0: beyond the resident kernel's token count every launch takes the streaming kernel, as before the packed one
+// the ONE selection rule: p2v_launch_attention follows it, p2v_attention_kernel (C ABI) reports it
+int p2v_attention_kernel_of(int head_dim, int tokens, int tapped) {
+  const int resident = p2v_resident_tokens_of(head_dim);
+  if (!resident || tokens <= 0 || tokens > P2V_MAX_TOKENS_STREAMED) return -1;
+  if (g_attn_stream) return P2V_KERNEL_STREAMING;
+  if (tokens <= resident) return P2V_KERNEL_RESIDENT;
+  if (g_attn_packed && head_dim == 64 && !tapped && tokens <= P2V_MAX_TOKENS_PACKED) return P2V_KERNEL_PACKED;
+  return P2V_KERNEL_STREAMING;
+}
+
 int p2v_launch_attention(const AttnArgs& a, int head_dim, hipStream_t st) {
   const int nkb = (a.N + 31) / 32;
   {   // the kernel folds s_q1^2 / s_attn into qk_scale: exact only for a power of two (both are PoT scales in the reference)
@@ -330,7 +341,12 @@ int p2v_launch_attention(const AttnArgs& a, int head_dim, hipStream_t st) {
     const float m2 = a.at.s_qkv_sq * a.at.inv_s_attn;
     if (!(m2 > 0.f) || frexpf(m2, &ex) != 0.5f) return -2;
   }
-  if (g_attn_stream || a.N > p2v_resident_tokens_of(head_dim)) return p2v_launch_attention_stream(a, head_dim, st);
+  switch (p2v_attention_kernel_of(head_dim, a.N, a.probs_k != nullptr)) {
+    case P2V_KERNEL_RESIDENT: break;
+    case P2V_KERNEL_PACKED: return p2v_launch_attention_packed(a, st);
+    case P2V_KERNEL_STREAMING: return p2v_launch_attention_stream(a, head_dim, st);
+    default: return -1;
+  }
   if (head_dim == 64) { P2V_ATTN_CASES(64, 19, true) }
   if (head_dim == 32) { P2V_ATTN_CASES(32, 19, false) }
   return p2v_launch_attention_wide(a, head_dim, nkb, st);

@@ -33,6 +33,27 @@ __device__ __forceinline__ unsigned lis_prob_pair(float r0, float r1) {
   return out;
 }
 
+// Entry t of the two softmax tables (int_exp / int_polynomial, layers.py:334-358): exp_int of d = max - score = t, and the fp64 reciprocal of
+// float(exp_int) the per-score quotient is one multiply by.  Entry 256 is the sentinel of padded keys: 0 to the sum, and sum / 1 >= 2^32 makes
+// the exponent clamp, i.e. probability 0.  (k_lis_attention_packed fills its tables with this; the older kernels carry the same lines inline.)
+__device__ __forceinline__ void lis_table_entry(const p2v_attn& at, int t, long long* lutE, double* lutFR) {
+  if (t >= 256) {
+    lutE[256] = 0;
+    lutFR[256] = 1.0;
+    return;
+  }
+  int xi = -t;
+  const int lim = 32 * at.x0_int;
+  xi = xi < lim ? lim : xi;
+  const int q = xi / at.x0_int;                  // both <= 0: trunc == floor
+  const int r = xi - at.x0_int * q;
+  const long long z = (long long)r * (r + at.b_int) + at.c_int;
+  long long e = z << (32 - q);
+  e = e < 0 ? 0 : e;
+  lutE[t] = e;
+  lutFR[t] = 1.0 / (double)(float)e;             // (float)e is exact: z < 2^24
+}
+
 // ISH: the score multiplier qk_scale * s_q1^2 / s_attn is 2^-pshift with pshift >= 1 (head_dim 64: qk_scale = 1/8): the qact_attn1
 // codes come from an integer round-half-even shift instead of the fp32 cvt / mul / rndne / med3 / cvt chain (2.5 VALU per score less)
 #ifdef P2V_DIAG

@@ -131,6 +131,7 @@ extern int g_ln_gemm_ver;
 extern int g_gemm_tile;
 extern int g_resid_pre;
 extern int g_attn_stream;
+extern int g_attn_packed;
 extern int g_ln_pre;
 extern int g_gemm_rows;
 int g_cls_rows = 1;       // 0: the last block of p2v_forward computes every row, as the other blocks do (A/B and parity runs)
@@ -153,6 +154,7 @@ static const struct Switch {
     {"ln_gemm_version", "P2V_LN_GEMM_V", &g_ln_gemm_ver, 1, 3, 1, 0},
     {"gemm_tile", "P2V_GEMM_TILE", &g_gemm_tile, 0, 256, 128, 0},
     {"attn_stream", "P2V_ATTN_STREAM", &g_attn_stream, 0, 1, 1, ANY_ENV | ANY_API},
+    {"attn_packed", "P2V_ATTN_PACKED", &g_attn_packed, 0, 1, 1, 0},
     {"ln_pre", "P2V_LN_PRE", &g_ln_pre, 0, 1, 1, ANY_ENV | ANY_API},
     {"resid_pre", "P2V_RESID_PRE", &g_resid_pre, 0, 1, 1, ANY_ENV | ANY_API},
     {"gemm_rows", "P2V_GEMM_ROWS", &g_gemm_rows, 0, 2, 1, 0},
@@ -174,6 +176,11 @@ int p2v_abi_version(void) { read_env_once(); return P2V_ABI_VERSION; }
 
 int p2v_resident_tokens(int head_dim) { return p2v_resident_tokens_of(head_dim); }
 int p2v_max_tokens(int head_dim) { return p2v_resident_tokens_of(head_dim) ? P2V_MAX_TOKENS_STREAMED : 0; }
+int p2v_packed_tokens(int head_dim) { return head_dim == 64 ? P2V_MAX_TOKENS_PACKED : 0; }
+int p2v_attention_kernel(int head_dim, int tokens, int tapped) {
+  read_env_once();
+  return p2v_attention_kernel_of(head_dim, tokens, tapped);
+}
 
 int p2v_set_tuning(const char* name, int value) {
   if (!name) return fail(P2V_E_ARG, "p2v_set_tuning: null name");

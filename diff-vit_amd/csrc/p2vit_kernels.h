@@ -50,7 +50,7 @@ struct AttnArgs {
   int8_t* out;
   int8_t* probs_k;
   int pshift;           // filled by the launcher: score multiplier = 2^-pshift (>= 1) -> integer requant path; 0 = fp32 path
-  int nq;               // query rows to compute, in whole 16-row blocks (0 = all): the resident kernel; the streaming kernel computes all rows
+  int nq;               // query rows to compute, in whole 16-row blocks (0 = all): the resident and the packed kernel; the streaming kernel computes all rows
 #ifdef P2V_DIAG
   unsigned long long* stamps;   // diagnostic build only: 16 cycle stamps per workgroup (wave 0) or null
 #endif
@@ -86,6 +86,9 @@ bool p2v_ln_gemm_supported(int epi, int C, int N, int table_cells);
 int p2v_launch_ln_gemm(int epi, const LnArgs& a, const GemmArgs& g, hipStream_t st);   // -3: shape not fused
 int p2v_launch_attention(const AttnArgs& a, int head_dim, hipStream_t st);
 int p2v_launch_attention_stream(const AttnArgs& a, int head_dim, hipStream_t st);   // any token count up to P2V_MAX_TOKENS_STREAMED (p2vit_attn_stream.hip)
+int p2v_launch_attention_packed(const AttnArgs& a, hipStream_t st);   // head_dim 64, no tap, 609 .. P2V_MAX_TOKENS_PACKED tokens (p2vit_attn_packed.hip); the lower end is p2v_attention_kernel_of's: the launcher itself refuses only what has no instantiation (below 10 groups of 64 keys)
+// which kernel p2v_launch_attention takes under the current switches: the P2V_KERNEL_* values of include/p2vit.h, -1 = refused (p2vit_attn.hip)
+int p2v_attention_kernel_of(int head_dim, int tokens, int tapped);
 // tokens per image the resident attention kernel covers (K / V^T of a head in LDS: 3 * head_dim bytes per key); 0: head_dim not instantiated
 inline int p2v_resident_tokens_of(int head_dim) {
   if (head_dim == 32 || head_dim == 48 || head_dim == 64 || head_dim == 80) return P2V_MAX_TOKENS;

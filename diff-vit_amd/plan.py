@@ -93,6 +93,15 @@ class FrozenPlan:
         """integer value of the C plan pointer (the ``plan`` argument of ``torch.ops.p2vit.forward``)."""
         return int(self._handle.value or 0)
 
+    @property
+    def attention_kernel(self):
+        """'resident' | 'packed' | 'stream': the attention kernel the forward of this geometry launches under the current switches - the
+        library's own selection (p2v_attention_kernel), asked at every read."""
+        which = E.lib().p2v_attention_kernel(self.D // self.H, self.tokens, 0)
+        if which < 0:
+            raise NotImplementedError('no attention kernel for head_dim %d at %d tokens' % (self.D // self.H, self.tokens))
+        return ('resident', 'packed', 'stream')[which]
+
     # ---------------------------------------------------------------------------------------------
     def _dev(self, t, dtype=torch.float32):
         t = t.detach().to(dtype).contiguous().to(self.device)

@@ -44,10 +44,15 @@
  *     map launch by launch, one workspace through a history of calls, 2 / 5 / 10 tokens per image against the oracle.)
  *
  * Limits of what is instantiated (everything else returns P2V_E_UNSUPPORTED, at plan creation where the geometry is known):
- *   - ViT attention: head_dim 32, 48, 64, 80, 96 or 128 (round 4; before: 32 / 64); up to P2V_MAX_TOKENS_STREAMED = 4096 tokens per image.  The
- *     fast kernel keeps K / V^T of an image's head in LDS: P2V_MAX_TOKENS = 608 tokens (224^2 / 16 = 197, 384^2 / 16 = 577, ...), 544 at head_dim 96,
- *     384 at head_dim 128 (p2v_resident_tokens); beyond, a streaming kernel re-reads K / V per query block (round 4: slow, exact, so that no
- *     geometry of the reference's VisionTransformer is refused; 448^2 / 16 = 785, 512^2 / 16 = 1025);
+ *   - ViT attention: head_dim 32, 48, 64, 80, 96 or 128 (round 4; before: 32 / 64); up to P2V_MAX_TOKENS_STREAMED = 4096 tokens per image.  Three
+ *     kernels, chosen per launch (p2v_attention_kernel tells which), all with the same codes:
+ *       resident - K / V^T (bf16) of an image's head in LDS, a query block's scores in registers: up to P2V_MAX_TOKENS = 608 tokens (224^2 / 16 =
+ *         197, 384^2 / 16 = 577, ...), 544 at head_dim 96, 384 at head_dim 128 (p2v_resident_tokens);
+ *       packed - head_dim 64 without the probs_k tap, beyond the resident kernel up to P2V_MAX_TOKENS_PACKED = 1216 tokens (448^2 / 16 = 785,
+ *         512^2 / 16 = 1025; p2v_packed_tokens): K and V^T (int8) in LDS, score codes four to a register, P.V on the int8 MFMA;
+ *       streaming - everything else up to 4096 tokens (other head dimensions beyond their resident limit, 1217 tokens and more, every launch
+ *         with probs_k beyond the resident limit): re-reads K / V per query block (round 4: slow, exact, so that no geometry of the
+ *         reference's VisionTransformer is refused);
  *     Swin window attention: head_dim 32, windows up to 8 x 8;
  *   - embed_dim and MLP width of a plan: multiples of 16 (round 4; before: 64) - the contractions walk 64-deep k-tiles through zero weight
  *     columns (p2v_linear: k_pad = round_up(K, 64)); the per-operator GEMM entry points take K in whole k-tiles;
@@ -70,10 +75,20 @@ extern "C" {
 #define P2V_ABI_VERSION 6
 #define P2V_MAX_TOKENS 608            /* tokens per image of the RESIDENT ViT attention kernel (K / V^T of a head in LDS; 19 pairs of 32 keys) */
 #define P2V_MAX_TOKENS_STREAMED 4096  /* tokens per image of the streaming attention kernel that takes over beyond the resident one's limit (round 4) */
+#define P2V_MAX_TOKENS_PACKED 1216    /* tokens per image of the packed attention kernel (head_dim 64: K / V^T as int8 in LDS; 19 groups of 64 keys) */
 /* tokens per image a plan / p2v_lis_attention accepts at this head dimension (P2V_MAX_TOKENS_STREAMED; 0: head_dim not instantiated), and how many of
- * them the resident (fast) kernel covers: 608 up to head_dim 80, 544 at 96, 384 at 128 - launches beyond run the streaming kernel */
+ * them the resident (fast) kernel covers: 608 up to head_dim 80, 544 at 96, 384 at 128 - launches beyond run the packed or the streaming kernel */
 int p2v_max_tokens(int head_dim);
 int p2v_resident_tokens(int head_dim);
+/* (additive) tokens per image the packed kernel covers beyond the resident one: P2V_MAX_TOKENS_PACKED at head_dim 64, 0 at every other */
+int p2v_packed_tokens(int head_dim);
+/* (additive) the kernel a p2v_lis_attention / p2v_lis_attention_rows / plan launch of this shape takes under the current switches
+ * ("attn_stream", "attn_packed"); tapped: probs_k != NULL.  -1: the shape is refused (head_dim not instantiated, tokens outside 1 .. 4096).
+ * It is the function the launcher itself asks. */
+#define P2V_KERNEL_RESIDENT 0
+#define P2V_KERNEL_PACKED 1
+#define P2V_KERNEL_STREAMING 2
+int p2v_attention_kernel(int head_dim, int tokens, int tapped);
 
 enum {
   P2V_OK = 0,
@@ -405,8 +420,8 @@ int p2v_lis_attention(const int8_t* qkv, int batch, int tokens, int heads, int h
  * The same core for the first `query_rows` query tokens of every image only (1 <= query_rows <= tokens; all keys and values take
  * part): what the last block of a ViT needs, whose output is read through the class token alone.  Same layouts and checks as
  * p2v_lis_attention, no probs_k tap.  The kernel works in blocks of 16 query rows: rows 0 .. min(tokens, 16 * ceil(query_rows / 16)) - 1
- * of every image in `out` are written (each with its own, correct values), the rows behind them are not touched.  Beyond the
- * resident kernel's token count (p2v_resident_tokens) the streaming kernel computes and writes every row. */
+ * of every image in `out` are written (each with its own, correct values), the rows behind them are not touched: so the resident and
+ * the packed kernel.  Where the streaming kernel runs (p2v_attention_kernel) it computes and writes every row. */
 int p2v_lis_attention_rows(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int query_rows,
                            int8_t* out, void* stream);
 
@@ -621,12 +636,13 @@ const char* p2v_last_error(void);
 int p2v_abi_version(void);
 
 /* Scheduling / A-B switches of the process (also read once from the environment: P2V_LN_GEMM, P2V_LN_GEMM_V, P2V_LN_GENERIC,
- * P2V_LN_ROWS, P2V_ATTN_WAVES, P2V_GEMM_TILE, P2V_RESID_PRE, P2V_LN_PRE, P2V_ATTN_STREAM, P2V_GEMM_ROWS, P2V_CLS_ROWS).  None of them changes a result - every variant is
+ * P2V_LN_ROWS, P2V_ATTN_WAVES, P2V_GEMM_TILE, P2V_RESID_PRE, P2V_LN_PRE, P2V_ATTN_STREAM, P2V_ATTN_PACKED, P2V_GEMM_ROWS, P2V_CLS_ROWS).  None of them changes a result - every variant is
  * bit-identical and is driven through this call by the parity tests (profiles/r04_alt_paths.txt: the whole GPU suite on the alternatives):
  *   "ln_gemm" 0/1 (fuse LayerNorm into qkv / fc1), "ln_gemm_version" 1/2/3 (round-2 4-wave / pipelined 4-wave (default) / 8-wave fused kernel),
  *   "ln_generic" 0/1 (generic LayerNorm chain), "ln_rows" 1..64, "attn_waves" 4..8,
  *   "gemm_tile" 0/128/256 (tile height of the layer GEMMs; 0 = 256 rows when the grid still fills the chip),
  *   "resid_pre" 0/1 (use p2v_epilogue.resid_tab), "ln_pre" 0/1 (use p2v_ln.pre), "attn_stream" 0/1 (streaming attention kernel everywhere),
+ *   "attn_packed" 0/1, nothing else (default 1; 0: beyond the resident kernel's token count every launch takes the streaming kernel),
  *   "cls_rows" 0/1 (default 1: p2v_forward / p2v_forward_u8 / p2v_forward_profile* with stop_after = -1 run the last block behind its qkv
  *   GEMM on the class-token rows only - one query row per (image, head), then proj, norm2, fc1, fc2 on `batch` rows; the logits do not
  *   depend on the other rows.  Consequence: after such a call the workspace views "x", "att", "hid" and "ln" hold the LAST block's values

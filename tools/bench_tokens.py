@@ -1,5 +1,6 @@
 """GPU: throughput of the DeiT-S architecture at other image sizes (token counts), with the per-kernel split of one single-stream forward.
-python tools/bench_tokens.py [batch]  ->  224 (197 tokens), 384 (577: the resident attention kernel's range), 448 (785) and 512 (1025: the streaming kernel)."""
+python tools/bench_tokens.py [batch] [sizes]  ->  224 (197 tokens), 384 (577: the resident attention kernel's range), 448 (785) and 512 (1025:
+the packed kernel; the streaming kernel with P2V_ATTN_PACKED=0); each line names the attention kernel the plan runs."""
 import os, sys, time
 from functools import partial
 import torch
@@ -31,7 +32,8 @@ for img in sizes:
             run()
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / n
-        print('img %d (%d tokens) batch %d %-10s %8.1f img/s  %7.3f ms' % (img, (img // 16) ** 2 + 1, batch, mode, batch / dt, dt * 1e3), flush=True)
+        print('img %d (%d tokens, %s) batch %d %-10s %8.1f img/s  %7.3f ms' % (img, (img // 16) ** 2 + 1, getattr(plan, 'attention_kernel', '-'), batch, mode,
+                                                                                 batch / dt, dt * 1e3), flush=True)
     prof = plan.profile(x, bc)
     agg = {}
     for kind, ms in prof:
