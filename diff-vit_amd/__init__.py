@@ -35,8 +35,8 @@ from .plan import FrozenPlan  # noqa: F401
 from .ptq import BIT_TYPE_DICT, QAct, QConv2d, QIntLayerNorm, QIntSoftmax, QLinear  # noqa: F401
 from .vit import (VisionTransformer, deit_base_patch16_224, deit_small_patch16_224, deit_tiny_patch16_224,  # noqa: F401
                   vit_base_patch16_224, vit_large_patch16_224)
-from .swin import (SwinTransformer, swin_base_patch4_window7_224, swin_small_patch4_window7_224,  # noqa: F401
-                   swin_tiny_patch4_window7_224)
+from .swin import (SwinTransformer, swin_base_patch4_window7_224, swin_base_patch4_window12_384,  # noqa: F401
+                   swin_large_patch4_window12_384, swin_small_patch4_window7_224, swin_tiny_patch4_window7_224)
 from .swin_plan import SwinPlan  # noqa: F401
 from . import cka  # noqa: F401
 from .cka import MinibatchAdvCKA, MinibatchCKA, compute_cka, get_activations  # noqa: F401
@@ -48,5 +48,6 @@ from .score import DeviceMeter, score_rows_reference  # noqa: F401
 __all__ = ['BIT_TYPE_DICT', 'QAct', 'QConv2d', 'QIntLayerNorm', 'QIntSoftmax', 'QLinear', 'Config', 'VisionTransformer',
            'deit_tiny_patch16_224', 'deit_small_patch16_224', 'deit_base_patch16_224', 'vit_base_patch16_224',
            'vit_large_patch16_224', 'FrozenPlan', 'SwinTransformer', 'swin_tiny_patch4_window7_224',
-           'swin_small_patch4_window7_224', 'swin_base_patch4_window7_224', 'SwinPlan', 'get_activations', 'MinibatchCKA',
+           'swin_small_patch4_window7_224', 'swin_base_patch4_window7_224', 'swin_base_patch4_window12_384',
+           'swin_large_patch4_window12_384', 'SwinPlan', 'get_activations', 'MinibatchCKA',
            'MinibatchAdvCKA', 'compute_cka', 'compute_ddv', 'gen_adv_inputs', 'AttackPGD', 'DeviceMeter', 'score_rows_reference']

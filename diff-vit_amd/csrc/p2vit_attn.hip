@@ -306,7 +306,9 @@ __global__ __launch_bounds__(256, 3) void k_window_attention(WinAttnArgs a) {
 // host launchers (called from the C ABI in p2vit_capi.cpp)
 // ---------------------------------------------------------------------------------------------------
 int g_attn_waves = 8;     // P2V_ATTN_WAVES
+int p2v_launch_window_attention_wide(const WinAttnArgs& a, hipStream_t st);      // p2vit_winattn_wide.hip: windows of 9 x 9 ... 12 x 12
 int p2v_launch_window_attention(const WinAttnArgs& a, hipStream_t st) {
+  if (a.wa.ws > 8) return p2v_launch_window_attention_wide(a, st);
   const int hgroups = (a.H + 3) / 4;
   const dim3 grid((unsigned)(a.B * a.wa.n_windows * hgroups));
   if (a.wa.ws == 7) {

@@ -1008,8 +1008,8 @@ int p2v_window_attention(const int8_t* qkv, int batch, int tokens_per_image, int
   if (!qkv || !wa || !out || !wa->table_codes || !wa->win_index) return fail(P2V_E_ARG, "p2v_window_attention: null argument");
   if (batch <= 0 || tokens_per_image <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad window attention shape");
   if (head_dim != 32) return fail(P2V_E_UNSUPPORTED, "window attention: head_dim must be 32");
-  if (wa->ws < 1 || wa->ws > 8 || wa->n_windows < 1 || wa->ws * wa->ws * wa->n_windows > tokens_per_image)
-    return fail(P2V_E_SHAPE, "window attention: window size must be 1..8 and windows must fit the token count");
+  if (wa->ws < 1 || wa->ws > 12 || wa->n_windows < 1 || wa->ws * wa->ws * wa->n_windows > tokens_per_image)
+    return fail(P2V_E_SHAPE, "window attention: window size must be 1..12 and windows must fit the token count");
   {
     const int rc = check_lis_consts("p2v_window_attention", wa->x0_int, wa->b_int, wa->c_int);
     if (rc != P2V_OK) return rc;

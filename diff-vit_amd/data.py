@@ -153,12 +153,12 @@ def model_family(model_name):
     return 'swin' if model_name.startswith('swin') else ('vit' if model_name.startswith('vit') else 'deit')
 
 
-def build_loaders(data_root, model_name, val_batchsize, calib_batchsize, num_workers=0, uint8=False):
+def build_loaders(data_root, model_name, val_batchsize, calib_batchsize, num_workers=0, uint8=False, input_size=224):
     """the reference's two loaders (test_quant.py:118-144): val (in order) and train (shuffled, drop_last; calibration batches).
     ``uint8``: the batches are the uint8 crops, NHWC [B, H, W, 3] (a quarter of the bytes to copy; ``forward_uint8`` normalises them on
-    the device with the family's MODEL_STATS)."""
+    the device with the family's MODEL_STATS).  ``input_size``: the crop the model takes (384 for the window-12 Swin factories)."""
     mean, std, crop_pct = MODEL_STATS[model_family(model_name)]
-    tf = build_transform(mean=mean, std=std, crop_pct=crop_pct, to_uint8=uint8)
+    tf = build_transform(input_size=input_size, mean=mean, std=std, crop_pct=crop_pct, to_uint8=uint8)
     val = torch.utils.data.DataLoader(ImageFolder(os.path.join(data_root, 'val'), tf), batch_size=val_batchsize, shuffle=False,
                                       num_workers=num_workers, pin_memory=torch.cuda.is_available())       # (test_quant.py:128: pin_memory=True)
     train_dir = os.path.join(data_root, 'train')

@@ -70,7 +70,8 @@ def str2model(name):
     d = {'deit_tiny': vit.deit_tiny_patch16_224, 'deit_small': vit.deit_small_patch16_224,
          'deit_base': vit.deit_base_patch16_224, 'vit_base': vit.vit_base_patch16_224,
          'vit_large': vit.vit_large_patch16_224, 'swin_tiny': swin.swin_tiny_patch4_window7_224,
-         'swin_small': swin.swin_small_patch4_window7_224, 'swin_base': swin.swin_base_patch4_window7_224}
+         'swin_small': swin.swin_small_patch4_window7_224, 'swin_base': swin.swin_base_patch4_window7_224,
+         'swin_base_384': swin.swin_base_patch4_window12_384, 'swin_large_384': swin.swin_large_patch4_window12_384}
     print('Model: %s' % name)
     return d[name]
 
@@ -366,7 +367,8 @@ def main(argv=None):
     if args.real_data:
         # test_quant.py:118-144: ImageFolder val / train trees with the model family's mean / std / crop
         from .data import build_loaders
-        loader, train_loader = build_loaders(args.data, args.model, args.val_batchsize, args.calib_batchsize, 0, uint8=args.uint8_input)
+        loader, train_loader = build_loaders(args.data, args.model, args.val_batchsize, args.calib_batchsize, 0, uint8=args.uint8_input,
+                                             input_size=arch['img_size'])
     else:
         # labels: the float model's own top-1 ("agreement with fp32"), the metric BASELINE.json names besides images/sec
         u8 = args.uint8_input

@@ -360,12 +360,12 @@ class SwinTransformer(nn.Module):
         return self.forward(expand_uint8(images, lut, layout), bits)
 
 
-def _factory(name, embed_dim, depths, num_heads, img_size=224):
+def _factory(name, embed_dim, depths, num_heads, img_size=224, window_size=7):
     def make(pretrained=False, quant=False, calibrate=False, cfg=None, **kwargs):
         if cfg is None:
             from .config import Config
             cfg = Config()
-        kw = dict(patch_size=4, window_size=7, embed_dim=embed_dim, depths=depths, num_heads=num_heads, img_size=img_size)
+        kw = dict(patch_size=4, window_size=window_size, embed_dim=embed_dim, depths=depths, num_heads=num_heads, img_size=img_size)
         kw.update(kwargs)
         model = SwinTransformer(norm_layer=QIntLayerNorm, quant=quant, calibrate=calibrate, input_quant=True, cfg=cfg, **kw)
         if pretrained:       # swin_quant.py:838-844: the checkpoint of the torch-hub cache (never fetched here: checkpoint.load_pretrained)
@@ -380,3 +380,8 @@ swin_tiny_patch4_window7_224 = _factory('swin_tiny_patch4_window7_224', 96, (2, 
 swin_small_patch4_window7_224 = _factory('swin_small_patch4_window7_224', 96, (2, 2, 18, 2), (3, 6, 12, 24))
 swin_base_patch4_window7_224 = _factory('swin_base_patch4_window7_224', 128, (2, 2, 18, 2), (4, 8, 16, 32))
 swin_micro_patch4_window7_56 = _factory('swin_micro_patch4_window7_56', 64, (2, 2), (2, 4), img_size=56)     # 14x14 -> 7x7 tokens: both shift/no-shift and one merge
+# patch 4 / window 12 / 384^2: feature maps of 96, 48, 24 and 12 tokens, 144-token windows (k_window_attention_wide).  pretrained=True: the
+# reference has no factory, hence no checkpoint file name, for these - checkpoint.load_pretrained raises the KeyError of any name outside PRETRAINED_FILES
+swin_base_patch4_window12_384 = _factory('swin_base_patch4_window12_384', 128, (2, 2, 18, 2), (4, 8, 16, 32), img_size=384, window_size=12)
+swin_large_patch4_window12_384 = _factory('swin_large_patch4_window12_384', 192, (2, 2, 18, 2), (6, 12, 24, 48), img_size=384, window_size=12)
+swin_micro_patch4_window12_96 = _factory('swin_micro_patch4_window12_96', 64, (2, 2), (2, 4), img_size=96, window_size=12)   # 24x24 (four shifted windows) -> 12x12 (one window)

@@ -53,7 +53,8 @@
  *       streaming - everything else up to 4096 tokens (other head dimensions beyond their resident limit, 1217 tokens and more, every launch
  *         with probs_k beyond the resident limit): re-reads K / V per query block (round 4: slow, exact, so that no geometry of the
  *         reference's VisionTransformer is refused);
- *     Swin window attention: head_dim 32, windows up to 8 x 8;
+ *     Swin window attention: head_dim 32, windows up to 12 x 12 (up to 8 x 8: one lane per token; 9 x 9 ... 12 x 12, the
+ *     patch 4 / window 12 / 384^2 geometry: the kernel of csrc/p2vit_winattn_wide.hip, same codes);
  *   - embed_dim and MLP width of a plan: multiples of 16 (round 4; before: 64) - the contractions walk 64-deep k-tiles through zero weight
  *     columns (p2v_linear: k_pad = round_up(K, 64)); the per-operator GEMM entry points take K in whole k-tiles;
  *   - LayerNorm: up to 2048 channels, PTF input masks (in_scale / min in_scale) in {1, 2, 4, 8};
@@ -429,7 +430,8 @@ int p2v_lis_attention_rows(const int8_t* qkv, int batch, int tokens, int heads, 
  * cyclic shift / reverse of SwinTransformerBlock.forward, swin_quant.py:366-391, folded into the addressing):
  *   (q*scale) @ k^T -> qact_attn1 -> + qact_table(relative_position_bias_table)[index] -> qact2 -> (+ -100 mask) ->
  *   QIntSoftmax(log-int, uint4, sf = qact2 scale) -> @ v -> qact3.
- * q*scale rounds each element once in fp32 and the dot product over head_dim is exact (fp64), then rounded once. */
+ * q*scale rounds each element once in fp32 and the dot product over head_dim is exact (fp64), then rounded once.
+ * Windows of ws x ws tokens, 1 <= ws <= 12: beyond 12 p2v_window_attention returns P2V_E_SHAPE. */
 typedef struct p2v_winattn {
   float s_q1;        /* qact1 scale (pot)                                        */
   float qk_scale;    /* head_dim^-0.5 (swin_quant.py:80)                         */
@@ -438,11 +440,11 @@ typedef struct p2v_winattn {
   float s_q2;        /* qact2 scale (pot) = the softmax scaling factor           */
   float s_q3;        /* qact3 scale (pot)                                        */
   int32_t x0_int, b_int, c_int; /* I-BERT constants for sf = s_q2 (layers.py:334-351) */
-  const int8_t* table_codes;    /* dev [(2*ws-1)^2][heads] codes of qact_table(relative_position_bias_table) */
+  const int8_t* table_codes;    /* dev [(2*ws-1)^2][heads] codes of qact_table(relative_position_bias_table); 529 rows at ws = 12 */
   const int32_t* win_index;     /* dev [n_windows][ws*ws]: row (within the image) of token p of window w after shift+partition */
   const int8_t* region;         /* dev [n_windows][ws*ws] shifted-window region ids, or NULL (no mask): pairs from different
                                  * regions get -100 (swin_quant.py:325-349)                                                   */
-  int32_t ws, n_windows;
+  int32_t ws, n_windows;        /* window side (1 .. 12) and windows per image; ws*ws*n_windows <= tokens_per_image */
   int32_t qkv_stride;           /* bytes between qkv rows (0 = dense: 3*heads*head_dim)                  */
   int32_t out_stride;           /* bytes between out rows (0 = dense: heads*head_dim); lets the next GEMM read K padded to 64.  The kernel writes
                                  * the heads*head_dim codes of a row and NEVER the padding behind them: it keeps the caller's bytes, which

@@ -1,4 +1,7 @@
-"""GPU: randomized parity of the per-operator entry points against the oracle over odd shapes and extreme parameters."""
+"""GPU: randomized parity of the per-operator entry points against the oracle over odd shapes and extreme parameters.
+python tools/fuzz_ops.py [SEED=0] [CASES=30] [--max-window W] [--only OP[,OP...]]
+--max-window W (default 8, up to 12): the Swin window sizes also cycle through 9 .. W (the kernel for 65 .. 144 keys); the default case
+stream is unchanged.  --only: run these operators' cases alone (ln, attn, gemm, winattn, ln_gemm), from a generator of their own."""
 import ctypes as C, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle'))
@@ -6,6 +9,19 @@ import diff_vit_amd as dva
 import p2vit_oracle as O
 E = dva.engine
 L = E.lib()
+MAX_WINDOW, ONLY = 8, None
+for flag in ('--max-window', '--only'):
+    if flag in sys.argv:
+        at = sys.argv.index(flag)
+        val = sys.argv[at + 1]
+        del sys.argv[at:at + 2]
+        if flag == '--max-window':
+            MAX_WINDOW = int(val)
+            assert 8 <= MAX_WINDOW <= 12, '--max-window takes 8 .. 12'
+        else:
+            ONLY = val.split(',')
+            assert set(ONLY) <= {'ln', 'attn', 'gemm', 'winattn', 'ln_gemm'}, ONLY
+WINDOWS = [7, 4, 8, 7, 2] + list(range(9, MAX_WINDOW + 1))
 g = torch.Generator().manual_seed(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 fails = 0
 stats = {'resid_tables': 0, 'resid_tables_usable': 0}
@@ -232,7 +248,7 @@ def gemm_case(i):
 def winattn_case(i):
     global fails
     import swin_oracle as SO
-    ws = [7, 4, 8, 7, 2][i % 5]
+    ws = WINDOWS[i % len(WINDOWS)]
     mult = int(torch.randint(1, 4, (1,), generator=g))
     Hf = ws * mult
     shift = 0 if (mult == 1 or i % 2 == 0) else int(torch.randint(1, ws, (1,), generator=g))
@@ -287,11 +303,9 @@ def winattn_case(i):
 
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 30
 for i in range(n):
-    ln_case(i)
-    attn_case(i)
-    gemm_case(i)
-    winattn_case(i)
-    ln_gemm_case(i)
+    for name, case in (('ln', ln_case), ('attn', attn_case), ('gemm', gemm_case), ('winattn', winattn_case), ('ln_gemm', ln_gemm_case)):
+        if ONLY is None or name in ONLY:
+            case(i)
 torch.cuda.synchronize()
 print('fuzz: %d cases per op, %d failing; pre-folded RESID tables certified %d of %d' % (n, fails, stats['resid_tables_usable'], stats['resid_tables']))
 sys.exit(1 if fails else 0)
