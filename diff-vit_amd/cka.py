@@ -7,12 +7,16 @@ DDV_CKA.py), on the fused engine.
     compute_cka(model1, model2, batches, bit_config1, bit_config2, normalize_act=False)           float vs quantized heat map
 
 On a fused model (``model_quant()`` state) ``get_activations`` makes ONE ``p2v_forward_linear_taps`` call: its forward hooks on
-QConv2d / QLinear are fed by the engine (``VisionTransformer._forward_hooked``).  Otherwise (float model, ``-1`` entries, dequant) the
+QConv2d / QLinear are fed by the engine (``VisionTransformer._forward_hooked``).  A Swin model is called with its own signature
+(``bit_config`` None, 8 or 4 = Swin's ``bits``; a list is refused): in quant state one ``SwinPlan.forward_linear_taps`` replay feeds the
+hooks (``SwinTransformer._forward_hooked``) with [B, tokens, N] outputs in natural token order - the module graph would give qkv / proj in
+window order, a permutation of an image's features that a Gram matrix does not see.  Otherwise (float model, ``-1`` entries, dequant) the
 module graph runs with the hooks, as in the reference.  The CKA classes send GPU activations through the HIP kernels
 (``torch.ops.p2vit.cka_grams`` / ``hsic_accumulate``: one grouped Gram launch sequence for all layers of an update) and CPU
 activations through ``gram_matrix``, a plain-torch restatement of the same formula.
 
-``python -m diff_vit_amd.cka --model deit_small --bits 8 --batch 50 --iters 2`` writes ``<result-name>/_heatmap.pkl`` (float vs
+``python -m diff_vit_amd.cka --model deit_small --bits 8 --batch 50 --iters 2`` (or ``--model swin_tiny``; ``--bits mixed`` is refused
+for Swin) writes ``<result-name>/_heatmap.pkl`` (float vs
 quantized on the synthetic data of ``harness``)."""
 import argparse
 import copy
@@ -35,6 +39,8 @@ def normalize_activations(act):
 def get_activations(images, model, bit_config, device, normalize_act=False, layer_indices=None):
     """cka_utility.py:26-113: the outputs of every QConv2d / QLinear (and, without a bit_config, Attention.qkv_output /
     Mlp.fc1_output) in named_modules order.  Returns the list, or (list, layer_info) when ``layer_indices`` is given."""
+    from .swin import SwinTransformer
+    is_swin = isinstance(model, SwinTransformer)
     model = model.to(device)
     activations, layer_info, hooks = [], [], []
 
@@ -44,19 +50,28 @@ def get_activations(images, model, bit_config, device, normalize_act=False, laye
                 activations.append(module.qkv_output)
             elif isinstance(module, Mlp):
                 activations.append(module.fc1_output)
+            elif is_swin and output.dim() == 3 and output.shape[0] != images.shape[0]:
+                # the window modules of the module graph run on [B * nW, ws * ws, N], image-major: one row of features per image again
+                activations.append(output.reshape(images.shape[0], -1, output.shape[-1]))
             else:
                 activations.append(output)
             layer_info.append({'relative_index': len(layer_info), 'absolute_index': index, 'name': name, 'layer_type': type(module),
                                'path': '%s.%s' % (type(module).__module__, type(module).__name__)})
         return hook
 
-    kinds = (QConv2d, QLinear, Attention, Mlp) if bit_config is None else (QConv2d, QLinear)
+    if is_swin and isinstance(bit_config, (list, tuple)):
+        raise NotImplementedError('get_activations: a Swin model has one weight width and no per-layer bit_config list; pass 8, 4 or None')
+    # (a Swin has no Attention / Mlp taps: its float pass calls every QLinear as a module, so the hooks on them fire)
+    kinds = (QConv2d, QLinear, Attention, Mlp) if bit_config is None and not is_swin else (QConv2d, QLinear)
     for index, (name, layer) in enumerate(model.named_modules()):
         if type(layer) in kinds:
             hooks.append(layer.register_forward_hook(hook_return(index, name)))
     try:
         with torch.no_grad():
-            model(images.to(device), bit_config=bit_config, plot=False)
+            if is_swin:                                  # SwinTransformer.forward(x, bits): 8 when no width is named
+                model(images.to(device), bits=8 if bit_config is None else int(bit_config))
+            else:
+                model(images.to(device), bit_config=bit_config, plot=False)
     finally:
         for h in hooks:
             h.remove()
@@ -199,12 +214,21 @@ def main(argv=None):
     args = p.parse_args(argv)
     device = torch.device(args.device)
     fp = harness.str2model(args.model)(cfg=Config(True, True, 'minmax'))
-    fp.load_state_dict(synth.vit_state_dict(fp.arch, args.seed), strict=False)
+    is_swin = harness._is_swin(fp)
+    if is_swin:
+        if args.bits == 'mixed':
+            raise NotImplementedError('--bits mixed: a Swin model has one weight width (swin_quant.py:813-817)')
+        fp.load_state_dict(synth.swin_state_dict(fp.state_dict(), args.seed))
+    else:
+        fp.load_state_dict(synth.vit_state_dict(fp.arch, args.seed), strict=False)
     fp = fp.to(device).eval()
     q = copy.deepcopy(fp)
     harness.calibrate_model(q, synth.images(args.seed + 1, 10, fp.arch['img_size']).to(device))
-    L = 4 * fp.depth + 2
-    bits = {'8': [8] * L, '4': [4] * L, 'mixed': [8 if (i * 7 + 3) % 5 < 3 else 4 for i in range(L)]}[args.bits]
+    if is_swin:
+        bits = int(args.bits)
+    else:
+        L = 4 * fp.depth + 2
+        bits = {'8': [8] * L, '4': [4] * L, 'mixed': [8 if (i * 7 + 3) % 5 < 3 else 4 for i in range(L)]}[args.bits]
     loader = harness.SyntheticLoader(args.batch * args.iters, args.batch, fp.arch['img_size'], fp.arch['num_classes'], args.seed + 2, device)
     heatmap = compute_cka(fp, q, loader, None, bits).cpu().numpy()
     os.makedirs(args.result_name, exist_ok=True)

@@ -523,7 +523,7 @@ static GemmArgs gemm_args(const int8_t* A, int lda, int M, const int8_t* W, int 
 static int run_gemm(int epi, const int8_t* A, int lda, int M, int K, int N, const p2v_linear& lin, const p2v_epilogue& ep, void* out,
                     int ldo, int8_t* out_codes, hipStream_t st, bool few_rows = false) {
   const GemmArgs g = gemm_args(A, lda, M, lin.w_codes, K, N, lin, ep, out, ldo, out_codes);
-  if (few_rows && g_gemm_rows != 2 && g_gemm_tile == 0) return launch_rc(p2v_launch_gemm_rows(epi, g, st), "gemm_rows");
+  if (few_rows && g_gemm_rows != 2 && g_gemm_tile == 0 && !(epi == P2V_EPI_RESID && out_codes)) return launch_rc(p2v_launch_gemm_rows(epi, g, st), "gemm_rows");
   return launch_rc(p2v_launch_gemm(epi, g, st), "gemm_i8");
 }
 
@@ -898,6 +898,11 @@ int p2v_gemm_i8(int kind, const int8_t* A, int lda, int M, int K, int N, const p
   if (kind == P2V_EPI_GELU && check_gelu_tab("p2v_gemm_i8", epi->gelu) != P2V_OK) return P2V_E_ARG;
   if (kind == P2V_EPI_RESID && (!epi->s_mid || !epi->s_res || !epi->s_next || !epi->residual)) return fail(P2V_E_ARG, "RESID epilogue needs s_mid/s_res/s_next/residual");
   if (kind == P2V_EPI_EMBED && (!epi->s_next || !epi->pos_deq || epi->patches <= 0)) return fail(P2V_E_ARG, "EMBED epilogue needs s_next/pos_deq/patches");
+  if (kind == P2V_EPI_RESID && out_codes) {      // the mid-code tap: 16-byte stores like `out`, int8-stored weights
+    if ((uintptr_t)out_codes % 16 || (uintptr_t)out % 16) return fail(P2V_E_ARG, "p2v_gemm_i8: RESID out_codes and out must be 16-byte aligned");
+    if (lin->packed4) return fail(P2V_E_UNSUPPORTED, "p2v_gemm_i8: the RESID mid-code tap takes int8-stored weights (packed4 = 0)");
+  }
+  if (kind != P2V_EPI_RESID && kind != P2V_EPI_HEAD) out_codes = nullptr;
   return run_gemm(kind, A, lda, M, K, N, *lin, *epi, out, ldo, out_codes, (hipStream_t)stream);
 }
 
@@ -1029,12 +1034,51 @@ int p2v_window_attention(const int8_t* qkv, int batch, int tokens_per_image, int
   return launch_rc(p2v_launch_window_attention(a, (hipStream_t)stream), "window_attention");
 }
 
+// the layer output fmaf(acc, colscale, bias) as dense fp32 (P2V_OP_GEMM_F32): what a QLinear / QConv2d hook sees.  The public p2v_gemm_i8
+// goes on refusing the internal epilogue kind.
+static int gemm_f32_op(const p2v_op& o, void* stream) {
+  if (!o.in || !o.out || !o.lin.w_codes || !o.lin.colscale || !o.lin.bias) return fail(P2V_E_ARG, "P2V_OP_GEMM_F32: null argument");
+  if (o.M <= 0 || o.N <= 0 || o.K <= 0 || o.K % GBK_PAD) return fail(P2V_E_SHAPE, "P2V_OP_GEMM_F32: K=%d must be a positive multiple of %d", o.K, GBK_PAD);
+  if (o.lda <= 0 || o.lda % 16) return fail(P2V_E_UNSUPPORTED, "P2V_OP_GEMM_F32: lda must be a positive multiple of 16");
+  if (o.ldo < o.N || (o.ldo != o.N && o.ldo % 4)) return fail(P2V_E_SHAPE, "P2V_OP_GEMM_F32: ldo=%d must be N=%d, or a multiple of 4 beyond it", o.ldo, o.N);
+  if ((uintptr_t)o.in % 16 || (uintptr_t)o.out % 16) return fail(P2V_E_ARG, "P2V_OP_GEMM_F32: in and out must be 16-byte aligned");
+  return run_gemm(P2V_EPI_F32, (const int8_t*)o.in, o.lda, o.M, o.K, o.N, o.lin, p2v_epilogue{}, o.out, o.ldo, nullptr, (hipStream_t)stream);
+}
+static int cos_check(const p2v_cos_layer* layers, int n_layers, int n, const char* what);
+static p2v_cos_layer cos_op_layer(const p2v_op& o) {
+  const long long sample = (long long)(((unsigned long long)(unsigned)o.i3 << 32) | (unsigned)o.i2);
+  const size_t esz = o.i1 == P2V_COS_I8 ? 1 : 4;
+  const char* a = reinterpret_cast<const char*>(o.in);
+  return p2v_cos_layer{a, a ? a + (size_t)(o.i0 > 0 ? o.i0 : 0) * (size_t)(sample > 0 ? sample : 0) * esz : nullptr, o.lin.colscale, sample, o.lda, o.M, o.N, o.i1};
+}
+// one DDV stage of a recorded sequence: every refusal comes before the launch
+static int cos_op(const p2v_op& o, void* stream) {
+  if (!o.in || !o.out || !o.lin.w_codes) return fail(P2V_E_ARG, "P2V_OP_COS: null buffer, partials or stage record");
+  if ((uintptr_t)o.out % 8 || (uintptr_t)o.lin.w_codes % 8) return fail(P2V_E_ARG, "P2V_OP_COS: partials and stage record must be 8-byte aligned");
+  const p2v_cos_layer l = cos_op_layer(o);
+  const int rc = cos_check(&l, 1, o.i0, "P2V_OP_COS");
+  if (rc != P2V_OK) return rc;
+  const CosDesc d = p2v_cos_desc(l, o.i0, 0);
+  return launch_rc(p2v_launch_cos_stage(reinterpret_cast<const CosDesc*>(o.lin.w_codes), (long long)o.i0 * d.nsplit,
+                                        reinterpret_cast<unsigned long long*>(o.out), (hipStream_t)stream), "cos_stage");
+}
+static int cos_combine_op(const p2v_op& o, void* stream) {
+  if (!o.in || !o.out || !o.lin.w_codes) return fail(P2V_E_ARG, "P2V_OP_COS_COMBINE: null stage table, sums or partials");
+  if (o.i1 < 1) return fail(P2V_E_ARG, "P2V_OP_COS_COMBINE: a combine without stages (%d)", o.i1);
+  if (o.i0 < 1) return fail(P2V_E_SHAPE, "P2V_OP_COS_COMBINE: n = %d samples", o.i0);
+  if ((uintptr_t)o.in % 8 || (uintptr_t)o.out % 8 || (uintptr_t)o.lin.w_codes % 8) return fail(P2V_E_ARG, "P2V_OP_COS_COMBINE: pointers must be 8-byte aligned");
+  return launch_rc(p2v_launch_cos_combine(reinterpret_cast<const CosDesc*>(o.in), o.i1, o.i0, reinterpret_cast<const unsigned long long*>(o.lin.w_codes),
+                                          reinterpret_cast<double*>(o.out), (hipStream_t)stream), "cos_combine");
+}
+
 static int run_one_op(const p2v_op& o, void* stream) {
   switch (o.kind) {
     case P2V_OP_PATCHIFY:
       return p2v_quantize_patchify((const float*)o.in, o.i0, o.i1, o.i2, o.i3, o.i4, o.f0, (int8_t*)o.out, o.i5, stream);
     case P2V_OP_GEMM:
-      return p2v_gemm_i8(o.epi, (const int8_t*)o.in, o.lda, o.M, o.K, o.N, &o.lin, &o.ep, o.out, o.ldo, nullptr, stream);
+      // REQUANT / GELU: ep.tap_out (fp32 layer output) goes through with the epilogue; RESID: the same member names the int8 mid codes
+      return p2v_gemm_i8(o.epi, (const int8_t*)o.in, o.lda, o.M, o.K, o.N, &o.lin, &o.ep, o.out, o.ldo,
+                         o.epi == P2V_EPI_RESID ? reinterpret_cast<int8_t*>(o.ep.tap_out) : nullptr, stream);
     case P2V_OP_LAYERNORM:
       return p2v_int_layernorm((const int8_t*)o.in, o.lda, o.M, o.N, &o.ln, (int8_t*)o.out, o.ldo, stream);
     case P2V_OP_WINATTN:
@@ -1045,6 +1089,12 @@ static int run_one_op(const p2v_op& o, void* stream) {
       return p2v_avgpool_quant((const int8_t*)o.in, o.i0, o.i1, o.i2, o.f0, o.f1, (int8_t*)o.out, stream);
     case P2V_OP_LN_GEMM:
       return p2v_ln_gemm_i8(o.epi, (const int8_t*)o.in, o.lda, o.M, o.K, &o.ln, o.N, &o.lin, &o.ep, (int8_t*)o.out, o.ldo, nullptr, stream);
+    case P2V_OP_COS:
+      return cos_op(o, stream);
+    case P2V_OP_COS_COMBINE:
+      return cos_combine_op(o, stream);
+    case P2V_OP_GEMM_F32:
+      return gemm_f32_op(o, stream);
     default:
       return fail(P2V_E_ARG, "p2v_run_ops: unknown op kind %d", o.kind);
   }
@@ -1231,6 +1281,21 @@ int p2v_pair_cosine(const p2v_cos_layer* layers, int n_layers, int n, double* su
   if (ws_bytes < w.total) return fail(P2V_E_WORKSPACE, "p2v_pair_cosine: workspace %zu < %zu bytes", ws_bytes, w.total);
   if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_pair_cosine: the workspace must be 256-byte aligned");
   return launch_rc(p2v_launch_pair_cosine(descs, w, n, sums, ws, (hipStream_t)stream), "pair_cosine");
+}
+
+// stage records of a recorded DDV sequence (P2V_OP_COS / P2V_OP_COS_COMBINE): built once on the host, uploaded by the caller
+size_t p2v_cos_stage_desc_bytes(void) { return sizeof(CosDesc); }
+
+long long p2v_cos_stage_descs(const p2v_cos_layer* layers, int n_layers, int n, void* host_descs) {
+  const int rc = cos_check(layers, n_layers, n, "p2v_cos_stage_descs");
+  if (rc != P2V_OK) return rc;
+  if (!host_descs) return fail(P2V_E_ARG, "p2v_cos_stage_descs: null output");
+  std::vector<CosDesc> descs;
+  descs.reserve(n_layers);
+  const CosLayout w = p2v_cos_layout(layers, n_layers, n, &descs);
+  if (w.items >= (1LL << 31)) return fail(P2V_E_UNSUPPORTED, "p2v_cos_stage_descs: %lld partials", w.items);
+  memcpy(host_descs, descs.data(), descs.size() * sizeof(CosDesc));
+  return w.items;
 }
 
 // ---- scoring of the logits (p2vit_score.hip) -------------------------------------------------------------------------------------------

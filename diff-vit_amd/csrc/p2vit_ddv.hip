@@ -195,6 +195,13 @@ __global__ __launch_bounds__(256) void k_cos_combine_one(const CosDesc d, int n,
   cos_combine_body(d, idx, partials, sums + (long long)idx * 3);
 }
 
+// one stage of a recorded sequence (P2V_OP_COS): its record sits in a device table that the closing k_cos_combine walks; the stage's workgroups
+// write the partial slots [item0, item0 + n * nsplit) of that table's numbering
+__global__ __launch_bounds__(256) void k_cos_partial_stage(const CosDesc* __restrict__ desc, unsigned long long* __restrict__ partials) {
+  const CosDesc d = *desc;
+  cos_partial_body(d, blockIdx.x, partials + (d.item0 + (long long)blockIdx.x) * 3);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // host side (argument validation in p2vit_capi.cpp)
 // ---------------------------------------------------------------------------------------------------
@@ -256,6 +263,20 @@ int p2v_launch_pair_cosine_one(const CosDesc& d, int n, unsigned long long* part
   hipLaunchKernelGGL(k_cos_partial_one, dim3((unsigned)(n * d.nsplit)), dim3(256), 0, st, d, partials);
   CHECK_LAUNCH();
   hipLaunchKernelGGL(k_cos_combine_one, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d, n, partials, sums);
+  CHECK_LAUNCH();
+  return 0;
+}
+
+// P2V_OP_COS: the stage whose record is *desc_dev (items = n * nsplit of that record); P2V_OP_COS_COMBINE: every stage of the table at once
+int p2v_launch_cos_stage(const CosDesc* desc_dev, long long items, unsigned long long* partials, hipStream_t st) {
+  if (items < 1 || items >= (1LL << 31)) return -1;
+  hipLaunchKernelGGL(k_cos_partial_stage, dim3((unsigned)items), dim3(256), 0, st, desc_dev, partials);
+  CHECK_LAUNCH();
+  return 0;
+}
+int p2v_launch_cos_combine(const CosDesc* descs_dev, int L, int n, const unsigned long long* partials, double* sums, hipStream_t st) {
+  if ((long long)L * n >= (1LL << 31)) return -1;
+  hipLaunchKernelGGL(k_cos_combine, dim3((unsigned)(((long long)L * n + 255) / 256)), dim3(256), 0, st, descs_dev, L, n, partials, sums);
   CHECK_LAUNCH();
   return 0;
 }

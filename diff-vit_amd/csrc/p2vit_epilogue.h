@@ -16,6 +16,7 @@
 #define GBK 64
 #define P2V_EPI_GELU_TAB 5   // internal: P2V_EPI_GELU with a threshold table in LDS (p2v_epilogue.gelu.table != NULL)
 #define P2V_EPI_RESID_PRE 6  // internal: P2V_EPI_RESID with the constants of p2v_resid_prefold (p2v_epilogue.resid_tab != NULL)
+#define P2V_EPI_RESID_TAP 8  // internal: P2V_EPI_RESID that also stores the mid codes q3 (GemmArgs.out_codes != NULL); 7 is P2V_EPI_F32
 
 __device__ __forceinline__ int lds_off64(int row, int chunk) { return row * GBK + ((chunk ^ ((row >> 2) & 3)) << 4); }
 
@@ -141,11 +142,17 @@ __device__ __forceinline__ void gemm_epilogue_tile(const v16i& acc, int m, int n
 // (half the LDS reads and half the exposed read latencies of two gemm_epilogue_tile calls).  REQUANT / GELU / GELU_TAB / RESID.
 // LEAN: no look-ahead of the per-channel constants (24 registers in the RESID form): the 8-wave 256-row tile must stay within 128
 // VGPRs and has four waves per SIMD to cover the LDS round trip instead
-template <int EPI, bool LEAN = false>
+// TAP (RESID only): the codes of the QAct between the layer and the residual add, q3 = clamp(round((acc * colscale + bias) / s_mid)) - the
+// first rounding of the chain, taken from the registers that feed the second - also go to g.out_codes [M][ldo], through the same
+// half-swap into one 16-byte store per lane as the result.  The generic chain only: with a resid_tab the launcher still takes this
+// form for a tapped launch (both forms give the same codes: that is what the table's plan-time check proves).
+template <int EPI, bool LEAN = false, bool TAP = false>
 __device__ __forceinline__ void gemm_epilogue_tile2(const v16i (&acc)[2], int m_first, int n_tile, int nl, int h, const GemmArgs& g,
                                                     const EpiLds* e, const uint4 (&resv)[2], const unsigned char* gtab = nullptr) {
   static_assert(EPI == P2V_EPI_REQUANT || EPI == P2V_EPI_GELU || EPI == P2V_EPI_GELU_TAB || EPI == P2V_EPI_RESID, "row-pair epilogue");
+  static_assert(!TAP || EPI == P2V_EPI_RESID, "the mid-code tap belongs to RESID");
   unsigned d[2][4], res[2][4];
+  unsigned mid[2][TAP ? 4 : 1];
   const bool row_ok[2] = {m_first < g.M, m_first + 32 < g.M};
   if (EPI == P2V_EPI_RESID) {
     row16_to_halves(resv[0], res[0][0], res[0][1], res[0][2], res[0][3]);
@@ -166,72 +173,89 @@ __device__ __forceinline__ void gemm_epilogue_tile2(const v16i (&acc)[2], int m_
     }
     return k;
   };
-  Consts knext;
-  if (!LEAN) knext = load_consts(0);
+  // TAP: one 32-row block at a time (the constants are read once per block instead of once per pair), so that the packed mid codes of a
+  // block - four more dwords next to its result - are stored before the other block's are formed: the 8-wave tile stays within 128 VGPRs
+  constexpr int NPASS = TAP ? 2 : 1;
 #pragma unroll
-  for (int gq = 0; gq < 4; ++gq) {
-    const int n = n_tile + 8 * gq + 4 * h;
-    const Consts k = LEAN ? load_consts(gq) : knext;
-    if (!LEAN && gq < 3) knext = load_consts(gq + 1);
-    const float4 cs = k.cs, bs = k.bs;
-    float smv[4], srv[4], snv[4], rmv[4], rnv[4], mrv[4];
-    if (EPI == P2V_EPI_RESID) {
-      smv[0] = k.sm.x; smv[1] = k.sm.y; smv[2] = k.sm.z; smv[3] = k.sm.w;
-      srv[0] = k.sr.x; srv[1] = k.sr.y; srv[2] = k.sr.z; srv[3] = k.sr.w;
-      snv[0] = k.sn.x; snv[1] = k.sn.y; snv[2] = k.sn.z; snv[3] = k.sn.w;
-      rmv[0] = k.rm.x; rmv[1] = k.rm.y; rmv[2] = k.rm.z; rmv[3] = k.rm.w;
-      rnv[0] = k.rn.x; rnv[1] = k.rn.y; rnv[2] = k.rn.z; rnv[3] = k.rn.w;
-      if (LEAN) {           // -128 * s_res on the fly (exact): four registers less
+  for (int pass = 0; pass < NPASS; ++pass) {
+    const int b0 = TAP ? pass : 0, b1 = TAP ? pass + 1 : 2;
+    Consts knext;
+    if (!LEAN) knext = load_consts(0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) mrv[i] = -128.f * srv[i];
-      } else {
-        mrv[0] = k.mr.x; mrv[1] = k.mr.y; mrv[2] = k.mr.z; mrv[3] = k.mr.w;
+    for (int gq = 0; gq < 4; ++gq) {
+      const int n = n_tile + 8 * gq + 4 * h;
+      const Consts k = LEAN ? load_consts(gq) : knext;
+      if (!LEAN && gq < 3) knext = load_consts(gq + 1);
+      const float4 cs = k.cs, bs = k.bs;
+      float smv[4], srv[4], snv[4], rmv[4], rnv[4], mrv[4];
+      if (EPI == P2V_EPI_RESID) {
+        smv[0] = k.sm.x; smv[1] = k.sm.y; smv[2] = k.sm.z; smv[3] = k.sm.w;
+        srv[0] = k.sr.x; srv[1] = k.sr.y; srv[2] = k.sr.z; srv[3] = k.sr.w;
+        snv[0] = k.sn.x; snv[1] = k.sn.y; snv[2] = k.sn.z; snv[3] = k.sn.w;
+        rmv[0] = k.rm.x; rmv[1] = k.rm.y; rmv[2] = k.rm.z; rmv[3] = k.rm.w;
+        rnv[0] = k.rn.x; rnv[1] = k.rn.y; rnv[2] = k.rn.z; rnv[3] = k.rn.w;
+        if (LEAN) {           // -128 * s_res on the fly (exact): four registers less
+#pragma unroll
+          for (int i = 0; i < 4; ++i) mrv[i] = -128.f * srv[i];
+        } else {
+          mrv[0] = k.mr.x; mrv[1] = k.mr.y; mrv[2] = k.mr.z; mrv[3] = k.mr.w;
+        }
       }
-    }
-    float yy[2][4];
+      float yy[2][4];
 #pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      yy[b][0] = __builtin_fmaf((float)acc[b][4 * gq + 0], cs.x, bs.x);      // one rounding, see gemm_epilogue_tile
-      yy[b][1] = __builtin_fmaf((float)acc[b][4 * gq + 1], cs.y, bs.y);
-      yy[b][2] = __builtin_fmaf((float)acc[b][4 * gq + 2], cs.z, bs.z);
-      yy[b][3] = __builtin_fmaf((float)acc[b][4 * gq + 3], cs.w, bs.w);
-      if (EPI != P2V_EPI_RESID && g.ep.tap_out && row_ok[b] && n < g.N) {
-        const float un = EPI == P2V_EPI_REQUANT ? 1.0f / g.ep.inv_s_out : (EPI == P2V_EPI_GELU_TAB ? 1.0f / g.ep.gelu.k : 1.0f);
-        *reinterpret_cast<float4*>(g.ep.tap_out + (long long)(m_first + 32 * b) * g.N + n) =
-            make_float4(yy[b][0] * un, yy[b][1] * un, yy[b][2] * un, yy[b][3] * un);
+      for (int b = b0; b < b1; ++b) {
+        yy[b][0] = __builtin_fmaf((float)acc[b][4 * gq + 0], cs.x, bs.x);      // one rounding, see gemm_epilogue_tile
+        yy[b][1] = __builtin_fmaf((float)acc[b][4 * gq + 1], cs.y, bs.y);
+        yy[b][2] = __builtin_fmaf((float)acc[b][4 * gq + 2], cs.z, bs.z);
+        yy[b][3] = __builtin_fmaf((float)acc[b][4 * gq + 3], cs.w, bs.w);
+        if (EPI != P2V_EPI_RESID && g.ep.tap_out && row_ok[b] && n < g.N) {
+          const float un = EPI == P2V_EPI_REQUANT ? 1.0f / g.ep.inv_s_out : (EPI == P2V_EPI_GELU_TAB ? 1.0f / g.ep.gelu.k : 1.0f);
+          *reinterpret_cast<float4*>(g.ep.tap_out + (long long)(m_first + 32 * b) * g.N + n) =
+              make_float4(yy[b][0] * un, yy[b][1] * un, yy[b][2] * un, yy[b][3] * un);
+        }
       }
-    }
-    if (EPI == P2V_EPI_GELU_TAB) {
-      const int goff = (int)g.ep.gelu.off;
-      gelu_tab_q8x8(yy[0], yy[1], gtab + goff * 8, (float)-goff, (float)(g.ep.gelu.cells - 1 - goff) + 0.5f, d[0][gq], d[1][gq]);
-      continue;
-    }
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const float (&y)[4] = yy[b];
-      float q[4];
-      if (EPI == P2V_EPI_REQUANT) {
-        d[b][gq] = pack4_rne_sat(y[0], y[1], y[2], y[3]);
+      if (EPI == P2V_EPI_GELU_TAB) {
+        const int goff = (int)g.ep.gelu.off;
+        gelu_tab_q8x8(yy[0], yy[1], gtab + goff * 8, (float)-goff, (float)(g.ep.gelu.cells - 1 - goff) + 0.5f, d[0][gq], d[1][gq]);
         continue;
-      } else if (EPI == P2V_EPI_GELU) {
-        gelu_q8x4(y, g.ep.inv_s_out, q);
-      } else {   // RESID, see gemm_epilogue_tile
-        float q3[4], xs[4];
-        div_q8fx4<true>(y, smv, rmv, q3);
-        const unsigned ru = res[b][gq] ^ 0x80808080u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xs[i] = __builtin_fmaf((float)((ru >> (8 * i)) & 255u), srv[i], mrv[i]) + q3[i] * smv[i];
-        div_q8fx4<false>(xs, snv, rnv, q);
       }
-      d[b][gq] = pack4_sat(q[0], q[1], q[2], q[3]);
-    }
-    if (EPI == P2V_EPI_RESID) __builtin_amdgcn_sched_barrier(0);   // keep the constant reads of the next group from being hoisted (register pressure)
-  }
 #pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const uint4 o = halves_to_row16(d[b][0], d[b][1], d[b][2], d[b][3]);
-    if (row_ok[b] && n_tile + 16 * h < g.N)
-      *reinterpret_cast<uint4*>(reinterpret_cast<int8_t*>(g.out) + (long long)(m_first + 32 * b) * g.ldo + n_tile + 16 * h) = o;
+      for (int b = b0; b < b1; ++b) {
+        const float (&y)[4] = yy[b];
+        float q[4];
+        if (EPI == P2V_EPI_REQUANT) {
+          d[b][gq] = pack4_rne_sat(y[0], y[1], y[2], y[3]);
+          continue;
+        } else if (EPI == P2V_EPI_GELU) {
+          gelu_q8x4(y, g.ep.inv_s_out, q);
+        } else {   // RESID, see gemm_epilogue_tile
+          float q3[4], xs[4];
+          div_q8fx4<true>(y, smv, rmv, q3);
+          if constexpr (TAP) mid[b][gq] = pack4_sat(q3[0], q3[1], q3[2], q3[3]);
+          const unsigned ru = res[b][gq] ^ 0x80808080u;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) xs[i] = __builtin_fmaf((float)((ru >> (8 * i)) & 255u), srv[i], mrv[i]) + q3[i] * smv[i];
+          div_q8fx4<false>(xs, snv, rnv, q);
+        }
+        d[b][gq] = pack4_sat(q[0], q[1], q[2], q[3]);
+      }
+      if (EPI == P2V_EPI_RESID) __builtin_amdgcn_sched_barrier(0);   // keep the constant reads of the next group from being hoisted (register pressure)
+    }
+#pragma unroll
+    for (int b = b0; b < b1; ++b) {
+      const uint4 o = halves_to_row16(d[b][0], d[b][1], d[b][2], d[b][3]);
+      if constexpr (TAP) {
+        // both stores at base + one 32-bit lane offset (the launcher checks M * ldo < 2^32): no 64-bit address pair per row and output
+        const uint4 t = halves_to_row16(mid[b][0], mid[b][1], mid[b][2], mid[b][3]);
+        const unsigned off = (unsigned)(m_first + 32 * b) * (unsigned)g.ldo + (unsigned)(n_tile + 16 * h);
+        if (row_ok[b] && n_tile + 16 * h < g.N) {
+          *reinterpret_cast<uint4*>(reinterpret_cast<int8_t*>(g.out) + off) = o;
+          *reinterpret_cast<uint4*>(g.out_codes + off) = t;
+        }
+      } else if (row_ok[b] && n_tile + 16 * h < g.N) {
+        *reinterpret_cast<uint4*>(reinterpret_cast<int8_t*>(g.out) + (long long)(m_first + 32 * b) * g.ldo + n_tile + 16 * h) = o;
+      }
+    }
   }
 }
 

@@ -343,8 +343,12 @@ __device__ __forceinline__ void gemm_compute_tile_dma(unsigned aX0, unsigned aX1
 #else
 #define GD_STAMP(slot) do { } while (0)
 #endif
-template <int EPI, bool W4, int MT>
+// EPI_ = P2V_EPI_RESID_TAP: the RESID kernel with the mid-code tap of gemm_epilogue_tile2 (int8-stored weights only)
+template <int EPI_, bool W4, int MT>
 __global__ __launch_bounds__(128 * MT, MT == 4 ? 4 : 3) void k_gemm_dma(GemmArgs g) {
+  constexpr bool TAP = EPI_ == P2V_EPI_RESID_TAP;
+  constexpr int EPI = TAP ? P2V_EPI_RESID : EPI_;
+  static_assert(!(TAP && W4), "the mid-code tap is instantiated for int8-stored weights");
   constexpr int NST = 3;                                         // stages of the LDS-DMA ring
   constexpr int TBM = 64 * MT;                                   // tile rows
   constexpr int NTH = 128 * MT;                                  // threads
@@ -434,7 +438,11 @@ __global__ __launch_bounds__(128 * MT, MT == 4 ? 4 : 3) void k_gemm_dma(GemmArgs
     for (int mi = 0; mi < 2; ++mi) {
       const int m = m0 + wm * 64 + mi * 32 + l31, n = n0 + wn * 64 + ni * 32 + 16 * h;
       resv[ni][mi] = make_uint4(0, 0, 0, 0);
-      if (m < g.M && n < g.N) resv[ni][mi] = *reinterpret_cast<const uint4*>(g.ep.residual + (long long)m * g.ldo + n);
+      if constexpr (TAP) {      // base + 32-bit lane offset, like the tapped epilogue's stores (no address pairs held across the column groups)
+        unsigned row = (unsigned)m;
+        asm volatile("" : "+v"(row));         // formed again for each column group: a row offset kept across the first group's epilogue spills
+        if (m < g.M && n < g.N) resv[ni][mi] = *reinterpret_cast<const uint4*>(g.ep.residual + (row * (unsigned)g.ldo + (unsigned)n));
+      } else if (m < g.M && n < g.N) resv[ni][mi] = *reinterpret_cast<const uint4*>(g.ep.residual + (long long)m * g.ldo + n);
     }
   };
   if (RES && MT == 2) {
@@ -487,7 +495,7 @@ __global__ __launch_bounds__(128 * MT, MT == 4 ? 4 : 3) void k_gemm_dma(GemmArgs
       gemm_epilogue_resid_pre<MT == 4>(acc[ni], m0 + wm * 64 + l31, n0 + wn * 64 + ni * 32, wn * 64 + ni * 32, h, g,
                                        reinterpret_cast<const ResidLds*>(sE), resv[ni]);
     else
-      gemm_epilogue_tile2<EPI, (MT == 4 && EPI == P2V_EPI_RESID)>(acc[ni], m0 + wm * 64 + l31, n0 + wn * 64 + ni * 32, wn * 64 + ni * 32, h, g, sE,
+      gemm_epilogue_tile2<EPI, ((MT == 4 || TAP) && EPI == P2V_EPI_RESID), TAP>(acc[ni], m0 + wm * 64 + l31, n0 + wn * 64 + ni * 32, wn * 64 + ni * 32, h, g, sE,
                                                                    resv[ni], dyn_lds);
   }
   GD_STAMP(4);
@@ -552,7 +560,7 @@ int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
   g.tiles_n = (g.N + GBN - 1) / GBN;
   if (epi != P2V_EPI_HEAD && epi != P2V_EPI_EMBED && epi != P2V_EPI_F32) {
     // "gemm_rows" = 1: the few-rows kernel wherever it applies (parity runs against this kernel); an explicit tile height means this kernel
-    if (g_gemm_rows == 1 && g_gemm_tile == 0) return p2v_launch_gemm_rows(epi, g0, st);
+    if (g_gemm_rows == 1 && g_gemm_tile == 0 && !(epi == P2V_EPI_RESID && g.out_codes)) return p2v_launch_gemm_rows(epi, g0, st);
     // the tiled kernel addresses both matrices with 32-bit lane offsets
     if ((long long)g.M * g.lda + g.K >= (1LL << 32) || (long long)g.tiles_n * GBN * g.K >= (1LL << 32)) return -1;
     // 256-row tiles (8 waves, two workgroups per CU) when the grid still gives every CU its two workgroups; else 128-row tiles
@@ -592,11 +600,18 @@ int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
 #define P2V_K_DMA3P(E) (k_gemm_dma<E, true, 2>)
 #define P2V_K_DMA3L(E) (k_gemm_dma<E, false, 4>)
 #define P2V_K_DMA3PL(E) (k_gemm_dma<E, true, 4>)
+    if (epi == P2V_EPI_RESID && g.out_codes) {
+      // the mid-code tap: the generic RESID chain whatever resid_tab says (same codes); int8-stored weights, tiled kernel only
+      if (g.w4 || (long long)g.M * g.ldo >= (1LL << 32)) return -1;
+      if (big) hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, false, 4>), grid4, block4, 0, st, g);
+      else hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, false, 2>), grid4, block4, 0, st, g);
+    } else {
     if (big) {
       if (g.w4) { P2V_LAUNCH_TILED(P2V_K_DMA3PL) }
       else { P2V_LAUNCH_TILED(P2V_K_DMA3L) }
     } else if (g.w4) { P2V_LAUNCH_TILED(P2V_K_DMA3P) }          // packed int4 weights: the LDS-DMA kernel only
     else { P2V_LAUNCH_TILED(P2V_K_DMA3) }
+    }
 #undef P2V_LAUNCH_TILED
     CHECK_LAUNCH();
     return 0;

@@ -143,6 +143,9 @@ CosDesc p2v_cos_desc(const p2v_cos_layer& a, int n, long long item0);
 CosLayout p2v_cos_layout(const p2v_cos_layer* layers, int L, int n, std::vector<CosDesc>* descs);
 int p2v_launch_pair_cosine(const std::vector<CosDesc>& descs, const CosLayout& w, int n, double* sums, void* ws, hipStream_t st);
 int p2v_launch_pair_cosine_one(const CosDesc& d, int n, unsigned long long* partials, double* sums, hipStream_t st);
+// recorded sequences (P2V_OP_COS / P2V_OP_COS_COMBINE): the records live in a device table built by p2v_cos_stage_descs
+int p2v_launch_cos_stage(const CosDesc* desc_dev, long long items, unsigned long long* partials, hipStream_t st);
+int p2v_launch_cos_combine(const CosDesc* descs_dev, int L, int n, const unsigned long long* partials, double* sums, hipStream_t st);
 
 // scoring of the logits (p2vit_score.hip): one record per row, then the fold into a totals slot (p2v_score_logits / p2v_score_accumulate)
 int p2v_launch_score_rows(const float* logits, long long ld, int rows, int classes, const long long* labels, int* ranks, double* loss,

@@ -16,12 +16,22 @@ between the launches of the forward (exact integer sums; per-channel PTF scales 
 model, ``-1`` entries, ``model_dequant()``, a CPU model) runs the module graph with forward hooks on the same-named modules and reduces
 through ``torch.ops.p2vit.pair_cosine`` (GPU tensors) or ``pair_cosine_cpu`` (CPU tensors, the plain-torch twin).
 
-Not covered: Swin models (``NotImplementedError``); the reference's norm1 / norm2 / attn.qact3 / mlp.qact2 hook points, whose codes
-never leave LDS or registers in the fused kernels; and forward hooks of your own on QAct / QIntLayerNorm modules of a fused model - they
-never fire, because the engine bypasses the module graph (hooks on QLinear / QConv2d are served, see ``cka``).
+Swin models (``swin_stage_names``): ``compute_ddv(swin, x, xa, 8)`` (or 4: Swin's ``bits``, one weight width for the whole model) on a
+quant-state GPU model makes ONE ``SwinPlan.forward_ddv`` call - a recorded sequence with a ``P2V_OP_COS`` record behind every launch that
+completes a stage and one combine at its end.  Its stages are the QActs of the module graph outside the window kernel - patch_embed's two,
+per block qact1 (norm1), attn.qact1, attn.qact3, attn.qact4, qact2, qact3 (norm2), mlp.qact1, mlp.qact2, qact4, per merge qact1 / qact2, the
+tail's qact2 / qact3 / act_out - and with ``with_linear`` the fp32 output of every QConv2d / QLinear.  attn.qact4 and mlp.qact2 are the
+codes between proj / fc2 and the residual add: the RESID epilogue stores them next to its result.  ``bit_config=None``, a float,
+dequantized or CPU Swin hooks the same-named modules (outputs of the window modules, [B * nW, ...], are regrouped per image).  A LIST
+``bit_config`` raises ``NotImplementedError`` for a Swin: the reference's Swin has no per-layer widths (swin_quant.py:813-817).
 
-``python -m diff_vit_amd.ddv --model deit_small --bits 8 --n 50`` prints the float-vs-quantized similarity per stage on the synthetic
-data of ``harness`` and writes ``ddv_result/ddv.pkl``."""
+Not covered: for ViT / DeiT the reference's norm1 / norm2 / attn.qact3 / mlp.qact2 hook points (that stage list is unchanged); the QActs
+inside the Swin window kernel (qact_attn1, qact2, qact_table, the softmax); DDV on sliced streams; and forward hooks of your own on QAct /
+QIntLayerNorm modules of a fused model - they never fire, because the engine bypasses the module graph (hooks on QLinear / QConv2d are
+served, see ``cka``).
+
+``python -m diff_vit_amd.ddv --model deit_small --bits 8 --n 50`` (or ``--model swin_tiny``; ``--bits mixed`` is refused for Swin) prints
+the float-vs-quantized similarity per stage on the synthetic data of ``harness`` and writes ``ddv_result/ddv.pkl``."""
 import argparse
 import copy
 import os
@@ -43,6 +53,24 @@ def stage_names(depth, with_linear=True):
         names += ([p + 'mlp.fc1'] if with_linear else []) + [p + 'mlp.qact1']
         names += ([p + 'mlp.fc2'] if with_linear else []) + [p + 'qact4']
     return names + ['qact2'] + (['head'] if with_linear else []) + ['act_out']
+
+
+def swin_stage_names(depths, with_linear=True):
+    """the DDV stages of a Swin model in execution order (a linear layer in front of the QAct that follows it), the one list
+    ``SwinPlan.forward_ddv`` and the module-graph path share: 9 per block, 2 per merge, 5 fixed; ``with_linear`` adds 4 per block, 1 per
+    merge and 2."""
+    lin = bool(with_linear)
+    names = (['patch_embed.proj'] if lin else []) + ['patch_embed.qact_before_norm', 'patch_embed.qact']
+    for li, depth in enumerate(depths):
+        for bi in range(depth):
+            p = 'layers.%d.blocks.%d.' % (li, bi)
+            names += [p + 'qact1'] + ([p + 'attn.qkv'] if lin else []) + [p + 'attn.qact1', p + 'attn.qact3']
+            names += ([p + 'attn.proj'] if lin else []) + [p + 'attn.qact4', p + 'qact2', p + 'qact3']
+            names += ([p + 'mlp.fc1'] if lin else []) + [p + 'mlp.qact1'] + ([p + 'mlp.fc2'] if lin else []) + [p + 'mlp.qact2', p + 'qact4']
+        if li < len(depths) - 1:
+            p = 'layers.%d.downsample.' % li
+            names += [p + 'qact1'] + ([p + 'reduction'] if lin else []) + [p + 'qact2']
+    return names + ['qact2', 'qact3'] + (['head'] if lin else []) + ['act_out']
 
 
 def reference_keys(depth):
@@ -126,14 +154,57 @@ def _hooked_outputs(model, x, bit_config, names, fused_state):
     return [got[nm] for nm in names]
 
 
+def _swin_hooked_outputs(model, x, names):
+    """the module graph of a Swin model with forward hooks on the stages' modules; every output as [B, features of the image] (the window
+    modules run on [B * nW, ws * ws, C], image-major: a reshape regroups them per image)"""
+    mods = dict(model.named_modules())
+    got, hooks = {}, []
+    for nm in names:
+        hooks.append(mods[nm].register_forward_hook(lambda m, i, o, nm=nm: got.__setitem__(nm, o.detach())))
+    try:
+        with torch.no_grad():
+            model.act_out(model.head(model.forward_features(x)))
+    finally:
+        for h in hooks:
+            h.remove()
+    return [got[nm].reshape(x.shape[0], -1) for nm in names]
+
+
+def _compute_ddv_swin(model, x, xa, bit_config, with_linear):
+    if isinstance(bit_config, (list, tuple)):
+        raise NotImplementedError('compute_ddv: a Swin model has one weight width and no per-layer bit_config list '
+                                  '(swin_quant.py:813-817); pass 8, 4 or None')
+    dev = _device_of(model)
+    x, xa = x.to(dev).float(), xa.to(dev).float()
+    quant_state = model.quant and all(m.quant and not m.calibrate for m in model._q_modules())
+    if bit_config is not None and quant_state and dev.type == 'cuda':
+        if int(bit_config) not in (4, 8):
+            raise ValueError('%r is not in list' % (bit_config,))
+        if model._plan is None or model._plan.bits != int(bit_config):
+            model.freeze(dev, bits=int(bit_config))
+        _, names, sums = model._plan.forward_ddv(torch.cat((x, xa), 0), with_linear)
+        return names, sums
+    names = swin_stage_names(model.arch['depths'], with_linear)
+    a, b = _swin_hooked_outputs(model, x, names), _swin_hooked_outputs(model, xa, names)
+    if dev.type == 'cuda':
+        return names, torch.ops.p2vit.pair_cosine(a, b, [None] * len(a))
+    return names, pair_cosine_cpu(a, b)
+
+
 def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True):
     """modeldiff_p2.compute_ddv:84-116 for ``model`` under ``bit_config``: dict stage name -> fp64 tensor [n] (on the model's device)."""
     from .swin import SwinTransformer
     from .vit import VisionTransformer
-    if isinstance(model, SwinTransformer) or not isinstance(model, VisionTransformer):
-        raise NotImplementedError('compute_ddv covers the ViT / DeiT models (the fused Swin engine has no DDV stages)')
+    if not isinstance(model, (SwinTransformer, VisionTransformer)):
+        raise NotImplementedError('compute_ddv covers the ViT / DeiT and the Swin models')
+    if isinstance(model, SwinTransformer) and isinstance(bit_config, (list, tuple)):
+        _compute_ddv_swin(model, normal_inputs, adv_inputs, bit_config, with_linear)       # raises
     if tuple(normal_inputs.shape) != tuple(adv_inputs.shape) or normal_inputs.dim() != 4 or normal_inputs.shape[0] < 1:
         raise AssertionError('compute_ddv: clean and perturbed inputs must be two [n, C, H, W] batches of one shape')
+    if isinstance(model, SwinTransformer):
+        names, sums = _compute_ddv_swin(model, normal_inputs, adv_inputs, bit_config, with_linear)
+        d = ddv_from_sums(sums)
+        return {nm: d[k] for k, nm in enumerate(names)}
     dev = _device_of(model)
     x, xa = normal_inputs.to(dev).float(), adv_inputs.to(dev).float()
     has_fp = bit_config is not None and any(int(b) == -1 for b in bit_config)
@@ -249,14 +320,23 @@ def main(argv=None):
     args = p.parse_args(argv)
     device = torch.device(args.device)
     fp = harness.str2model(args.model)(cfg=Config(True, True, 'minmax'))
-    if not hasattr(fp, 'arch') or not hasattr(fp, 'depth'):
-        raise NotImplementedError('the DDV tool covers the ViT / DeiT models')
-    fp.load_state_dict(synth.vit_state_dict(fp.arch, args.seed), strict=False)
+    is_swin = harness._is_swin(fp)
+    if not hasattr(fp, 'arch') or not (is_swin or hasattr(fp, 'depth')):
+        raise NotImplementedError('the DDV tool covers the ViT / DeiT and the Swin models')
+    if is_swin:
+        if args.bits == 'mixed':
+            raise NotImplementedError('--bits mixed: a Swin model has one weight width (swin_quant.py:813-817)')
+        fp.load_state_dict(synth.swin_state_dict(fp.state_dict(), args.seed))
+    else:
+        fp.load_state_dict(synth.vit_state_dict(fp.arch, args.seed), strict=False)
     fp = fp.to(device).eval()
     q = copy.deepcopy(fp)
     harness.calibrate_model(q, synth.images(args.seed + 1, 10, fp.arch['img_size']).to(device))
-    L = 4 * fp.depth + 2
-    bits = {'8': [8] * L, '4': [4] * L, 'mixed': [8 if (i * 7 + 3) % 5 < 3 else 4 for i in range(L)]}[args.bits]
+    if is_swin:
+        bits = int(args.bits)
+    else:
+        L = 4 * fp.depth + 2
+        bits = {'8': [8] * L, '4': [4] * L, 'mixed': [8 if (i * 7 + 3) % 5 < 3 else 4 for i in range(L)]}[args.bits]
     x = synth.images(args.seed + 2, args.n, fp.arch['img_size']).to(device)
     x = (x - x.amin()) / (x.amax() - x.amin())                      # the attack works on images in [0, 1]
     torch.manual_seed(args.seed)

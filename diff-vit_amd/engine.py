@@ -67,6 +67,7 @@ class Block(C.Structure):
 
 
 OP_PATCHIFY, OP_GEMM, OP_LAYERNORM, OP_WINATTN, OP_MERGE, OP_AVGPOOL, OP_LN_GEMM = range(7)
+OP_COS, OP_COS_COMBINE, OP_GEMM_F32 = 7, 8, 9      # one DDV stage / the closing combine / a dense fp32 layer output (op table of include/p2vit.h)
 
 
 class Op(C.Structure):
@@ -153,6 +154,10 @@ def lib():
         L.p2v_ddv_tap_scratch_bytes.argtypes = [_p, _i]
         L.p2v_ddv_tap_scratch_bytes.restype = C.c_size_t
         L.p2v_forward_ddv.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _p, C.c_size_t, _p, _p]
+    if hasattr(L, 'p2v_cos_stage_descs'):         # recorded DDV stages (P2V_OP_COS / P2V_OP_COS_COMBINE), additive
+        L.p2v_cos_stage_desc_bytes.restype = C.c_size_t
+        L.p2v_cos_stage_descs.argtypes = [C.POINTER(CosLayer), _i, _i, _p]
+        L.p2v_cos_stage_descs.restype = _ll
     if hasattr(L, 'p2v_score_logits'):            # the scoring entry points are additive, found by their symbols
         L.p2v_score_logits.argtypes = [_p, _ll, _i, _i, _p, _p, _p, _p]
         L.p2v_score_totals_bytes.argtypes = [_i]

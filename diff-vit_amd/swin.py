@@ -336,8 +336,32 @@ class SwinTransformer(nn.Module):
             # ---- THE HOT PATH: HIP kernels through the C ABI ------------------------------------------------------------------
             if self._plan is None or self._plan.bits != bits:
                 self.freeze(x.device if x.is_cuda else None, bits=bits)
+            linear = self.linear_modules()
+            if any(m._forward_hooks for _, m in linear):
+                return self._forward_hooked(x, linear)
             return self._plan.forward(x)
         return self.act_out(self.head(self.forward_features(x)))
+
+    def linear_modules(self):
+        """(name, module) of the QConv2d / QLinear modules in ``named_modules`` order: the order of ``SwinPlan.forward_linear_taps``"""
+        return [(n, m) for n, m in self.named_modules() if type(m) in (QConv2d, QLinear)]
+
+    def _forward_hooked(self, x, linear):
+        """fused forward of a model with forward hooks on its QConv2d / QLinear modules (``cka.get_activations`` registers them): one
+        ``SwinPlan.forward_linear_taps`` call, then every hook once, in module order, as hook(module, (), output) with the layer's fp32
+        output ([B, tokens, N] in natural token order; QConv2d: the [B, D, H/P, W/P] view).  The engine cannot consume a replaced output:
+        a hook that returns one raises.  The contract of ``VisionTransformer._forward_hooked``."""
+        out, taps = self._plan.forward_linear_taps(x)
+        assert [n for n, _ in linear] == self._plan.linear_tap_names()
+        for (name, m), t in zip(linear, taps):
+            if type(m) is QConv2d:
+                t = t.view(t.shape[0], self.patch_grid[0], self.patch_grid[1], -1).permute(0, 3, 1, 2)
+            for hid, hook in list(m._forward_hooks.items()):
+                r = hook(m, (), {}, t) if m._forward_hooks_with_kwargs.get(hid, False) else hook(m, (), t)
+                if r is not None:
+                    raise RuntimeError('a forward hook on %s returned a replacement output: the fused engine cannot consume it '
+                                       '(model_dequant() runs the module graph, where it can)' % type(m).__name__)
+        return out
 
 
     def forward_uint8(self, images, bits=8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), layout='NHWC'):

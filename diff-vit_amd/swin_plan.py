@@ -210,15 +210,72 @@ class SwinPlan:
         return e
 
     # ---- forward -------------------------------------------------------------------------------------------------------
-    def _record(self, B, fused=True):
+    def _record(self, B, fused=True, ddv_n=0, with_linear=False, lin_taps=False):
         """the launch sequence of one forward at batch B as a ``p2v_op`` array with its own activation buffers (built once
         per batch size and stream slot, replayed by ``p2v_run_ops``).  ``fused``: norm1 + qkv and norm2 + fc1 of stages up to 384
         channels run as ONE launch each (``P2V_OP_LN_GEMM``: the LayerNorm output stays in LDS); the tap replay records the
-        unfused sequence, whose LayerNorm outputs exist in HBM."""
+        unfused sequence, whose LayerNorm outputs exist in HBM.
+        ``ddv_n`` > 0 (B = 2 * ddv_n, unfused): behind the launch that completes a DDV stage a ``P2V_OP_COS`` record reduces samples
+        [0, n) of the live buffer against samples [n, 2n); proj / fc2 also store their mid codes (attn.qact4 / mlp.qact2); ``with_linear``
+        adds the fp32 layer outputs through ONE scratch buffer; a ``P2V_OP_COS_COMBINE`` closes the sequence.
+        ``lin_taps`` (unfused): the fp32 output of every QConv2d / QLinear into a buffer of its own (``forward_linear_taps``)."""
         a = self.arch
         P, g = a['patch_size'], self.g
         dev = self.device
         ops, taps, keep = [], [], []
+        n = ddv_n
+        stages, lin_out = [], []
+        scratch = None
+        if n and with_linear:           # the largest single tap of the 2n images
+            big = max([B * g * g * a['embed_dim'], B * (self.head['N'] + 3)] +
+                      [B * st_['H'] * st_['H'] * max(b_['qkv']['N'], b_['fc1']['N']) for st_ in self.stages for b_ in st_['blocks']])
+            scratch = torch.empty(big, dtype=torch.float32, device=dev)
+            keep.append(scratch)
+
+        def stage(name, t_, rows, cols, stride, dtype=E.COS_I8, scale=None):
+            """DDV stage ``name``: per image rows x cols elements of ``t_`` (row stride ``stride`` elements: padding behind ``cols`` is never read)"""
+            if not n:
+                return
+            esz = 1 if dtype == E.COS_I8 else 4
+            lay = E.CosLayer(E.ptr(t_), C.c_void_p(t_.data_ptr() + n * rows * stride * esz), scale, rows * stride, stride, rows, cols, dtype)
+            o = E.Op()
+            o.kind, o.inp = E.OP_COS, E.ptr(t_)
+            o.i0, o.i1, o.M, o.N, o.lda = n, dtype, rows, cols, stride
+            ss = rows * stride
+            o.i2, o.i3 = ((ss & 0xffffffff) ^ 0x80000000) - 0x80000000, ss >> 32
+            o.lin.colscale = scale
+            ops.append(o)
+            stages.append((name, o, lay))
+
+        def ftap(name, rows_total, N):
+            """fp32 destination of layer ``name``'s output, or None: the one DDV scratch buffer / a buffer of its own for the linear taps"""
+            if lin_taps:
+                t_ = torch.empty(rows_total, N, dtype=torch.float32, device=dev)
+                keep.append(t_)
+                lin_out.append((name, t_))
+                return t_
+            if scratch is not None:
+                return scratch[:rows_total * N].view(rows_total, N)
+            return None
+
+        def ftap_stage(name, t_, rows):
+            if t_ is not None and n:
+                stage(name, t_, rows, t_.shape[1], t_.shape[1], E.COS_F32)
+
+        def gemm_f32(name, x, lin, rows):
+            """layers whose epilogue has no fp32 tap (RESID, HEAD): one fp32-output GEMM over the layer's int8 input; rows of the output
+            are a multiple of 16 bytes apart (a class count that is no multiple of 4)"""
+            N, ld = lin['N'], (lin['N'] + 3) // 4 * 4
+            t_ = ftap(name, x.shape[0], ld)
+            if t_ is None:
+                return
+            o = E.Op()
+            o.kind, o.inp, o.out = E.OP_GEMM_F32, E.ptr(x), E.ptr(t_)
+            o.M, o.K, o.N, o.lda, o.ldo = x.shape[0], x.shape[1], N, x.shape[1], ld
+            o.lin = lin['lin']
+            ops.append(o)
+            if n:
+                stage(name, t_, rows, N, ld, E.COS_F32)
 
         def buf(rows, cols, zero=False):
             t_ = (torch.zeros if zero else torch.empty)(rows, cols, dtype=torch.int8, device=dev)
@@ -251,14 +308,16 @@ class SwinPlan:
             ops.append(o)
             return out
 
-        def epi_req(inv_s):
+        def epi_req(inv_s, tap=None):
             e = E.Epilogue()
             e.inv_s_out = inv_s
+            e.tap_out = E.ptr(tap)
             return e
 
-        def epi_res(src, residual):
+        def epi_res(src, residual, mid=None):
             e = E.Epilogue()
             e.s_mid, e.s_res, e.s_next, e.residual, e.resid_tab = src.s_mid, src.s_res, src.s_next, E.ptr(residual), src.resid_tab
+            e.tap_out = E.ptr(mid)              # RESID records: the int8 mid-code destination (include/p2vit.h, op table)
             return e
 
         o = E.Op()
@@ -267,9 +326,13 @@ class SwinPlan:
         o.i0, o.i1, o.i2, o.i3, o.i4, o.i5, o.f0 = B, self.in_chans, a['img_size'], a['img_size'], P, self.k_patch, 1.0 / self.s_in
         ops.append(o)
         D0 = a['embed_dim']
-        pe = gemm(E.EPI_REQUANT, patches, self.pe, epi_req(1.0 / self.s_pe_b), buf(B * g * g, D0))
+        t_pe = ftap('patch_embed.proj', B * g * g, D0)
+        pe = gemm(E.EPI_REQUANT, patches, self.pe, epi_req(1.0 / self.s_pe_b, t_pe), buf(B * g * g, D0))
+        ftap_stage('patch_embed.proj', t_pe, g * g)
+        stage('patch_embed.qact_before_norm', pe, g * g, D0, D0)
         x = lnorm(pe, self.pe_ln, D0, buf(B * g * g, D0))
         taps.append((len(ops), 'patch_embed.qact', x))
+        stage('patch_embed.qact', x, g * g, D0, D0)
         for li, stg in enumerate(self.stages):
             T, Cc = stg['H'] * stg['H'], stg['C']
             rows = B * T
@@ -278,8 +341,10 @@ class SwinPlan:
             qkv = buf(rows, 3 * Cc)
             att = buf(rows, pad64(Cc))
             hid = buf(rows, 4 * Cc)
+            mid = buf(rows, Cc) if n else None
             for bi, b in enumerate(stg['blocks']):
                 p = 'layers.%d.blocks.%d.' % (li, bi)
+                t_qkv, t_fc1 = ftap(p + 'attn.qkv', rows, b['qkv']['N']), None
                 e_fc1 = epi_req(b['inv_s_fc1'])
                 e_fc1.gelu = E.gelu_table(b['inv_s_fc1'], self.device)       # exact GELU -> qact1 threshold table (cached per scale)
                 fuse = (fused and b['qkv']['wf'] is not None and E.lib().p2v_ln_gemm_fusable(E.EPI_REQUANT, Cc, b['qkv']['N'], 0) == 1
@@ -289,22 +354,37 @@ class SwinPlan:
                 else:
                     lnorm(x, b['ln1'], Cc, ln)
                     taps.append((len(ops), p + 'qact1', ln))
-                    gemm(E.EPI_REQUANT, ln, b['qkv'], epi_req(b['inv_s_qkv']), qkv)
+                    stage(p + 'qact1', ln, T, Cc, ln.shape[1])
+                    gemm(E.EPI_REQUANT, ln, b['qkv'], epi_req(b['inv_s_qkv'], t_qkv), qkv)
+                    ftap_stage(p + 'attn.qkv', t_qkv, T)
+                    stage(p + 'attn.qact1', qkv, T, 3 * Cc, 3 * Cc)
                 o = E.Op()
                 o.kind, o.inp, o.out = E.OP_WINATTN, E.ptr(qkv), E.ptr(att)
                 o.i0, o.i1, o.i2, o.i3 = B, T, b['heads'], 32
                 o.wa = b['wa']
                 o.wa.out_stride = att.shape[1]
                 ops.append(o)
-                gemm(E.EPI_RESID, att, b['proj'], epi_res(b['proj_epi'], x), x2)
+                stage(p + 'attn.qact3', att, T, Cc, att.shape[1])       # (the out_stride padding of att is never written: cols = Cc)
+                gemm_f32(p + 'attn.proj', att, b['proj'], T)
+                gemm(E.EPI_RESID, att, b['proj'], epi_res(b['proj_epi'], x, mid), x2)
+                stage(p + 'attn.qact4', mid, T, Cc, Cc)
                 taps.append((len(ops), p + 'qact2', x2))
+                stage(p + 'qact2', x2, T, Cc, Cc, scale=b['proj_epi'].s_next)
                 if fuse:
                     ln_gemm(E.EPI_GELU, x2, b['ln2'], Cc, b['fc1'], e_fc1, hid)
                 else:
                     lnorm(x2, b['ln2'], Cc, ln)
+                    stage(p + 'qact3', ln, T, Cc, ln.shape[1])
+                    t_fc1 = ftap(p + 'mlp.fc1', rows, b['fc1']['N'])
+                    e_fc1.tap_out = E.ptr(t_fc1)
                     gemm(E.EPI_GELU, ln, b['fc1'], e_fc1, hid)
-                gemm(E.EPI_RESID, hid, b['fc2'], epi_res(b['fc2_epi'], x2), x)
+                    ftap_stage(p + 'mlp.fc1', t_fc1, T)
+                    stage(p + 'mlp.qact1', hid, T, hid.shape[1], hid.shape[1])
+                gemm_f32(p + 'mlp.fc2', hid, b['fc2'], T)
+                gemm(E.EPI_RESID, hid, b['fc2'], epi_res(b['fc2_epi'], x2, mid), x)
+                stage(p + 'mlp.qact2', mid, T, Cc, Cc)
                 taps.append((len(ops), p + 'qact4', x))
+                stage(p + 'qact4', x, T, Cc, Cc, scale=b['fc2_epi'].s_next)
             if stg['merge'] is not None:
                 m, H = stg['merge'], stg['H']
                 r2 = B * (H // 2) * (H // 2)
@@ -314,16 +394,22 @@ class SwinPlan:
                 o.i0, o.i1, o.i2, o.i3 = B, H, H, Cc
                 ops.append(o)
                 lnm = lnorm(gathered, m['ln'], 4 * Cc, buf(r2, 4 * Cc))
+                stage('layers.%d.downsample.qact1' % li, lnm, r2 // B, 4 * Cc, 4 * Cc)
+                gemm_f32('layers.%d.downsample.reduction' % li, lnm, m['red'], r2 // B)
                 x = gemm(E.EPI_RESID, lnm, m['red'], epi_res(m['epi'], buf(r2, 2 * Cc, zero=True)), buf(r2, 2 * Cc))
                 taps.append((len(ops), 'layers.%d.downsample.qact2' % li, x))
+                stage('layers.%d.downsample.qact2' % li, x, r2 // B, 2 * Cc, 2 * Cc, scale=m['epi'].s_next)
         fin = lnorm(x, self.fin_ln, self.C_last, buf(x.shape[0], self.C_last))
         taps.append((len(ops), 'qact2', fin))
+        stage('qact2', fin, self.H_last * self.H_last, self.C_last, self.C_last)
         pooled = buf(B, self.C_last)
         o = E.Op()
         o.kind, o.inp, o.out = E.OP_AVGPOOL, E.ptr(fin), E.ptr(pooled)
         o.i0, o.i1, o.i2, o.f0, o.f1 = B, self.H_last * self.H_last, self.C_last, self.s_f, 1.0 / self.s_pool
         ops.append(o)
         taps.append((len(ops), 'qact3', pooled))
+        stage('qact3', pooled, 1, self.C_last, self.C_last)
+        gemm_f32('head', pooled, self.head, 1)
         e = E.Epilogue()
         e.inv_s_out, e.s_out = 1.0 / self.s_out, self.s_out
         o = E.Op()
@@ -331,8 +417,36 @@ class SwinPlan:
         o.M, o.K, o.N, o.lda, o.ldo = B, self.C_last, self.head['N'], self.C_last, self.head['N']
         o.lin, o.ep = self.head['lin'], e
         ops.append(o)
-        arr = (E.Op * len(ops))(*ops)
-        return dict(ops=arr, n=len(ops), taps=taps, keep=keep)
+        rec = dict(taps=taps, keep=keep, head=len(ops) - 1, lin_out=lin_out)
+        if n:
+            # the stages reference a STATIC logits buffer (their records hold its address); forward_ddv returns a copy
+            ldl = (self.head['N'] + 3) // 4 * 4
+            logits = torch.zeros(B, ldl, dtype=torch.float32, device=dev)
+            o.out, o.ldo = E.ptr(logits), ldl
+            stage('act_out', logits, 1, self.head['N'], ldl, E.COS_F32)
+            L = E.lib()
+            lays = (E.CosLayer * len(stages))(*[st_[2] for st_ in stages])
+            dbytes = L.p2v_cos_stage_desc_bytes()
+            host = (C.c_char * (dbytes * len(stages)))()
+            items = L.p2v_cos_stage_descs(lays, len(stages), n, host)
+            if items < 0:
+                E.check(int(items))
+            descs = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(dev)
+            partials = torch.empty(int(items) * 3, dtype=torch.int64, device=dev)
+            sums = torch.empty(len(stages), n, 3, dtype=torch.float64, device=dev)
+            for k, (_, so, _) in enumerate(stages):
+                so.out = E.ptr(partials)
+                so.lin.w_codes = C.c_void_p(descs.data_ptr() + k * dbytes)
+            o = E.Op()
+            o.kind, o.inp, o.out = E.OP_COS_COMBINE, E.ptr(descs), E.ptr(sums)
+            o.i0, o.i1 = n, len(stages)
+            o.lin.w_codes = E.ptr(partials)
+            ops.append(o)
+            keep += [logits, descs, partials]
+            rec.update(names=[st_[0] for st_ in stages], sums=sums, logits=logits)
+        rec['ops'] = (E.Op * len(ops))(*ops)
+        rec['n'] = len(ops)
+        return rec
 
     def _replay(self, images, slot, taps=None, profile=False):
         with torch.cuda.device(self.device):       # the recorded pointers and the launch stream belong to the plan's GPU
@@ -362,6 +476,53 @@ class SwinPlan:
             done = upto
         E.check(L.p2v_run_ops(C.cast(C.byref(r['ops'], done * C.sizeof(E.Op)), C.POINTER(E.Op)), r['n'] - done, E.stream_ptr(self.device)))
         return out
+
+    def _replay_extra(self, images, key, **kw):
+        """replay the recorded sequence ``key`` (made with ``_record(B, fused=False, **kw)`` on first use) in one ``p2v_run_ops`` call"""
+        with torch.cuda.device(self.device):
+            if key not in self._recorded:
+                self._recorded[key] = self._record(images.shape[0], fused=False, **kw)
+            r = self._recorded[key]
+            r['ops'][0].inp = E.ptr(images)
+            out = None
+            if 'logits' not in r:
+                out = torch.empty(images.shape[0], self.head['N'], dtype=torch.float32, device=self.device)
+                r['ops'][r['head']].out = E.ptr(out)
+            E.check(E.lib().p2v_run_ops(r['ops'], r['n'], E.stream_ptr(self.device)))
+            return r, out
+
+    def forward_ddv(self, images_2n, with_linear=True):
+        """The DDV of the quantized model inside the forward: ``images_2n`` = n clean images followed by their n perturbed twins.
+        Returns (logits [2n, classes], byte-equal to ``forward``; stage names = ``ddv.swin_stage_names(depths, with_linear)``; sums fp64
+        [stages, n, 3] = sum a.b, sum a.a, sum b.b per stage and pair).  One recorded sequence, one ``p2v_run_ops`` call on the current
+        stream: every stage is reduced from the live buffer right behind the launch that completes it (the LayerNorm outputs exist in HBM
+        because the unfused sequence is recorded; attn.qact4 / mlp.qact2 come from the mid-code output of the RESID epilogue), one combine
+        launch closes it.  The QActs inside the window kernel (qact_attn1, qact2, qact_table, the softmax) are not stages."""
+        images_2n = self._check_images(images_2n)
+        if images_2n.shape[0] < 2 or images_2n.shape[0] % 2:
+            raise AssertionError('forward_ddv takes n clean images followed by their n perturbed twins, got %d images' % images_2n.shape[0])
+        n = images_2n.shape[0] // 2
+        r, _ = self._replay_extra(images_2n, ('ddv', n, bool(with_linear)), ddv_n=n, with_linear=bool(with_linear))
+        return r['logits'][:, :self.head['N']].clone(), list(r['names']), r['sums'].clone()
+
+    def forward_linear_taps(self, images):
+        """(logits, [fp32 tensors]): the output of every QConv2d / QLinear in ``named_modules`` order (patch_embed.proj; qkv, proj, fc1,
+        fc2 of every block; downsample.reduction behind a stage's blocks; head) as [B, tokens, N] in NATURAL token order ([B, N] for the
+        head).  The module graph would hand qkv and proj over in window order ([B * nW, ws * ws, N]): the same values with the tokens of an
+        image permuted.  A Gram matrix over the flattened features of an image (CKA) does not see a permutation of features."""
+        images = self._check_images(images)
+        B = images.shape[0]
+        r, out = self._replay_extra(images, ('lin', B), lin_taps=True)
+        return out, [t_[:, :self.head['N']].clone() if nm == 'head' else t_.view(B, -1, t_.shape[1]).clone() for nm, t_ in r['lin_out']]
+
+    def linear_tap_names(self):
+        names = ['patch_embed.proj']
+        for li, st_ in enumerate(self.stages):
+            for bi in range(len(st_['blocks'])):
+                names += ['layers.%d.blocks.%d.%s' % (li, bi, k) for k in ('attn.qkv', 'attn.proj', 'mlp.fc1', 'mlp.fc2')]
+            if st_['merge'] is not None:
+                names.append('layers.%d.downsample.reduction' % li)
+        return names + ['head']
 
     def _check_images(self, images):
         a = self.arch

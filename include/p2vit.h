@@ -385,7 +385,11 @@ int p2v_u8_patchify(const uint8_t* img, int layout, const void* lut_i8, int batc
 
 /* out = epilogue(A[M][K] . W[N][K]^T): int8 MFMA (v_mfma_i32_32x32x32_i8), fp32 epilogue in the
  * reference's operation order.  lda/ldo in elements.  `out` is int8 [M][ldo] except HEAD (fp32 [M][ldo]);
- * when out_codes != NULL the HEAD epilogue also writes the int8 logit codes there ([M][ldo]).
+ * when out_codes != NULL the HEAD epilogue also writes the int8 logit codes there ([M][ldo]), and the RESID epilogue the codes of the QAct
+ * between the layer and the residual add (attn.qact4 / mlp.qact2 of Swin, attn.qact3 / mlp.qact2 of ViT): q3 = clamp(round((acc *
+ * colscale[n] + bias[n]) / s_mid[n])), the first rounding of the RESID formula below, int8 [M][ldo].  A tapped RESID launch runs the generic
+ * chain of the tiled kernel whatever resid_tab says (same codes, `out` byte-identical with and without the tap); out and out_codes 16-byte
+ * aligned, int8-stored weights (P2V_E_UNSUPPORTED for packed4).  Other epilogues ignore out_codes.
  * K is a multiple of 64 and MAY exceed lda (a width that is not a multiple of 64: the weight columns [width, K) are zero): the
  * contraction then walks into the next row, so (M-1)*lda + K bytes of A must be readable.  ldo >= N.  P2V_E_SHAPE otherwise.
  * Written: columns [0, N) of rows [0, M) of `out` (and of out_codes, same ldo) - never the columns [N, ldo) - and tap_out as a dense
@@ -475,8 +479,20 @@ int p2v_avgpool_quant(const int8_t* x, int batch, int tokens, int C, float s_in,
  *   P2V_OP_MERGE      in, out; i0 batch, i1 H, i2 W, i3 C
  *   P2V_OP_AVGPOOL    in, out; i0 batch, i1 tokens, i2 C; f0 s_in, f1 inv_s_out
  *   P2V_OP_LN_GEMM    in (residual-stream codes), out; epi (REQUANT / GELU); M rows, K = C channels of the LayerNorm, N, lda row stride
- *                     of `in`, ldo == N; ln; lin (w_frag required); ep      = p2v_ln_gemm_i8: LayerNorm fused into the GEMM that reads it */
-enum { P2V_OP_PATCHIFY = 0, P2V_OP_GEMM = 1, P2V_OP_LAYERNORM = 2, P2V_OP_WINATTN = 3, P2V_OP_MERGE = 4, P2V_OP_AVGPOOL = 5, P2V_OP_LN_GEMM = 6 };
+ *                     of `in`, ldo == N; ln; lin (w_frag required); ep      = p2v_ln_gemm_i8: LayerNorm fused into the GEMM that reads it
+ *   (appended, additive - no structure, earlier kind or P2V_ABI_VERSION changes:)
+ *   P2V_OP_GEMM, epi == P2V_EPI_RESID: ep.tap_out, read as int8_t*, optionally names the MID-code destination [M][ldo] (p2v_gemm_i8's
+ *                     out_codes for RESID); REQUANT / GELU records of P2V_OP_GEMM and P2V_OP_LN_GEMM pass ep.tap_out (fp32 [M][N]) through
+ *   P2V_OP_COS        one DDV stage: samples [0, n) of the live buffer `in` against samples [n, 2n) of it.  i0 n, i1 dtype (P2V_COS_*),
+ *                     M rows, N cols, lda row stride, i2 | i3 << 32 sample stride (elements; p2v_cos_layer's rules); lin.colscale the
+ *                     per-channel scales or NULL; lin.w_codes the stage's record in the device table of p2v_cos_stage_descs (built from
+ *                     the same layer); out the partial slots of the whole table.  One launch
+ *   P2V_OP_COS_COMBINE  closes the stages of a sequence: in the device table, i1 its stages (>= 1), i0 n, lin.w_codes the partial slots,
+ *                     out sums fp64 [stages][n][3].  One launch
+ *   P2V_OP_GEMM_F32   in (A), out fp32 [M][ldo] = fmaf(acc, colscale, bias), columns [0, N) only: M, K, N, lda, ldo (N: dense, or a multiple
+ *                     of 4 beyond it); lin; in and out 16-byte aligned.  (The public p2v_gemm_i8 refuses this epilogue.) */
+enum { P2V_OP_PATCHIFY = 0, P2V_OP_GEMM = 1, P2V_OP_LAYERNORM = 2, P2V_OP_WINATTN = 3, P2V_OP_MERGE = 4, P2V_OP_AVGPOOL = 5, P2V_OP_LN_GEMM = 6,
+       P2V_OP_COS = 7, P2V_OP_COS_COMBINE = 8, P2V_OP_GEMM_F32 = 9 };
 typedef struct p2v_op {
   int32_t kind, epi;
   const void* in;
@@ -577,6 +593,12 @@ size_t p2v_pair_cosine_workspace_bytes(const p2v_cos_layer* layers, int n_layers
  * dtype) only and the partials are combined in a fixed order, no atomics: bitwise repeatable.  layers: HOST array (copied to the
  * workspace before the call returns); ws 256-byte aligned.  Two launches on `stream`. */
 int p2v_pair_cosine(const p2v_cos_layer* layers, int n_layers, int n, double* sums, void* ws, size_t ws_bytes, void* stream);
+/* The same reduction as records of a replayed sequence (P2V_OP_COS per stage, one P2V_OP_COS_COMBINE at the end; the op table of p2v_op).
+ * p2v_cos_stage_descs checks the layers like p2v_pair_cosine and writes n_layers opaque stage records of p2v_cos_stage_desc_bytes() each to
+ * HOST memory; the caller uploads them once (8-byte aligned) and keeps them with the sequence.  Returns the number of partial slots (3 x
+ * uint64 each) the stages write, or a negative status. */
+size_t p2v_cos_stage_desc_bytes(void);
+long long p2v_cos_stage_descs(const p2v_cos_layer* layers, int n_layers, int n, void* host_descs);
 
 /* The quantized model's DDV inside the fused forward.  images: dev fp32 [2n][in_chans][img][img], n clean images then their n perturbed
  * twins; logits: dev fp32 [2n][num_classes], equal to p2v_forward's.  Right after the launch that completes a stage, two small launches

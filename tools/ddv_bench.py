@@ -2,6 +2,7 @@
 per model.
 
     python tools/ddv_bench.py [--n 50] [--reps 10] [--models deit_small,vit_base]
+    python tools/ddv_bench.py --swin swin_base [--n 50] [--reps 10]        the Swin lines (below), instead of the ViT / DeiT ones
 
   (a)  forward_ms                 FrozenPlan.forward of the 2n images (one stream; the last block on the class rows only)
        forward_all_rows_ms        the same with the switch cls_rows = 0: every row of the last block, what every tap entry point computes
@@ -11,7 +12,15 @@ per model.
        reduction                  bytes the reductions of (b) read (both operands of every stage), the time they add to the all-rows
                                   forward, and the rate; `standalone`: ONE grouped p2v_pair_cosine over buffers of the same shapes,
                                   ~0.9 GB that no launch has just written.  HBM: 8.0 TB/s peak, 6.29 TB/s measured for a float4 copy
-                                  (MI355X_MICROARCH.md); the live buffers of (b) mostly sit in the 256 MiB Infinity Cache."""
+                                  (MI355X_MICROARCH.md); the live buffers of (b) mostly sit in the 256 MiB Infinity Cache.
+
+  --swin (synthetic weights, calibrated on two images, 8-bit, one stream):
+       forward_ms                 SwinPlan.forward of the 2n images (n_streams = 1)
+       ddv_int8_ms                SwinPlan.forward_ddv(with_linear=False): the recorded sequence with a P2V_OP_COS behind every stage
+       ddv_linear_ms              forward_ddv(with_linear=True): + every linear output through ONE fp32 scratch buffer
+       taps_torch_ms              the alternative it replaces: forward(taps=...) (segmented replay, every tap cloned) +
+                                  torch.ops.p2vit.pair_cosine on the cloned taps
+       resid_tap                  the last stage's fc2 (RESID) launch alone, without and with the mid-code output, median of 10 x 20 launches"""
 import argparse
 import json
 import os
@@ -85,12 +94,64 @@ def run(model, n, reps):
                           'hbm_TBps': {'peak': 8.0, 'measured_copy': 6.29}}}
 
 
+def run_swin(name, n, reps):
+    import contextlib
+    import ctypes as C
+    E = dva.engine
+    with contextlib.redirect_stdout(sys.stderr):
+        model = dva.harness.str2model(name)(cfg=dva.Config(True, True, 'minmax'))
+    model.load_state_dict(dva.synth.swin_state_dict(model.state_dict(), 0))
+    model = model.cuda().eval()
+    img = model.arch['img_size']
+    with torch.no_grad():
+        dva.harness.calibrate_model(model, dva.synth.images(0, 2, img).cuda())
+    plan = model.freeze(torch.device('cuda:0'), bits=8)
+    x = dva.synth.images(1, 2 * n, img).cuda()
+    t_fwd = timed(lambda: plan.forward(x, n_streams=1), reps)
+    t_b = timed(lambda: plan.forward_ddv(x, False), reps)
+    t_c = timed(lambda: plan.forward_ddv(x, True), reps)
+
+    def taps_torch():
+        taps = {}
+        logits = plan.forward(x, taps=taps)
+        ts = list(taps.values())
+        return torch.ops.p2vit.pair_cosine([t[:t.shape[0] // 2].reshape(n, -1, t.shape[1]) for t in ts],
+                                           [t[t.shape[0] // 2:].reshape(n, -1, t.shape[1]) for t in ts], [None] * len(ts)), logits
+    t_d = timed(taps_torch, reps)
+    # the mid-code tap on one RESID launch: fc2 of the last stage at 2n images
+    b = plan.stages[-1]['blocks'][-1]
+    rows, Cc = 2 * n * plan.H_last * plan.H_last, plan.C_last
+    hid = torch.randint(-128, 128, (rows, 4 * Cc), dtype=torch.int8, device='cuda')
+    res = torch.randint(-128, 128, (rows, Cc), dtype=torch.int8, device='cuda')
+    out, mid = torch.empty_like(res), torch.empty_like(res)
+    epi = E.Epilogue()
+    src = b['fc2_epi']
+    epi.s_mid, epi.s_res, epi.s_next, epi.residual, epi.resid_tab = src.s_mid, src.s_res, src.s_next, E.ptr(res), src.resid_tab
+    L = E.lib()
+
+    def fc2(tap):
+        for _ in range(20):
+            E.check(L.p2v_gemm_i8(E.EPI_RESID, E.ptr(hid), 4 * Cc, rows, 4 * Cc, Cc, C.byref(b['fc2']['lin']), C.byref(epi), E.ptr(out), Cc,
+                                  E.ptr(mid) if tap else None, E.stream_ptr()))
+    t_plain, t_tap = timed(lambda: fc2(False), reps) / 20, timed(lambda: fc2(True), reps) / 20
+    return {'model': name, 'n': n, 'images': 2 * n, 'stages_int8': len(dva.ddv.swin_stage_names(model.arch['depths'], False)),
+            'stages_linear': len(dva.ddv.swin_stage_names(model.arch['depths'], True)),
+            'forward_ms': round(t_fwd, 3), 'ddv_int8_ms': round(t_b, 3), 'ddv_linear_ms': round(t_c, 3), 'taps_torch_ms': round(t_d, 3),
+            'ddv_int8_over_forward': round(t_b / t_fwd, 3),
+            'resid_tap': {'layer': 'stage %d fc2' % (len(plan.stages) - 1), 'M': rows, 'K': 4 * Cc, 'N': Cc, 'prefolded': bool(src.resid_tab),
+                          'plain_us': round(t_plain * 1e3, 2), 'tapped_us': round(t_tap * 1e3, 2)}}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--n', type=int, default=50)
     p.add_argument('--reps', type=int, default=10)
     p.add_argument('--models', default='deit_small,vit_base')
+    p.add_argument('--swin', default=None, help='a Swin factory name of harness.str2model (swin_base): the Swin lines instead')
     a = p.parse_args()
+    if a.swin:
+        print(json.dumps(run_swin(a.swin, a.n, a.reps)), flush=True)
+        return
     for m in a.models.split(','):
         print(json.dumps(run(m, a.n, a.reps)), flush=True)
 
