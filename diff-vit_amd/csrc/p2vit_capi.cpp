@@ -911,7 +911,7 @@ size_t p2v_ln_prefold_bytes(int C) { return C > 0 ? (size_t)2 * round_up(C, 256)
 int p2v_ln_prefold(p2v_ln* ln, int C, float* buf, size_t buf_bytes) {
   if (!ln || !buf) return fail(P2V_E_ARG, "p2v_ln_prefold: null argument");
   ln->pre = kNoPre;
-  if (C <= 0 || C % 4 || C > 2048) return fail(P2V_E_SHAPE, "p2v_ln_prefold: C must be a positive multiple of 4 up to 2048");
+  if (C <= 0 || C % 4 || C > P2V_LN_MAX_C) return fail(P2V_E_SHAPE, "p2v_ln_prefold: C must be a positive multiple of 4 up to %d", P2V_LN_MAX_C);
   if (!ln_constants_present(*ln, false)) return fail(P2V_E_ARG, "p2v_ln_prefold: LayerNorm constants missing");      // (the fold does not read the mask)
   if (buf_bytes < p2v_ln_prefold_bytes(C)) return fail(P2V_E_WORKSPACE, "p2v_ln_prefold: buffer %zu < %zu bytes", buf_bytes, p2v_ln_prefold_bytes(C));
   OwnerDevice own(buf);
@@ -946,6 +946,11 @@ int p2v_int_layernorm(const int8_t* x, long long row_stride, int rows, int C, co
   if (C % 4 || row_stride % 4 || out_stride % 4) return fail(P2V_E_UNSUPPORTED, "C and strides must be multiples of 4");
   if (rows <= 0) return fail(P2V_E_SHAPE, "rows must be positive");
   if (C <= 0 || row_stride < 0 || out_stride < C) return fail(P2V_E_SHAPE, "p2v_int_layernorm: C=%d must be positive, row_stride non-negative, out_stride >= C", C);
+  if (C > P2V_LN_MAX_C) return fail(P2V_E_SHAPE, "p2v_int_layernorm: C=%d, the LayerNorm kernels cover up to %d channels", C, P2V_LN_MAX_C);
+  // rows beyond 2048 channels (new with the row-per-workgroup kernel) are taken only as whole rows: a row_stride inside the row would make
+  // the input rows overlap.  Up to 2048 channels the entry point keeps what it accepted before.
+  if (C > 2048 && row_stride < C)
+    return fail(P2V_E_SHAPE, "p2v_int_layernorm: C=%d beyond 2048 channels needs row_stride >= C (got %lld)", C, row_stride);
   LnArgs a{x, row_stride, rows, C, *ln, out, out_stride};
   a.pre = ln->pre;                       // optional: constants folded ahead of the launch (p2v_ln_prefold)
   return launch_rc(p2v_launch_layernorm(a, (hipStream_t)stream), "int_layernorm");

@@ -81,7 +81,10 @@ int p2v_launch_gemm(int epi, const GemmArgs& g, hipStream_t st);
 int p2v_launch_gemm_rows(int epi, const GemmArgs& g, hipStream_t st);
 // table of the pre-folded RESID epilogue (p2v_epilogue.resid_tab): [ceil(N/128)][6][128] floats; flags: dev [2] preset to {1, 0}
 int p2v_launch_resid_prefold(const p2v_linear& lin, const p2v_epilogue& ep, int N, float* tab, unsigned* flags, hipStream_t st);
+#define P2V_LN_MAX_C 4096   // channels of a LayerNorm row: k_int_layernorm up to 2048, k_int_layernorm_xwide beyond
 int p2v_launch_layernorm(const LnArgs& a, hipStream_t st);
+// rows of 2049 .. 4096 channels, a row per workgroup (p2vit_ln_xwide.hip); p2v_launch_layernorm routes to it with force_generic / pre filled
+int p2v_launch_layernorm_xwide(const LnArgs& a, hipStream_t st);
 bool p2v_ln_gemm_supported(int epi, int C, int N, int table_cells);
 int p2v_launch_ln_gemm(int epi, const LnArgs& a, const GemmArgs& g, hipStream_t st);   // -3: shape not fused
 int p2v_launch_attention(const AttnArgs& a, int head_dim, hipStream_t st);

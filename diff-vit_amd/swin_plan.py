@@ -288,7 +288,7 @@ class SwinPlan:
         def gemm(kind, x, lin, epi, out):
             o = E.Op()
             o.kind, o.epi, o.inp, o.out = E.OP_GEMM, kind, E.ptr(x), E.ptr(out)
-            o.M, o.K, o.N, o.lda, o.ldo = x.shape[0], x.shape[1], lin['N'], x.shape[1], lin['N']
+            o.M, o.K, o.N, o.lda, o.ldo = x.shape[0], x.shape[1], lin['N'], x.shape[1], out.shape[1]
             o.lin, o.ep = lin['lin'], epi
             ops.append(o)
             return out
@@ -340,14 +340,18 @@ class SwinPlan:
             ln = buf(rows, pad64(Cc))
             qkv = buf(rows, 3 * Cc)
             att = buf(rows, pad64(Cc))
-            hid = buf(rows, 4 * Cc)
+            # the MLP's hidden codes: as wide as fc2 contracts over (int(Cc * mlp_ratio), walked in whole 64-deep k-tiles: columns behind
+            # fc1's outputs stay zero and meet zero weight columns) - NOT 4 * Cc, which made fc2 read rows and weights of another width
+            # whenever mlp_ratio was not 4
+            fc1_n, hid_k = stg['blocks'][0]['fc1']['N'], stg['blocks'][0]['fc2']['K']
+            hid = buf(rows, hid_k, zero=hid_k != fc1_n)
             mid = buf(rows, Cc) if n else None
             for bi, b in enumerate(stg['blocks']):
                 p = 'layers.%d.blocks.%d.' % (li, bi)
                 t_qkv, t_fc1 = ftap(p + 'attn.qkv', rows, b['qkv']['N']), None
                 e_fc1 = epi_req(b['inv_s_fc1'])
                 e_fc1.gelu = E.gelu_table(b['inv_s_fc1'], self.device)       # exact GELU -> qact1 threshold table (cached per scale)
-                fuse = (fused and b['qkv']['wf'] is not None and E.lib().p2v_ln_gemm_fusable(E.EPI_REQUANT, Cc, b['qkv']['N'], 0) == 1
+                fuse = (fused and b['qkv']['wf'] is not None and hid_k == fc1_n and E.lib().p2v_ln_gemm_fusable(E.EPI_REQUANT, Cc, b['qkv']['N'], 0) == 1
                         and E.lib().p2v_ln_gemm_fusable(E.EPI_GELU, Cc, b['fc1']['N'], e_fc1.gelu.cells if e_fc1.gelu.table else 0) == 1)
                 if fuse:
                     ln_gemm(E.EPI_REQUANT, x, b['ln1'], Cc, b['qkv'], epi_req(b['inv_s_qkv']), qkv)
@@ -379,7 +383,7 @@ class SwinPlan:
                     e_fc1.tap_out = E.ptr(t_fc1)
                     gemm(E.EPI_GELU, ln, b['fc1'], e_fc1, hid)
                     ftap_stage(p + 'mlp.fc1', t_fc1, T)
-                    stage(p + 'mlp.qact1', hid, T, hid.shape[1], hid.shape[1])
+                    stage(p + 'mlp.qact1', hid, T, fc1_n, hid.shape[1])
                 gemm_f32(p + 'mlp.fc2', hid, b['fc2'], T)
                 gemm(E.EPI_RESID, hid, b['fc2'], epi_res(b['fc2_epi'], x2, mid), x)
                 stage(p + 'mlp.qact2', mid, T, Cc, Cc)

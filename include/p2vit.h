@@ -57,7 +57,11 @@
  *     patch 4 / window 12 / 384^2 geometry: the kernel of csrc/p2vit_winattn_wide.hip, same codes);
  *   - embed_dim and MLP width of a plan: multiples of 16 (round 4; before: 64) - the contractions walk 64-deep k-tiles through zero weight
  *     columns (p2v_linear: k_pad = round_up(K, 64)); the per-operator GEMM entry points take K in whole k-tiles;
- *   - LayerNorm: up to 2048 channels, PTF input masks (in_scale / min in_scale) in {1, 2, 4, 8};
+ *   - LayerNorm: up to 4096 channels as an operator (p2v_int_layernorm, P2V_OP_LAYERNORM, p2v_ln_prefold: up to 2048 a row per wave or
+ *     half wave, beyond that a row per workgroup, csrc/p2vit_ln_xwide.hip - the 4 * 768 = 3072-channel PatchMerging norm of Swin-L); a
+ *     p2v_plan (ViT) keeps embed_dim <= 2048.  PTF input masks (in_scale / min in_scale) in {1, 2, 4, 8}, and the row's sum of squares
+ *     must fit 32 unsigned bits: C * (128 * largest mask)^2 < 2^32 (any mask up to C = 4092, masks <= 4 at C = 4096) - the caller's to
+ *     check, the kernels do not;
  *   - LayerNorm output scale: p2v_ln.inv_out is MULTIPLIED by where the reference divides by the scale - identical for the power-of-two
  *     scales of this path; for any other scale pass p2v_ln.out_scale too and the kernel divides (exact, ABI 3);
  *   - REQUANT epilogues fold 1/scale into the column constants: it must be a power of two;
@@ -175,7 +179,8 @@ typedef struct p2v_ln {
   p2v_ln_pre pre;         /* optional (ABI 5), see above */
 } p2v_ln;
 /* Fold the constants of *ln for C channels into buf (dev, p2v_ln_prefold_bytes(C) bytes, owned by the caller, must outlive the launches) and
- * set ln->pre.  Reads the arrays back to the host: synchronises the device; call it after the arrays have been written. */
+ * set ln->pre.  Reads the arrays back to the host: synchronises the device; call it after the arrays have been written.  C: a positive
+ * multiple of 4 up to 4096 (P2V_E_SHAPE otherwise). */
 size_t p2v_ln_prefold_bytes(int C);
 int p2v_ln_prefold(p2v_ln* ln, int C, float* buf, size_t buf_bytes);
 
@@ -398,8 +403,10 @@ int p2v_gemm_i8(int epilogue_kind, const int8_t* A, int lda, int M, int K, int N
                 const p2v_epilogue* epi, void* out, int ldo, int8_t* out_codes, void* stream);
 
 /* rows x C int8 -> rows x C int8; row r of the input starts at x + r*row_stride (lets the final norm
- * touch only the cls rows, vit_fquant.py:766-767).  C: a multiple of 4 up to 2048; out_stride >= C; bytes [C, out_stride) of an
- * output row are not written. */
+ * touch only the cls rows, vit_fquant.py:766-767).  C: a multiple of 4 up to 4096 (P2V_E_SHAPE beyond, before any launch; see the limits above for the bound
+ * on the PTF masks of rows wider than 2048); row_stride and out_stride: independent multiples of 4, out_stride >= C, and beyond 2048 channels
+ * row_stride >= C as well (P2V_E_SHAPE: input rows that overlap are taken only at the widths that took them before); bytes
+ * [C, out_stride) of an output row and rows >= `rows` are not written. */
 int p2v_int_layernorm(const int8_t* x, long long row_stride, int rows, int C, const p2v_ln* ln,
                       int8_t* out, long long out_stride, void* stream);
 

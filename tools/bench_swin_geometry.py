@@ -1,6 +1,6 @@
 """GPU: the patch 4 / window 12 / 384^2 Swin geometry next to 224^2 / window 7 in ONE call: sliced int8 forward rate as bench_swin runs
 it (warm-up, then timed loops bracketed by synchronisation), the rate per number of stream slices, and the per-kind launch times of
-SwinPlan.profile (window attention, GEMMs, LayerNorm) at the slice size.
+SwinPlan.profile (window attention, GEMMs, LayerNorm; the stand-alone LayerNorm launches of 1024 channels and more one by one) at the slice size.
 python tools/bench_swin_geometry.py [BATCH=64] [STEPS=10] [MODELS=swin_base_384,swin_base]"""
 import collections, contextlib, os, sys, time
 import torch
@@ -58,18 +58,23 @@ for name in names:
     Bl = (B + n_sl - 1) // n_sl
     prof = plan.profile(x[:Bl]); prof = plan.profile(x[:Bl])
     rec = plan._recorded[(Bl, 0, True)]
-    kinds, detail = collections.OrderedDict(), collections.OrderedDict()
+    kinds, detail, norms = collections.OrderedDict(), collections.OrderedDict(), collections.OrderedDict()
     for i, (kind, e, ms) in enumerate(prof):
         o = rec['ops'][i]
         a = kinds.setdefault(kind, [0, 0.0]); a[0] += 1; a[1] += ms
         if kind == 'window_attention':
             d = detail.setdefault('window_attention T=%d heads=%d ws=%d' % (o.i1, o.i2, o.wa.ws), [0, 0.0]); d[0] += 1; d[1] += ms
+        if kind == 'layernorm' and o.N >= 1024:            # the stand-alone LayerNorms of the wide stages and of the merges, by (channels, rows)
+            d = norms.setdefault((o.N, o.M), [0, 0.0]); d[0] += 1; d[1] += ms
     tot = sum(v[1] for v in kinds.values())
     print('  per-kind launch times, one slice of %d images on one stream (total %.2f ms):' % (Bl, tot))
     for k, (n, ms) in sorted(kinds.items(), key=lambda kv: -kv[1][1]):
         print('    %-18s x%3d  %8.3f ms  %5.1f %%  %8.2f us per image' % (k, n, ms, 100 * ms / tot, 1e3 * ms / Bl))
     for k, (n, ms) in detail.items():
         print('      %-40s x%3d  %8.3f ms  %7.2f ns per token and launch' % (k, n, ms, 1e6 * ms / n / (Bl * int(k.split('T=')[1].split()[0]))))
+    for (C_, rows), (n, ms) in norms.items():
+        print('      layernorm C=%-5d rows=%-6d              x%3d  %8.3f ms  %7.2f us per launch  %6.2f ps per row byte' % (
+            C_, rows, n, ms, 1e3 * ms / n, 1e9 * ms / n / (rows * C_)))
     del plan, model, x
     torch.cuda.empty_cache()
 if len(rates) == 2:
