@@ -44,10 +44,13 @@ from . import ddv  # noqa: F401
 from .ddv import AttackPGD, compute_ddv, gen_adv_inputs  # noqa: F401
 from . import score  # noqa: F401
 from .score import DeviceMeter, score_rows_reference  # noqa: F401
+from . import profiling  # noqa: F401
+from .profiling import gen_profiling_inputs_in_blackbox, metrics_output_diversity  # noqa: F401
 
 __all__ = ['BIT_TYPE_DICT', 'QAct', 'QConv2d', 'QIntLayerNorm', 'QIntSoftmax', 'QLinear', 'Config', 'VisionTransformer',
            'deit_tiny_patch16_224', 'deit_small_patch16_224', 'deit_base_patch16_224', 'vit_base_patch16_224',
            'vit_large_patch16_224', 'FrozenPlan', 'SwinTransformer', 'swin_tiny_patch4_window7_224',
            'swin_small_patch4_window7_224', 'swin_base_patch4_window7_224', 'swin_base_patch4_window12_384',
            'swin_large_patch4_window12_384', 'SwinPlan', 'get_activations', 'MinibatchCKA',
-           'MinibatchAdvCKA', 'compute_cka', 'compute_ddv', 'gen_adv_inputs', 'AttackPGD', 'DeviceMeter', 'score_rows_reference']
+           'MinibatchAdvCKA', 'compute_cka', 'compute_ddv', 'gen_adv_inputs', 'AttackPGD', 'DeviceMeter', 'score_rows_reference',
+           'gen_profiling_inputs_in_blackbox', 'metrics_output_diversity']

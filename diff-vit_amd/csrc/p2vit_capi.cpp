@@ -1325,6 +1325,72 @@ int p2v_score_accumulate(const int32_t* ranks, const double* loss, int rows, con
   return launch_rc(p2v_launch_score_accumulate(ranks, loss, rows, ks, n_k, totals_slot, (hipStream_t)stream), "score_accumulate");
 }
 
+// ---- search-based profiling inputs (p2vit_profile.hip) ---------------------------------------------------------------------------------
+static bool prof_sizes_ok(int n, int classes) { return n >= 1 && n <= P2V_PROFILE_MAX_N && classes >= 1 && classes <= P2V_PROFILE_MAX_CLASSES; }
+
+size_t p2v_profile_state_bytes(int n, int classes) { return prof_sizes_ok(n, classes) ? (size_t)p2v_profile_layout(n, classes).bytes : 0; }
+
+static int prof_state_check(const char* who, const void* state, size_t state_bytes, int n, int classes) {
+  if (!state) return fail(P2V_E_ARG, "%s: null state block", who);
+  if ((uintptr_t)state % 16) return fail(P2V_E_ARG, "%s: the state block must be 16-byte aligned", who);
+  if (!prof_sizes_ok(n, classes))
+    return fail(P2V_E_SHAPE, "%s: n %d (1 ... %d), classes %d (1 ... %d)", who, n, P2V_PROFILE_MAX_N, classes, P2V_PROFILE_MAX_CLASSES);
+  if (state_bytes < p2v_profile_state_bytes(n, classes))
+    return fail(P2V_E_WORKSPACE, "%s: state block %zu < %zu bytes", who, state_bytes, p2v_profile_state_bytes(n, classes));
+  return P2V_OK;
+}
+
+static int prof_image_check(const char* who, int n, long long image_elems, int idx, long long pos) {
+  if (n < 1 || n > P2V_PROFILE_MAX_N || image_elems < 1 || image_elems > (1LL << 30))
+    return fail(P2V_E_SHAPE, "%s: n %d (1 ... %d), image_elems %lld (1 ... 2^30)", who, n, P2V_PROFILE_MAX_N, image_elems);
+  if (idx < 0 || idx >= n) return fail(P2V_E_ARG, "%s: idx %d outside [0, %d)", who, idx, n);
+  if (pos < 0 || pos >= image_elems) return fail(P2V_E_ARG, "%s: pos %lld outside [0, %lld)", who, pos, image_elems);
+  return P2V_OK;
+}
+
+int p2v_profile_init(void* state, size_t state_bytes, int n, int classes, const float* logits1, const float* logits2, void* stream) {
+  if (!logits1 || !logits2) return fail(P2V_E_ARG, "p2v_profile_init: null logits");
+  if ((uintptr_t)logits1 % 4 || (uintptr_t)logits2 % 4) return fail(P2V_E_ARG, "p2v_profile_init: logits must be 4-byte aligned");
+  const int rc = prof_state_check("p2v_profile_init", state, state_bytes, n, classes);
+  if (rc != P2V_OK) return rc;
+  return launch_rc(p2v_launch_profile_init(state, n, classes, logits1, logits2, (hipStream_t)stream), "profile_init");
+}
+
+int p2v_profile_candidates(const float* inputs, int n, long long image_elems, int idx, long long pos, float epsilon, float* staging,
+                           void* stream) {
+  if (!inputs || !staging) return fail(P2V_E_ARG, "p2v_profile_candidates: null argument");
+  if ((uintptr_t)inputs % 16 || (uintptr_t)staging % 16) return fail(P2V_E_ARG, "p2v_profile_candidates: inputs and staging must be 16-byte aligned");
+  const int rc = prof_image_check("p2v_profile_candidates", n, image_elems, idx, pos);
+  if (rc != P2V_OK) return rc;
+  return launch_rc(p2v_launch_profile_candidates(inputs, image_elems, idx, pos, epsilon, staging, (hipStream_t)stream), "profile_candidates");
+}
+
+int p2v_profile_step(void* state, size_t state_bytes, int n, int classes, const float* cand1, const float* cand2, const float* staging,
+                     float* inputs, long long image_elems, int idx, long long pos, double* trace_row, void* stream) {
+  if (!cand1 || !cand2 || !staging || !inputs || !trace_row) return fail(P2V_E_ARG, "p2v_profile_step: null argument");
+  if ((uintptr_t)cand1 % 4 || (uintptr_t)cand2 % 4) return fail(P2V_E_ARG, "p2v_profile_step: candidate logits must be 4-byte aligned");
+  if ((uintptr_t)inputs % 16 || (uintptr_t)staging % 16) return fail(P2V_E_ARG, "p2v_profile_step: inputs and staging must be 16-byte aligned");
+  if ((uintptr_t)trace_row % 8) return fail(P2V_E_ARG, "p2v_profile_step: the trace row must be 8-byte aligned");
+  int rc = prof_state_check("p2v_profile_step", state, state_bytes, n, classes);
+  if (rc != P2V_OK) return rc;
+  rc = prof_image_check("p2v_profile_step", n, image_elems, idx, pos);
+  if (rc != P2V_OK) return rc;
+  return launch_rc(p2v_launch_profile_step(state, n, classes, cand1, cand2, staging, inputs, image_elems, idx, pos, trace_row,
+                                           (hipStream_t)stream), "profile_step");
+}
+
+int p2v_profile_diversity(const float* logits, long long ld, int n, int classes, double* out, void* ws, size_t ws_bytes, void* stream) {
+  if (!logits || !out || !ws) return fail(P2V_E_ARG, "p2v_profile_diversity: null argument");
+  if ((uintptr_t)logits % 4 || (uintptr_t)out % 8 || (uintptr_t)ws % 8)
+    return fail(P2V_E_ARG, "p2v_profile_diversity: logits must be 4-byte, out and ws 8-byte aligned");
+  if (!prof_sizes_ok(n, classes) || ld < classes)
+    return fail(P2V_E_SHAPE, "p2v_profile_diversity: n %d (1 ... %d), classes %d (1 ... %d), ld %lld", n, P2V_PROFILE_MAX_N, classes,
+                P2V_PROFILE_MAX_CLASSES, ld);
+  if (ws_bytes < (size_t)n * n * 8) return fail(P2V_E_WORKSPACE, "p2v_profile_diversity: workspace %zu < %zu bytes", ws_bytes, (size_t)n * n * 8);
+  return launch_rc(p2v_launch_profile_diversity(logits, ld, n, classes, reinterpret_cast<double*>(ws), out, (hipStream_t)stream),
+                   "profile_diversity");
+}
+
 int p2v_ddv_stage_count(const p2v_plan* plan, int with_linear) {
   if (!plan) return fail(P2V_E_ARG, "p2v_ddv_stage_count: null plan");
   return 5 * plan->d.depth + 3 + (with_linear ? 4 * plan->d.depth + 1 : 0);

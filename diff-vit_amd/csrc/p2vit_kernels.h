@@ -154,3 +154,17 @@ int p2v_launch_cos_combine(const CosDesc* descs_dev, int L, int n, const unsigne
 int p2v_launch_score_rows(const float* logits, long long ld, int rows, int classes, const long long* labels, int* ranks, double* loss,
                           hipStream_t st);
 int p2v_launch_score_accumulate(const int* ranks, const double* loss, int rows, const int* ks, int n_k, void* totals, hipStream_t st);
+
+// search-based profiling inputs (p2vit_profile.hip): the state block of p2v_profile_* and its launches
+struct ProfLayout {        // offsets into the state block; doubles first, then the fp32 tables
+  int n, classes;
+  long long d[2], g[2], rowd[2], rowg[2];      // in doubles: D [n][n], g [n], rowd [2][n], rowg [2] per model; the score is double 0
+  long long o[2], o0[2];                        // in floats from the block's start: O [n][classes], O0 [n][classes] per model
+  long long bytes;
+};
+ProfLayout p2v_profile_layout(int n, int classes);
+int p2v_launch_profile_init(void* state, int n, int classes, const float* logits1, const float* logits2, hipStream_t st);
+int p2v_launch_profile_candidates(const float* inputs, long long elems, int idx, long long pos, float eps, float* staging, hipStream_t st);
+int p2v_launch_profile_step(void* state, int n, int classes, const float* cand1, const float* cand2, const float* staging, float* inputs,
+                            long long elems, int idx, long long pos, double* trace, hipStream_t st);
+int p2v_launch_profile_diversity(const float* logits, long long ld, int n, int classes, double* ws, double* out, hipStream_t st);

@@ -31,7 +31,9 @@ QIntLayerNorm modules of a fused model - they never fire, because the engine byp
 served, see ``cka``).
 
 ``python -m diff_vit_amd.ddv --model deit_small --bits 8 --n 50`` (or ``--model swin_tiny``; ``--bits mixed`` is refused for Swin) prints
-the float-vs-quantized similarity per stage on the synthetic data of ``harness`` and writes ``ddv_result/ddv.pkl``."""
+the float-vs-quantized similarity per stage on the synthetic data of ``harness`` and writes ``ddv_result/ddv.pkl``.  ``--inputs blackbox
+--mut-iters 1000`` takes the perturbed twins from ``profiling.gen_profiling_inputs_in_blackbox`` on (float model, quantized model) instead
+of PGD (the default, ``--inputs pgd``)."""
 import argparse
 import copy
 import os
@@ -314,6 +316,9 @@ def main(argv=None):
     p.add_argument('--bits', default='8', choices=['8', '4', 'mixed'])
     p.add_argument('--n', default=50, type=int, help='seed samples')
     p.add_argument('--steps', default=50, type=int, help='PGD steps')
+    p.add_argument('--inputs', default='pgd', choices=['pgd', 'blackbox'],
+                   help='the perturbed twins: PGD on the float model, or ModelDiff\'s black-box search on (float, quantized)')
+    p.add_argument('--mut-iters', default=1000, type=int, help='iterations of the black-box search (--inputs blackbox)')
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--device', default='cuda')
     p.add_argument('--result-name', default='ddv_result')
@@ -339,8 +344,14 @@ def main(argv=None):
         bits = {'8': [8] * L, '4': [4] * L, 'mixed': [8 if (i * 7 + 3) % 5 < 3 else 4 for i in range(L)]}[args.bits]
     x = synth.images(args.seed + 2, args.n, fp.arch['img_size']).to(device)
     x = (x - x.amin()) / (x.amax() - x.amin())                      # the attack works on images in [0, 1]
-    torch.manual_seed(args.seed)
-    adv = gen_adv_inputs(fp, x, num_steps=args.steps)
+    if args.inputs == 'blackbox':
+        import numpy as np
+        from . import profiling
+        adv = profiling.gen_profiling_inputs_in_blackbox(fp, None, q, bits, x, max_iterations=args.mut_iters,
+                                                         rng=np.random.RandomState(args.seed))
+    else:
+        torch.manual_seed(args.seed)
+        adv = gen_adv_inputs(fp, x, num_steps=args.steps)
     d_fp = compute_ddv(fp, x, adv, None)
     d_q = compute_ddv(q, x, adv, bits)
     sim, ref = similarity(d_fp, d_q), reference_similarity(d_fp, d_q)

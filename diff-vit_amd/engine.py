@@ -163,6 +163,13 @@ def lib():
         L.p2v_score_totals_bytes.argtypes = [_i]
         L.p2v_score_totals_bytes.restype = C.c_size_t
         L.p2v_score_accumulate.argtypes = [_p, _p, _i, C.POINTER(C.c_int), _i, _p, _p]
+    if hasattr(L, 'p2v_profile_step'):            # the profiling-input search is additive, found by its symbols
+        L.p2v_profile_state_bytes.argtypes = [_i, _i]
+        L.p2v_profile_state_bytes.restype = C.c_size_t
+        L.p2v_profile_init.argtypes = [_p, C.c_size_t, _i, _i, _p, _p, _p]
+        L.p2v_profile_candidates.argtypes = [_p, _i, _ll, _i, _ll, _f, _p, _p]
+        L.p2v_profile_step.argtypes = [_p, C.c_size_t, _i, _i, _p, _p, _p, _p, _ll, _i, _ll, _p, _p]
+        L.p2v_profile_diversity.argtypes = [_p, _ll, _i, _i, _p, _p, C.c_size_t, _p]
     L.p2v_forward_profile.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_int32), _i]
     L.p2v_forward_profile_begin.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(_p)]

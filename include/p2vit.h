@@ -663,6 +663,56 @@ int p2v_score_logits(const float* logits, long long ld, int rows, int classes, c
 size_t p2v_score_totals_bytes(int n_k);
 int p2v_score_accumulate(const int32_t* ranks, const double* loss, int rows, const int* ks, int n_k, void* totals_slot, void* stream);
 
+/* ---- Search-based profiling inputs (additive: no structure, existing entry point or P2V_ABI_VERSION changes; a binding finds it by its
+ * symbols) --------------------------------------------------------------------------------------------------------------------------
+ * ModelDiff's Algorithm 1 as the reference runs it (dataset_utility.py:193-302), with the state of the search in device memory.  For the
+ * logits O [n][classes] (fp32, taken in fp64) of a model on the current inputs and O0 on the seed inputs:
+ *   dist(a, b)  = sqrt(sum_k ((double)a_k - (double)b_k)^2)
+ *   diversity   = (sum over all n^2 ordered pairs (i, j) of dist(O_i, O_j)) / n^2        np.mean(cdist(O, O)), diagonal zeros included
+ *   divergence  = (sum_i dist(O_i, O0_i)) / n
+ *   score       = divergence1 * divergence2 * diversity1 * diversity2, multiplied in this order in fp64      (dataset_utility.py:258)
+ * An iteration mutates ONE element `pos` of ONE image `idx` by +epsilon ("right", candidate 0) and by -epsilon ("left", candidate 1), so
+ * only row idx of O, row and column idx of the distance matrix D and entry idx of the divergence terms g change.
+ *
+ * The STATE BLOCK (device memory of the caller, 16-byte aligned, p2v_profile_state_bytes(n, classes) bytes; 0 = outside the limits):
+ *   double score, one double of padding; per model D [n][n], g [n], rowd [2][n], rowg [2] (fp64; rowd / rowg: the candidates' distances
+ *   of the last step); then per model O [n][classes], O0 [n][classes] (fp32, dense).
+ * LIMITS: 1 <= n <= P2V_PROFILE_MAX_N, 1 <= classes <= P2V_PROFILE_MAX_CLASSES, 1 <= image_elems <= 2^30.
+ *
+ * p2v_profile_init        fills the block from the two models' logits of the seed inputs (dev fp32 [n][classes], dense): O = O0 = logits,
+ *                         D, g (= 0) and the score (five launches).
+ * p2v_profile_candidates  writes image idx of inputs (dev fp32 [n][image_elems]) twice into staging (dev fp32 [2][image_elems]) with
+ *                         element pos replaced by x + epsilon (candidate 0) and x - epsilon (candidate 1): fp32 additions, no clipping.
+ *                         16-byte copies where source and destination chunk are aligned, scalar otherwise.  One launch.
+ * p2v_profile_step        cand1 / cand2 (dev fp32 [2][classes], dense): the logits of model 1 / model 2 on the staging batch.  Launch 1: the
+ *                         n distances from each candidate row to the rows of O (0 in the row's own slot) and its divergence term, into
+ *                         rowd / rowg.  Launch 2 (one workgroup): per candidate the n^2 positions of D with row and column idx replaced,
+ *                         added in one fixed position order, the n entries of g likewise, the score; then the rule of
+ *                         dataset_utility.py:292-301 against the stored score (IEEE comparisons):
+ *                             right <= score and left <= score: keep (0);  else right > left: take right (1);  else take left (2).
+ *                         On 1 / 2 it commits row and column idx of D, g[idx], row idx of O of both models, the score, and copies
+ *                         staging[candidate][pos] to inputs[idx][pos].  Always writes trace_row (dev fp64 [4]) = { score_right,
+ *                         score_left, decision, score after }.
+ * p2v_profile_diversity   the diversity of one logits tensor (dev fp32 [n][ld], ld >= classes) into *out (dev fp64); ws: n * n * 8 bytes
+ *                         of device memory, 8-byte aligned.  Two launches.
+ * Every distance comes from one device function with one operand and summation order (independent of pointer alignment), and every sum
+ * runs over the positions after the substitution - the initial score too.  So a candidate whose two logits rows equal the current rows bit
+ * for bit scores BIT-EQUAL to the stored score and the inputs are kept, as the reference's `<=` does (an input-quantised model, epsilon
+ * below the input step).  No atomics; results are bitwise repeatable.  A kernel writes the elements of its result and nothing else.
+ * Nothing here allocates, frees or synchronises; launches of one search are ordered by the one stream they are enqueued on.
+ * P2V_E_ARG: null pointer; state / inputs / staging not 16-byte, trace_row / out / ws not 8-byte, logits / cand not 4-byte aligned; idx
+ * outside [0, n), pos outside [0, image_elems).  P2V_E_SHAPE: n, classes, image_elems outside the limits, ld < classes.  P2V_E_WORKSPACE:
+ * state_bytes / ws_bytes too small.  All of them before the first HIP call. */
+#define P2V_PROFILE_MAX_N 1024
+#define P2V_PROFILE_MAX_CLASSES 65536
+size_t p2v_profile_state_bytes(int n, int classes);
+int p2v_profile_init(void* state, size_t state_bytes, int n, int classes, const float* logits1, const float* logits2, void* stream);
+int p2v_profile_candidates(const float* inputs, int n, long long image_elems, int idx, long long pos, float epsilon, float* staging,
+                           void* stream);
+int p2v_profile_step(void* state, size_t state_bytes, int n, int classes, const float* cand1, const float* cand2, const float* staging,
+                     float* inputs, long long image_elems, int idx, long long pos, double* trace_row, void* stream);
+int p2v_profile_diversity(const float* logits, long long ld, int n, int classes, double* out, void* ws, size_t ws_bytes, void* stream);
+
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
 
