@@ -84,6 +84,7 @@ struct p2v_plan {
   float inv_s_input;
   p2v_epilogue embed_epi;
   const int8_t* cls_codes;
+  const int8_t* embed_cls_codes = nullptr;   // p2v_plan_set_embed_tap_cls: the class row of the qact_embed plane (FULL DDV stages), or null
   bool embed_set;
   std::vector<p2v_block> blocks;
   std::vector<char> block_set;
@@ -263,6 +264,12 @@ int p2v_plan_set_embed(p2v_plan* plan, float inv_s_input, const p2v_epilogue* e,
   plan->embed_epi.patches = plan->patches;
   plan->cls_codes = cls_row_codes;
   plan->embed_set = true;
+  return P2V_OK;
+}
+
+int p2v_plan_set_embed_tap_cls(p2v_plan* plan, const int8_t* cls_embed_codes) {
+  if (!plan || !cls_embed_codes) return fail(P2V_E_ARG, "p2v_plan_set_embed_tap_cls: null argument");
+  plan->embed_cls_codes = cls_embed_codes;
   return P2V_OK;
 }
 
@@ -512,7 +519,7 @@ static GemmArgs gemm_args(const int8_t* A, int lda, int M, const int8_t* W, int 
                           void* out, int ldo, int8_t* out_codes) {
   GemmArgs g;
   g.A = A; g.lda = lda; g.M = M; g.W = W; g.K = K; g.N = N; g.w4 = lin.packed4 ? 1 : 0;
-  g.colscale = lin.colscale; g.bias = lin.bias; g.ep = ep; g.out = out; g.ldo = ldo; g.out_codes = out_codes; g.tiles_n = 0;
+  g.colscale = lin.colscale; g.bias = lin.bias; g.ep = ep; g.out = out; g.ldo = ldo; g.out_codes = out_codes; g.out_codes2 = nullptr; g.tiles_n = 0;
 #ifdef P2V_DIAG
   g.stamps = nullptr;
 #endif
@@ -560,10 +567,13 @@ struct DdvCtx {
   double* sums;
   float* tap;                     // the one fp32 tap buffer of with_linear, or null
   int stage;
+  float* scratch = nullptr;       // P2V_DDV_STAGES_FULL: the same buffer, for the fp32 LayerNorm values (set whatever with_linear says); null = the engine stages
 };
-static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st) {
-  const size_t esz = dtype == P2V_COS_I8 ? 1 : 4;
-  const p2v_cos_layer l{base, reinterpret_cast<const char*>(base) + (size_t)c->n * rows * cols * esz, scale, (long long)rows * cols, cols, rows, cols, dtype};
+// sample_stride (elements): 0 = the samples are dense, rows * cols apart; else e.g. the patch rows of a [T][cols] token layout
+static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st, long long sample_stride = 0) {
+  const size_t esz = dtype == P2V_COS_F32 ? 4 : 1;
+  if (!sample_stride) sample_stride = (long long)rows * cols;
+  const p2v_cos_layer l{base, reinterpret_cast<const char*>(base) + (size_t)c->n * sample_stride * esz, scale, sample_stride, cols, rows, cols, dtype};
   const CosDesc d = p2v_cos_desc(l, c->n, 0);        // (logits / head rows of a class count that is no multiple of 4: d.vec = 0, scalar loads)
   if ((long long)c->n * d.nsplit > c->slots)
     return fail(P2V_E_WORKSPACE, "p2v_forward_ddv: a stage of %d x %d needs %lld partials, the workspace holds %lld", rows, cols,
@@ -634,10 +644,15 @@ struct Fwd {
   // DDV stages (p2v_forward_ddv): the int8 codes a launch has just completed, fp32 values, and the fp32 tap that sits in the one tap buffer
   int ddv_i8(const void* buf, int rows, int cols, const float* scale) { return (done || !o.ddv) ? P2V_OK : ddv_reduce(o.ddv, buf, rows, cols, P2V_COS_I8, scale, st); }
   int ddv_f32(const void* buf, int rows, int cols) { return (done || !o.ddv) ? P2V_OK : ddv_reduce(o.ddv, buf, rows, cols, P2V_COS_F32, nullptr, st); }
+  // codes of a QAct with per-channel (PTF) scales as the fp32 values a hook on it sees, RN(code * scale[c])
+  int ddv_i8_deq(const void* buf, int rows, int cols, const float* scale) { return (done || !o.ddv) ? P2V_OK : ddv_reduce(o.ddv, buf, rows, cols, P2V_COS_I8_DEQ, scale, st); }
   int ddv_tap(int rows, int cols) { return (o.ddv && o.ddv->tap) ? ddv_f32(o.ddv->tap, rows, cols) : P2V_OK; }
+  // P2V_DDV_STAGES_FULL: the stages behind the reference's remaining hook points (LayerNorm values, the mid codes of the stem and of proj / fc2)
+  float* full() const { return (!done && o.ddv) ? o.ddv->scratch : nullptr; }
   int layernorm(const LnArgs& a) { return step(P2V_K_LAYERNORM, [&] { return launch_rc(p2v_launch_layernorm(a, st), "int_layernorm"); }); }
-  int gemm(int kind, bool few, int epi, const int8_t* A, int lda, int rows, int K, int N, const p2v_linear& lin, const p2v_epilogue& ep, void* out, int ldo) {
-    return step(kind, [&] { return run_gemm(epi, A, lda, rows, K, N, lin, ep, out, ldo, nullptr, st, few); });
+  int gemm(int kind, bool few, int epi, const int8_t* A, int lda, int rows, int K, int N, const p2v_linear& lin, const p2v_epilogue& ep, void* out, int ldo,
+           int8_t* out_codes = nullptr) {
+    return step(kind, [&] { return run_gemm(epi, A, lda, rows, K, N, lin, ep, out, ldo, out_codes, st, few); });
   }
   // QIntLayerNorm of `rows` rows of x -> QLinear -> `out`: one fused launch where the kernel covers the shape and the layer has fragment-order
   // weights (the LayerNorm codes then stay in LDS; parity runs read the workspace, so for them the kernel writes them too), else the
@@ -646,6 +661,12 @@ struct Fwd {
                 int8_t* out, bool few) {
     LnArgs ln{X, stride, rows, D, norm, LN, D};
     ln.pre = norm.pre;
+    if (float* vals = full()) {     // FULL DDV stages: the unfused pair, the LayerNorm's values reduced before the GEMM's tap reuses the buffer
+      ln.tap_out = vals;
+      int rc = layernorm(ln);
+      if (rc || (rc = ddv_f32(vals, T, D))) return rc;                                                           // norm1 / norm2
+      return gemm(k_gemm, few, epi, LN, D, rows, Dk, N, lin, e, out, N);
+    }
     if (!few && lin.w_frag && p2v_ln_gemm_supported(epi, D, N, e.gelu.table ? e.gelu.cells : 0)) {
       if (o.stop_after < 0) ln.out = nullptr;
       return step(k_fused, [&] { return run_ln_gemm(epi, ln, lin, e, N, out, st); });
@@ -677,8 +698,11 @@ struct Fwd {
     p2v_epilogue ep = b.proj_epi;
     ep.residual = X;
     ep.resid_tab = p->resid_tab[(size_t)i * 4 + bp];
-    if ((rc = gemm(P2V_K_GEMM_PROJ, rs.few, P2V_EPI_RESID, ATT, ldx, rs.rows, Dk, D, proj, ep, X, ldx))) return rc;
-    if ((rc = lin_tap(2 + 4 * i, ATT, ldx, rs.rows, Dk, D, proj)) || (rc = ddv_tap(T, D)) || (rc = ddv_i8(X, T, D, b.proj_epi.s_next))) return rc;   // attn.proj, Block.qact2
+    // (FULL DDV stages: the codes of attn.qact3 go to ln, which nothing reads between norm1's GEMM and norm2)
+    if ((rc = gemm(P2V_K_GEMM_PROJ, rs.few, P2V_EPI_RESID, ATT, ldx, rs.rows, Dk, D, proj, ep, X, ldx, full() ? LN : nullptr))) return rc;
+    if ((rc = lin_tap(2 + 4 * i, ATT, ldx, rs.rows, Dk, D, proj)) || (rc = ddv_tap(T, D))) return rc;            // attn.proj
+    if (full() && (rc = ddv_i8_deq(LN, T, D, b.proj_epi.s_mid))) return rc;                                      // attn.qact3
+    if ((rc = ddv_i8(X, T, D, b.proj_epi.s_next))) return rc;                                                    // Block.qact2
     // norm2 (attention's channel scale!) -> /mlp.channel_scale -> mlp.qact0 -> fc1 -> GELU -> qact1     vit_fquant.py:464, layers_quant.py:305-316,331-333
     p2v_epilogue e1{};
     e1.inv_s_out = b.inv_s_fc1;
@@ -690,8 +714,9 @@ struct Fwd {
     p2v_epilogue e2 = b.fc2_epi;
     e2.residual = X;
     e2.resid_tab = p->resid_tab[(size_t)i * 4 + 2 + b2];
-    if ((rc = gemm(P2V_K_GEMM_FC2, rs.few, P2V_EPI_RESID, HID, Hd, rs.rows, Hk, D, fc2, e2, X, ldx))) return rc;
+    if ((rc = gemm(P2V_K_GEMM_FC2, rs.few, P2V_EPI_RESID, HID, Hd, rs.rows, Hk, D, fc2, e2, X, ldx, full() ? LN : nullptr))) return rc;
     if ((rc = lin_tap(4 + 4 * i, HID, Hd, rs.rows, Hk, D, fc2)) || (rc = ddv_tap(T, D))) return rc;             // mlp.fc2
+    if (full() && (rc = ddv_i8_deq(LN, T, D, b.fc2_epi.s_mid))) return rc;                                       // mlp.qact2
     return ddv_i8(X, T, D, b.fc2_epi.s_next);                                                                    // Block.qact4
   }
 };
@@ -726,9 +751,24 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
       return o.u8 ? launch_rc(p2v_launch_u8_patchify(o.u8, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, o.layout, (const int8_t*)o.lut, f.P, Kp, st), "u8_patchify")
                   : launch_rc(p2v_launch_patchify(o.images, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, p->inv_s_input, f.P, Kp, st), "quantize_patchify");
     });
-    if (rc || (rc = f.gemm(P2V_K_GEMM_EMBED, false, P2V_EPI_EMBED, f.P, Kp, rows_p, Kp, D, embed, p->embed_epi, f.X, D)) ||
-        (rc = f.lin_tap(0, f.P, Kp, rows_p, Kp, D, embed)))
+    if (rc) return rc;
+    if (f.full()) {
+      // FULL DDV stages of the stem: the patch matrix (qact_input: a permutation of the image's codes plus zero columns), then the EMBED launch
+      // with its two mid-code planes in qkv (free until block 0), both [M][D] in the token layout of x: patch_embed.qact over the patch rows,
+      // qact_embed over all rows once the constant class row is filled in
+      int8_t *pe = f.QKV, *em = f.QKV + (size_t)f.M * D;
+      GemmArgs g = gemm_args(f.P, Kp, rows_p, embed.w_codes, Kp, D, embed, p->embed_epi, f.X, D, pe);
+      g.out_codes2 = em;
+      if ((rc = f.ddv_i8(f.P, p->patches, Kp, nullptr)) ||                                                        // qact_input
+          (rc = f.step(P2V_K_GEMM_EMBED, [&] { return launch_rc(p2v_launch_gemm(P2V_EPI_EMBED, g, st), "gemm_i8"); })) ||
+          (rc = ddv_reduce(o.ddv, pe + D, p->patches, D, P2V_COS_I8, nullptr, st, (long long)T * D)) ||           // patch_embed.qact
+          (rc = launch_rc(p2v_launch_fill_cls(em, batch, T, D, p->embed_cls_codes, st), "fill_cls")) ||
+          (rc = f.ddv_i8(em, T, D, nullptr)))                                                                     // qact_embed
+        return rc;
+    } else if ((rc = f.gemm(P2V_K_GEMM_EMBED, false, P2V_EPI_EMBED, f.P, Kp, rows_p, Kp, D, embed, p->embed_epi, f.X, D))) {
       return rc;
+    }
+    if ((rc = f.lin_tap(0, f.P, Kp, rows_p, Kp, D, embed))) return rc;
   } else {
     // input_quant = False (vit_fquant.py:705, the vit_large factory :925): the fp32 image feeds the fake-quantised convolution
     if (embed.packed4) return fail(P2V_E_UNSUPPORTED, "input_quant = False: the patch-embed weights must be unpacked codes (packed4 = 0)");
@@ -754,6 +794,12 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
     if ((rc = f.block(i, bit_config + 1 + 4 * i, (cls_only && i == d.depth - 1) ? cls_rows : all_rows))) return rc;
 
   // norm over the cls rows only ([:,0]) -> qact2 -> head -> act_out         vit_fquant.py:766-796
+  if (float* vals = f.full()) {      // FULL DDV stages: the hook on `norm` sits in front of [:, 0] - the final norm once more, over every row (codes into ln)
+    LnArgs la{f.X, D, f.M, D, p->final_ln, f.LN, D};
+    la.pre = p->final_ln.pre;
+    la.tap_out = vals;
+    if ((rc = launch_rc(p2v_launch_layernorm(la, st), "int_layernorm")) || (rc = f.ddv_f32(vals, T, D))) return rc;   // norm
+  }
   LnArgs lf{f.X, (long long)T * D, batch, D, p->final_ln, f.CLS, D};
   lf.pre = p->final_ln.pre;
   if ((rc = f.layernorm(lf)) || (rc = f.ddv_i8(f.CLS, 1, D, nullptr))) return rc;                               // qact2
@@ -898,12 +944,38 @@ int p2v_gemm_i8(int kind, const int8_t* A, int lda, int M, int K, int N, const p
   if (kind == P2V_EPI_GELU && check_gelu_tab("p2v_gemm_i8", epi->gelu) != P2V_OK) return P2V_E_ARG;
   if (kind == P2V_EPI_RESID && (!epi->s_mid || !epi->s_res || !epi->s_next || !epi->residual)) return fail(P2V_E_ARG, "RESID epilogue needs s_mid/s_res/s_next/residual");
   if (kind == P2V_EPI_EMBED && (!epi->s_next || !epi->pos_deq || epi->patches <= 0)) return fail(P2V_E_ARG, "EMBED epilogue needs s_next/pos_deq/patches");
-  if (kind == P2V_EPI_RESID && out_codes) {      // the mid-code tap: 16-byte stores like `out`, int8-stored weights
+  if (kind == P2V_EPI_RESID && out_codes) {      // the mid-code tap: 16-byte stores like `out`, int8-stored weights (packed int4: p2v_gemm_resid_tap)
     if ((uintptr_t)out_codes % 16 || (uintptr_t)out % 16) return fail(P2V_E_ARG, "p2v_gemm_i8: RESID out_codes and out must be 16-byte aligned");
-    if (lin->packed4) return fail(P2V_E_UNSUPPORTED, "p2v_gemm_i8: the RESID mid-code tap takes int8-stored weights (packed4 = 0)");
+    if (lin->packed4) return fail(P2V_E_UNSUPPORTED, "p2v_gemm_i8: the RESID mid-code tap takes int8-stored weights (packed4 = 0); p2v_gemm_resid_tap takes both");
   }
   if (kind != P2V_EPI_RESID && kind != P2V_EPI_HEAD) out_codes = nullptr;
   return run_gemm(kind, A, lda, M, K, N, *lin, *epi, out, ldo, out_codes, (hipStream_t)stream);
+}
+
+int p2v_gemm_resid_tap(const int8_t* A, int lda, int M, int K, int N, const p2v_linear* lin, const p2v_epilogue* epi, int8_t* out, int ldo,
+                       int8_t* out_codes, void* stream) {
+  if (!A || !lin || !epi || !out || !out_codes) return fail(P2V_E_ARG, "p2v_gemm_resid_tap: null argument");
+  if (M <= 0 || N <= 0 || K <= 0 || K % GBK_PAD) return fail(P2V_E_SHAPE, "K=%d must be a positive multiple of %d", K, GBK_PAD);
+  if (N % 16 || ldo % 16 || lda % 16) return fail(P2V_E_UNSUPPORTED, "p2v_gemm_resid_tap: N, lda and ldo must be multiples of 16");
+  if (lda <= 0 || ldo < N) return fail(P2V_E_SHAPE, "p2v_gemm_resid_tap: lda=%d must be positive and ldo=%d must cover the %d outputs of a row", lda, ldo, N);
+  if (!epi->s_mid || !epi->s_res || !epi->s_next || !epi->residual) return fail(P2V_E_ARG, "RESID epilogue needs s_mid/s_res/s_next/residual");
+  if ((uintptr_t)out_codes % 16 || (uintptr_t)out % 16) return fail(P2V_E_ARG, "p2v_gemm_resid_tap: out_codes and out must be 16-byte aligned");
+  if ((long long)M * ldo >= (1LL << 32)) return fail(P2V_E_SHAPE, "p2v_gemm_resid_tap: M * ldo = %lld passes the 32-bit offsets of the tapped stores", (long long)M * ldo);
+  return run_gemm(P2V_EPI_RESID, A, lda, M, K, N, *lin, *epi, out, ldo, out_codes, (hipStream_t)stream);
+}
+
+int p2v_gemm_embed_tap(const int8_t* A, int lda, int M, int K, int N, const p2v_linear* lin, const p2v_epilogue* epi, int8_t* out, int ldo,
+                       int8_t* pe_codes, int8_t* embed_codes, void* stream) {
+  if (!A || !lin || !epi || !out || !pe_codes || !embed_codes) return fail(P2V_E_ARG, "p2v_gemm_embed_tap: null argument");
+  if (M <= 0 || N <= 0 || K <= 0 || K % GBK_PAD) return fail(P2V_E_SHAPE, "K=%d must be a positive multiple of %d", K, GBK_PAD);
+  if (N % 16 || ldo % 16 || lda % 16) return fail(P2V_E_UNSUPPORTED, "p2v_gemm_embed_tap: N, lda and ldo must be multiples of 16");
+  if (lda <= 0 || ldo < N) return fail(P2V_E_SHAPE, "p2v_gemm_embed_tap: lda=%d must be positive and ldo=%d must cover the %d outputs of a row", lda, ldo, N);
+  if (!epi->s_next || !epi->pos_deq || epi->patches <= 0) return fail(P2V_E_ARG, "EMBED epilogue needs s_next/pos_deq/patches");
+  if ((uintptr_t)out % 16 || (uintptr_t)pe_codes % 16 || (uintptr_t)embed_codes % 16)
+    return fail(P2V_E_ARG, "p2v_gemm_embed_tap: out, pe_codes and embed_codes must be 16-byte aligned");
+  GemmArgs g = gemm_args(A, lda, M, lin->w_codes, K, N, *lin, *epi, out, ldo, pe_codes);
+  g.out_codes2 = embed_codes;
+  return launch_rc(p2v_launch_gemm(P2V_EPI_EMBED, g, (hipStream_t)stream), "gemm_i8");
 }
 
 size_t p2v_ln_prefold_bytes(int C) { return C > 0 ? (size_t)2 * round_up(C, 256) * sizeof(float) : 0; }
@@ -953,6 +1025,20 @@ int p2v_int_layernorm(const int8_t* x, long long row_stride, int rows, int C, co
     return fail(P2V_E_SHAPE, "p2v_int_layernorm: C=%d beyond 2048 channels needs row_stride >= C (got %lld)", C, row_stride);
   LnArgs a{x, row_stride, rows, C, *ln, out, out_stride};
   a.pre = ln->pre;                       // optional: constants folded ahead of the launch (p2v_ln_prefold)
+  return launch_rc(p2v_launch_layernorm(a, (hipStream_t)stream), "int_layernorm");
+}
+
+int p2v_int_layernorm_tap(const int8_t* x, long long row_stride, int rows, int C, const p2v_ln* ln, int8_t* out, long long out_stride,
+                          float* tap_out, void* stream) {
+  if (!x || !ln || !out || !tap_out) return fail(P2V_E_ARG, "p2v_int_layernorm_tap: null argument");
+  if (C % 4 || row_stride % 4 || out_stride % 4) return fail(P2V_E_UNSUPPORTED, "C and strides must be multiples of 4");
+  if (rows <= 0) return fail(P2V_E_SHAPE, "rows must be positive");
+  if (C <= 0 || row_stride < 0 || out_stride < C) return fail(P2V_E_SHAPE, "p2v_int_layernorm_tap: C=%d must be positive, row_stride non-negative, out_stride >= C", C);
+  if (C > 2048) return fail(P2V_E_UNSUPPORTED, "p2v_int_layernorm_tap: C=%d, the value tap covers rows of up to 2048 channels", C);
+  if ((uintptr_t)tap_out % 16) return fail(P2V_E_ARG, "p2v_int_layernorm_tap: tap_out must be 16-byte aligned");
+  LnArgs a{x, row_stride, rows, C, *ln, out, out_stride};
+  a.pre = ln->pre;
+  a.tap_out = tap_out;
   return launch_rc(p2v_launch_layernorm(a, (hipStream_t)stream), "int_layernorm");
 }
 
@@ -1391,20 +1477,25 @@ int p2v_profile_diversity(const float* logits, long long ld, int n, int classes,
                    "profile_diversity");
 }
 
-int p2v_ddv_stage_count(const p2v_plan* plan, int with_linear) {
+int p2v_ddv_stage_count_ex(const p2v_plan* plan, int with_linear, int stage_set) {
   if (!plan) return fail(P2V_E_ARG, "p2v_ddv_stage_count: null plan");
-  return 5 * plan->d.depth + 3 + (with_linear ? 4 * plan->d.depth + 1 : 0);
+  if (stage_set != P2V_DDV_STAGES_ENGINE && stage_set != P2V_DDV_STAGES_FULL)
+    return fail(P2V_E_ARG, "p2v_ddv_stage_count_ex: unknown stage_set %d (P2V_DDV_STAGES_ENGINE = 0, P2V_DDV_STAGES_FULL = 1)", stage_set);
+  return 5 * plan->d.depth + 3 + (with_linear ? 4 * plan->d.depth + 1 : 0) + (stage_set == P2V_DDV_STAGES_FULL ? 4 * plan->d.depth + 4 : 0);
 }
+int p2v_ddv_stage_count(const p2v_plan* plan, int with_linear) { return p2v_ddv_stage_count_ex(plan, with_linear, P2V_DDV_STAGES_ENGINE); }
 
 // workgroups of the largest stage: p2v_cos_desc gives a sample at most 2048 / n (>= 1) splits while its rows stay below 2^16 per split -
 // true of every stage here (at most 4096 tokens); ddv_reduce checks each stage against this count before it launches
 static long long ddv_partial_slots(int n) { return n > 2048 ? n : 2048; }
 static size_t ddv_partial_bytes(int n) { return (size_t)ddv_partial_slots(n) * 3 * sizeof(unsigned long long); }
 
-size_t p2v_ddv_workspace_bytes(const p2v_plan* plan, int n) {
-  if (!plan || n <= 0 || n > (1 << 29)) return 0;
+// (the FULL stages live in buffers of the forward's workspace that are free where they are taken: the size does not depend on the stage set)
+size_t p2v_ddv_workspace_bytes_ex(const p2v_plan* plan, int n, int stage_set) {
+  if (!plan || n <= 0 || n > (1 << 29) || (stage_set != P2V_DDV_STAGES_ENGINE && stage_set != P2V_DDV_STAGES_FULL)) return 0;
   return ws_layout(plan, 2 * n).total + ddv_partial_bytes(n);        // (the forward's part is a multiple of 256 bytes)
 }
+size_t p2v_ddv_workspace_bytes(const p2v_plan* plan, int n) { return p2v_ddv_workspace_bytes_ex(plan, n, P2V_DDV_STAGES_ENGINE); }
 
 size_t p2v_ddv_tap_scratch_bytes(const p2v_plan* plan, int n) {
   if (!plan || n <= 0 || n > (1 << 29)) return 0;
@@ -1413,14 +1504,23 @@ size_t p2v_ddv_tap_scratch_bytes(const p2v_plan* plan, int n) {
   return (tok > head ? tok : head) * sizeof(float);
 }
 
-int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
-                    size_t ws_bytes, int with_linear, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream) {
+int p2v_forward_ddv_ex(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                       size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream) {
   if (!plan || !sums || !ws) return fail(P2V_E_ARG, "p2v_forward_ddv: null argument");
+  if (stage_set != P2V_DDV_STAGES_ENGINE && stage_set != P2V_DDV_STAGES_FULL)
+    return fail(P2V_E_ARG, "p2v_forward_ddv_ex: unknown stage_set %d (P2V_DDV_STAGES_ENGINE = 0, P2V_DDV_STAGES_FULL = 1)", stage_set);
+  const bool full = stage_set == P2V_DDV_STAGES_FULL;
   if (n <= 0 || n > (1 << 29)) return fail(P2V_E_SHAPE, "p2v_forward_ddv: n = %d pairs", n);
   if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_forward_ddv: the workspace must be 256-byte aligned");
+  if (full && !(plan->inv_s_input > 0.f))
+    return fail(P2V_E_UNSUPPORTED, "p2v_forward_ddv_ex: the FULL stage set needs the input QAct (input_quant = False has no qact_input stage)");
+  if (full && !plan->embed_cls_codes)
+    return fail(P2V_E_STATE, "p2v_forward_ddv_ex: the FULL stage set needs the class row of qact_embed (p2v_plan_set_embed_tap_cls)");
   const size_t fwd = ws_layout(plan, 2 * n).total;
   if (ws_bytes < fwd + ddv_partial_bytes(n)) return fail(P2V_E_WORKSPACE, "p2v_forward_ddv: workspace %zu < %zu bytes", ws_bytes, fwd + ddv_partial_bytes(n));
-  if (with_linear) {
+  if (full && !tap_scratch)
+    return fail(P2V_E_WORKSPACE, "p2v_forward_ddv_ex: the FULL stage set needs tap_scratch (%zu bytes) whatever with_linear says", p2v_ddv_tap_scratch_bytes(plan, n));
+  if (with_linear || full) {
     if (!tap_scratch) return fail(P2V_E_ARG, "p2v_forward_ddv: with_linear needs tap_scratch");
     if ((uintptr_t)tap_scratch % 16) return fail(P2V_E_ARG, "p2v_forward_ddv: tap_scratch must be 16-byte aligned");
     if (tap_scratch_bytes < p2v_ddv_tap_scratch_bytes(plan, n))
@@ -1428,6 +1528,7 @@ int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bi
   }
   DdvCtx ctx{n, reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + fwd), ddv_partial_slots(n), sums,
              with_linear ? tap_scratch : nullptr, 0};
+  ctx.scratch = full ? tap_scratch : nullptr;
   std::vector<float*> taps;
   if (with_linear) {
     taps.assign(plan->n_layers, tap_scratch);      // every linear output goes through the one buffer; the patch embedding is no DDV stage
@@ -1436,4 +1537,10 @@ int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bi
   FwdOpts o;
   o.images = images; o.ddv = &ctx; o.lin_tap = with_linear ? taps.data() : nullptr;
   return forward_impl(plan, 2 * n, bit_config, n_cfg, logits, ws, fwd, stream, o);
+}
+
+int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                    size_t ws_bytes, int with_linear, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream) {
+  return p2v_forward_ddv_ex(plan, images, n, bit_config, n_cfg, logits, ws, ws_bytes, with_linear, P2V_DDV_STAGES_ENGINE, tap_scratch,
+                            tap_scratch_bytes, sums, stream);
 }

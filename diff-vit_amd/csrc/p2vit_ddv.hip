@@ -195,6 +195,43 @@ __global__ __launch_bounds__(256) void k_cos_combine_one(const CosDesc d, int n,
   cos_combine_body(d, idx, partials, sums + (long long)idx * 3);
 }
 
+// P2V_COS_I8_DEQ (internal; the attn.qact3 / mlp.qact2 stages of P2V_DDV_STAGES_FULL): int8 codes with per-channel scales where every VALUE is
+// the fp32 product RN(code * scale[c]) - what the fake-quantising QAct hands to a forward hook (the PTF scales are no powers of two, so the
+// product rounds).  fp64 products of those fp32 values (exact) and fp64 accumulation in row order, like the fp32 form; a kernel of its own,
+// so that the three kernels above keep their code.
+__global__ __launch_bounds__(256) void k_cos_partial_deq_one(const CosDesc d, unsigned long long* __restrict__ partials) {
+  __shared__ double red[3][256];
+  const long long local = blockIdx.x;
+  const int sample = (int)(local / d.nsplit), split = (int)(local % d.nsplit);
+  const int r0 = split * d.rows_per_split, r1 = min(d.rows, r0 + d.rows_per_split);
+  const int ncg = (d.cols + 15) / 16;
+  const int cgt = min(ncg, 256), lanes = 256 / cgt;
+  const int t = threadIdx.x, cgl = t % cgt, rl = t / cgt;
+  const bool active = rl < lanes, vec = d.vec != 0;
+  const long long s_off = (long long)sample * d.sample_stride;
+  const int8_t* A = reinterpret_cast<const int8_t*>(d.a) + s_off;
+  const int8_t* B = reinterpret_cast<const int8_t*>(d.b) + s_off;
+  double dab = 0.0, daa = 0.0, dbb = 0.0;
+  if (active)
+    for (int cg = cgl; cg < ncg; cg += cgt) {
+      const int c0 = cg * 16, valid = min(16, d.cols - c0);
+      float sc[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) sc[j] = j < valid ? d.scale[c0 + j] : 0.f;
+#pragma unroll 2
+      for (int r = r0 + rl; r < r1; r += lanes) {
+        const long long o = (long long)r * d.row_stride + c0;
+        const v4i va = cos_load_i8(A + o, valid, vec), vb = cos_load_i8(B + o, valid, vec);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const float x = (float)(int)(int8_t)(va[j >> 2] >> (8 * (j & 3))) * sc[j], y = (float)(int)(int8_t)(vb[j >> 2] >> (8 * (j & 3))) * sc[j];
+          dab += (double)x * (double)y; daa += (double)x * (double)x; dbb += (double)y * (double)y;
+        }
+      }
+    }
+  cos_block_sum(red, dab, daa, dbb, partials + local * 3);
+}
+
 // one stage of a recorded sequence (P2V_OP_COS): its record sits in a device table that the closing k_cos_combine walks; the stage's workgroups
 // write the partial slots [item0, item0 + n * nsplit) of that table's numbering
 __global__ __launch_bounds__(256) void k_cos_partial_stage(const CosDesc* __restrict__ desc, unsigned long long* __restrict__ partials) {
@@ -212,7 +249,7 @@ CosDesc p2v_cos_desc(const p2v_cos_layer& a, int n, long long item0) {
   d.a = a.a; d.b = a.b; d.scale = a.scale;
   d.sample_stride = a.sample_stride; d.row_stride = a.row_stride;
   d.rows = a.rows; d.cols = a.cols; d.dtype = a.dtype;
-  const long long esz = a.dtype == P2V_COS_I8 ? 1 : 4;
+  const long long esz = a.dtype == P2V_COS_F32 ? 4 : 1;
   d.vec = ((uintptr_t)a.a % 16 == 0 && (uintptr_t)a.b % 16 == 0 && a.sample_stride * esz % 16 == 0 && a.row_stride * esz % 16 == 0) ? 1 : 0;
   const long long bytes = (long long)a.rows * a.cols * esz;
   long long ns = (bytes + 16383) / 16384;
@@ -260,7 +297,8 @@ int p2v_launch_pair_cosine(const std::vector<CosDesc>& descs, const CosLayout& w
 
 // one stage of p2v_forward_ddv: `partials` holds n * d.nsplit * 3 slots and is reused by the next stage on the same stream
 int p2v_launch_pair_cosine_one(const CosDesc& d, int n, unsigned long long* partials, double* sums, hipStream_t st) {
-  hipLaunchKernelGGL(k_cos_partial_one, dim3((unsigned)(n * d.nsplit)), dim3(256), 0, st, d, partials);
+  if (d.dtype == P2V_COS_I8_DEQ) hipLaunchKernelGGL(k_cos_partial_deq_one, dim3((unsigned)(n * d.nsplit)), dim3(256), 0, st, d, partials);
+  else hipLaunchKernelGGL(k_cos_partial_one, dim3((unsigned)(n * d.nsplit)), dim3(256), 0, st, d, partials);
   CHECK_LAUNCH();
   hipLaunchKernelGGL(k_cos_combine_one, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d, n, partials, sums);
   CHECK_LAUNCH();

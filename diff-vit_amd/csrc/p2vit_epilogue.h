@@ -17,6 +17,7 @@
 #define P2V_EPI_GELU_TAB 5   // internal: P2V_EPI_GELU with a threshold table in LDS (p2v_epilogue.gelu.table != NULL)
 #define P2V_EPI_RESID_PRE 6  // internal: P2V_EPI_RESID with the constants of p2v_resid_prefold (p2v_epilogue.resid_tab != NULL)
 #define P2V_EPI_RESID_TAP 8  // internal: P2V_EPI_RESID that also stores the mid codes q3 (GemmArgs.out_codes != NULL); 7 is P2V_EPI_F32
+#define P2V_EPI_EMBED_TAP 9  // internal: P2V_EPI_EMBED that also stores the patch_embed.qact and qact_embed codes (GemmArgs.out_codes / out_codes2)
 
 __device__ __forceinline__ int lds_off64(int row, int chunk) { return row * GBK + ((chunk ^ ((row >> 2) & 3)) << 4); }
 
@@ -54,9 +55,12 @@ __device__ __forceinline__ void gemm_stage_epilogue(EpiLds* e, int n0, int tid, 
 
 // EMBED and HEAD epilogues (one launch each per forward, k_gemm_i8) and F32 (the layer-output taps of p2v_forward_linear_taps); the
 // per-block epilogues of the layer GEMMs are gemm_epilogue_tile2
-template <int EPI>
+// TAP (EMBED only): the codes of PatchEmbed.qact and of qact_embed - the first two roundings of the chain, taken from the registers that
+// feed the next step - also go to g.out_codes / g.out_codes2, int8 [rows of out][ldo] in the token layout of `out` (patch rows only)
+template <int EPI, bool TAP = false>
 __device__ __forceinline__ void gemm_epilogue_tile(const v16i& acc, int m, int n_tile, int nl, int h, const GemmArgs& g, const EpiLds* e) {
   static_assert(EPI == P2V_EPI_EMBED || EPI == P2V_EPI_HEAD || EPI == P2V_EPI_F32, "stem / head / tap epilogue");
+  static_assert(!TAP || EPI == P2V_EPI_EMBED, "the stem's mid-code taps belong to EMBED");
   if constexpr (EPI == P2V_EPI_F32) {
     // QLinear / QConv2d output fmaf(acc, colscale, bias) stored as fp32 [M][ldo]: one rounding, as gemm_epilogue_tile2's tap_out
     if (m >= g.M) return;
@@ -82,6 +86,7 @@ __device__ __forceinline__ void gemm_epilogue_tile(const v16i& acc, int m, int n
   // nl = n_tile - n0 (column offset inside the block tile, for the LDS constants)
   const bool row_ok = m < g.M;
   unsigned d[4];
+  unsigned m1[TAP ? 4 : 1], m2[TAP ? 4 : 1];
   long long out_row = m;
   int tok = 0;
   if (EPI == P2V_EPI_EMBED) {
@@ -110,11 +115,20 @@ __device__ __forceinline__ void gemm_epilogue_tile(const v16i& acc, int m, int n
       if (n < g.N) pe = *reinterpret_cast<const float4*>(g.ep.pos_deq + (long long)tok * g.N + n);
       const float snv[4] = {sn.x, sn.y, sn.z, sn.w}, pev[4] = {pe.x, pe.y, pe.z, pe.w}, rnv[4] = {rn.x, rn.y, rn.z, rn.w};
       float xv[4];
+      float t1[TAP ? 4 : 1], t2[TAP ? 4 : 1];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float q1 = sat8f(y[i] * g.ep.inv_s_pe);               // PatchEmbed.qact
         const float q2 = sat8f(q1 * g.ep.pe_to_embed);              // qact_embed (both PoT: exact ratio)
         xv[i] = __builtin_fmaf(q2, g.ep.s_embed, pev[i]);           // + qact_pos(pos_embed); int*2^k exact -> one rounding
+        if constexpr (TAP) {
+          t1[i] = q1;
+          t2[i] = q2;
+        }
+      }
+      if constexpr (TAP) {
+        m1[gq] = pack4_sat(t1[0], t1[1], t1[2], t1[3]);
+        m2[gq] = pack4_sat(t2[0], t2[1], t2[2], t2[3]);
       }
       div_q8fx4<false>(xv, snv, rnv, q);                            // qact1 (PTF)
     } else {  // HEAD: logits fp32 on the act_out grid
@@ -134,6 +148,13 @@ __device__ __forceinline__ void gemm_epilogue_tile(const v16i& acc, int m, int n
     uint4 o = halves_to_row16(d[0], d[1], d[2], d[3]);
     if (row_ok && n_tile + 16 * h < g.N)
       *reinterpret_cast<uint4*>(reinterpret_cast<int8_t*>(g.out) + out_row * g.ldo + n_tile + 16 * h) = o;
+    if constexpr (TAP) {
+      const uint4 o1 = halves_to_row16(m1[0], m1[1], m1[2], m1[3]), o2 = halves_to_row16(m2[0], m2[1], m2[2], m2[3]);
+      if (row_ok && n_tile + 16 * h < g.N) {
+        *reinterpret_cast<uint4*>(g.out_codes + out_row * g.ldo + n_tile + 16 * h) = o1;
+        *reinterpret_cast<uint4*>(g.out_codes2 + out_row * g.ldo + n_tile + 16 * h) = o2;
+      }
+    }
   }
 }
 

@@ -28,8 +28,11 @@ __device__ __forceinline__ void gemm_compute_tile(const int8_t* cx, const int8_t
 // 64x32 each), <= 128 VGPRs -> 2 workgroups (16 waves) per CU.  Global->LDS staging goes through a 3-deep ring of NAMED registers
 // (an indexed array of prefetch registers is placed in scratch by hipcc: measured), one barrier per k-tile.  The layer GEMMs run
 // k_gemm_dma / k_ln_gemm.
-template <int EPI, bool W4>
+// EPI_ = P2V_EPI_EMBED_TAP: the EMBED kernel with the two mid-code taps of gemm_epilogue_tile
+template <int EPI_, bool W4>
 __global__ __launch_bounds__(512, 4) void k_gemm_i8(GemmArgs g) {
+  constexpr bool TAP = EPI_ == P2V_EPI_EMBED_TAP;
+  constexpr int EPI = TAP ? P2V_EPI_EMBED : EPI_;
   __shared__ __attribute__((aligned(16))) int8_t lds[2 * (GBM + GBN) * GBK + sizeof(EpiLds)];
   int8_t* sX = lds;                    // [2][GBM][GBK] activation rows
   int8_t* sW = lds + 2 * GBM * GBK;    // [2][GBN][GBK] weight rows
@@ -89,7 +92,7 @@ __global__ __launch_bounds__(512, 4) void k_gemm_i8(GemmArgs g) {
 #undef G_STEP
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
-    gemm_epilogue_tile<EPI>(acc[mi], m0 + wm * 64 + mi * 32 + l31, n0 + wn * 32, wn * 32, h, g, sE);
+    gemm_epilogue_tile<EPI, TAP>(acc[mi], m0 + wm * 64 + mi * 32 + l31, n0 + wn * 32, wn * 32, h, g, sE);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -343,12 +346,11 @@ __device__ __forceinline__ void gemm_compute_tile_dma(unsigned aX0, unsigned aX1
 #else
 #define GD_STAMP(slot) do { } while (0)
 #endif
-// EPI_ = P2V_EPI_RESID_TAP: the RESID kernel with the mid-code tap of gemm_epilogue_tile2 (int8-stored weights only)
+// EPI_ = P2V_EPI_RESID_TAP: the RESID kernel with the mid-code tap of gemm_epilogue_tile2 (int8-stored or packed int4 weights)
 template <int EPI_, bool W4, int MT>
 __global__ __launch_bounds__(128 * MT, MT == 4 ? 4 : 3) void k_gemm_dma(GemmArgs g) {
   constexpr bool TAP = EPI_ == P2V_EPI_RESID_TAP;
   constexpr int EPI = TAP ? P2V_EPI_RESID : EPI_;
-  static_assert(!(TAP && W4), "the mid-code tap is instantiated for int8-stored weights");
   constexpr int NST = 3;                                         // stages of the LDS-DMA ring
   constexpr int TBM = 64 * MT;                                   // tile rows
   constexpr int NTH = 128 * MT;                                  // threads
@@ -601,9 +603,12 @@ int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
 #define P2V_K_DMA3L(E) (k_gemm_dma<E, false, 4>)
 #define P2V_K_DMA3PL(E) (k_gemm_dma<E, true, 4>)
     if (epi == P2V_EPI_RESID && g.out_codes) {
-      // the mid-code tap: the generic RESID chain whatever resid_tab says (same codes); int8-stored weights, tiled kernel only
-      if (g.w4 || (long long)g.M * g.ldo >= (1LL << 32)) return -1;
-      if (big) hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, false, 4>), grid4, block4, 0, st, g);
+      // the mid-code tap: the generic RESID chain whatever resid_tab says (same codes); tiled kernel only
+      if ((long long)g.M * g.ldo >= (1LL << 32)) return -1;
+      if (big) {
+        if (g.w4) hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, true, 4>), grid4, block4, 0, st, g);
+        else hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, false, 4>), grid4, block4, 0, st, g);
+      } else if (g.w4) hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, true, 2>), grid4, block4, 0, st, g);
       else hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, false, 2>), grid4, block4, 0, st, g);
     } else {
     if (big) {
@@ -622,6 +627,10 @@ int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
   if (epi == P2V_EPI_F32) {
     if (g.w4) hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_F32, true>), grid, block, 0, st, g);
     else hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_F32, false>), grid, block, 0, st, g);
+  } else if (epi == P2V_EPI_EMBED && g.out_codes) {      // the stem's mid-code taps: both planes or neither
+    if (!g.out_codes2) return -1;
+    if (g.w4) hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED_TAP, true>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED_TAP, false>), grid, block, 0, st, g);
   } else if (epi == P2V_EPI_EMBED) {
     if (g.w4) hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED, true>), grid, block, 0, st, g);
     else hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED, false>), grid, block, 0, st, g);

@@ -20,6 +20,7 @@ struct GemmArgs {
   void* out;
   int ldo;
   int8_t* out_codes;
+  int8_t* out_codes2;   // EMBED tap only: the qact_embed codes (out_codes: the patch_embed.qact codes), both [rows of out][ldo]
   int tiles_n;          // filled by the launcher
 #ifdef P2V_DIAG
   unsigned long long* stamps;   // diagnostic build only: per-workgroup cycle stamps (6 per workgroup) or null
@@ -41,6 +42,7 @@ struct LnArgs {
   int rows_per_half;    // filled by the launcher: consecutive rows per 32-lane half wave
   int force_generic;    // filled by the launcher (P2V_LN_GENERIC=1: A/B and parity runs of the generic chain)
   LnPre pre;            // optional, see above
+  float* tap_out;       // optional: fp32 [rows][C], the unclamped integer output times out_scale (k_int_layernorm's TAP form, C <= 2048)
 };
 
 struct AttnArgs {
@@ -126,6 +128,7 @@ int p2v_launch_cka_grams(const std::vector<CkaDesc>& descs, const CkaLayout& w, 
 int p2v_launch_hsic(const float* g1, int l1, const float* g2, int l2, int n, void* acc, void* self1, void* self2, int dtype, hipStream_t st);
 
 // pair-cosine sums of the DDV model diff (p2vit_ddv.hip): one record per stage
+#define P2V_COS_I8_DEQ 2   // internal dtype of p2v_launch_pair_cosine_one: int8 codes, every value the fp32 product RN(code * scale[c]) (scale required)
 struct CosDesc {
   const void* a;
   const void* b;

@@ -16,7 +16,9 @@
 #ifndef LN_LDSC
 #define LN_LDSC true
 #endif
-template <int NCH, int LANES, bool PRE>        // PRE: the constants were folded when the plan was created (LnPre)
+// TAP: the value tap (a.tap_out, dense fp32 [rows][C]) - what a forward hook on the module sees, the UNCLAMPED integer of layers.py:288
+// times out_scale - stored from inside the per-element chain (ln_apply); the codes are byte-identical to the launch without it
+template <int NCH, int LANES, bool PRE, bool TAP = false>        // PRE: the constants were folded when the plan was created (LnPre)
 __global__ __launch_bounds__(256) void k_int_layernorm(LnArgs a) {
   // per-channel constants are folded once per workgroup, shared through LDS, then held in registers (re-reading them from
   // LDS per row frees 46 VGPRs but measured 10 % slower: the kernel is bound by VALU issue, not by occupancy)
@@ -101,8 +103,16 @@ __global__ __launch_bounds__(256) void k_int_layernorm(LnArgs a) {
     }
     asm volatile("" ::: "memory");                 // the loads stay above this line
     unsigned outw[R][NCH];
+    if constexpr (TAP) {
+      float* taps[R];
+#pragma unroll
+      for (int u = 0; u < R; ++u) taps[u] = (rr + u < LN_ROWS && row + u < a.rows) ? a.tap_out + (row + u) * (long long)a.C : nullptr;
+      if constexpr (R == 1) ln_row<NCH, LANES, decltype(L), true>(wcur[0], L, a.ln, a.C, l32, outw[0], taps[0]);
+      else ln_rows<NCH, LANES, R, decltype(L), true>(wcur, L, a.ln, a.C, l32, outw, taps);
+    } else {
     if constexpr (R == 1) ln_row<NCH, LANES>(wcur[0], L, a.ln, a.C, l32, outw[0]);
     else ln_rows<NCH, LANES, R>(wcur, L, a.ln, a.C, l32, outw);
+    }
 #pragma unroll
     for (int u = 0; u < R; ++u)
 #pragma unroll
@@ -740,7 +750,7 @@ int p2v_launch_layernorm(const LnArgs& a_, hipStream_t st) {
   LnArgs a = a_;
   a.force_generic = g_ln_generic;
   if (!g_ln_pre) a.pre.gm = nullptr;
-  if (a.C > 2048) return p2v_launch_layernorm_xwide(a, st);      // a row per workgroup (p2vit_ln_xwide.hip); below, nothing changes
+  if (a.C > 2048) return a.tap_out ? -1 : p2v_launch_layernorm_xwide(a, st);      // a row per workgroup (p2vit_ln_xwide.hip); below, nothing changes
   a.rows_per_half = g_ln_rows;
   const int LN_ROWS = g_ln_rows;
   // one row per WAVE above 384 channels (64 lanes x 4 channels x up to 8 groups = 2048 channels): the per-lane constants of a half-wave
@@ -749,6 +759,18 @@ int p2v_launch_layernorm(const LnArgs& a_, hipStream_t st) {
   const int nch = wide ? (a.C + 255) / 256 : (a.C + 127) / 128;
   const int rows_per_block = (wide ? 4 : 8) * LN_ROWS;
   dim3 grid((unsigned)((a.rows + rows_per_block - 1) / rows_per_block)), block(256);
+  if (a.tap_out) {      // the value tap (p2v_int_layernorm_tap, the FULL stage set of p2v_forward_ddv_ex): same grid, same codes
+#define P2V_LN_TAP(N_, L_) case N_: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<N_, L_, true, true>), grid, block, 0, st, a); \
+                                    else hipLaunchKernelGGL((k_int_layernorm<N_, L_, false, true>), grid, block, 0, st, a); break;
+    if (wide) {
+      switch (nch) { P2V_LN_TAP(2, 64) P2V_LN_TAP(3, 64) P2V_LN_TAP(4, 64) P2V_LN_TAP(5, 64) P2V_LN_TAP(6, 64) P2V_LN_TAP(7, 64) P2V_LN_TAP(8, 64) default: return -1; }
+    } else {
+      switch (nch) { P2V_LN_TAP(1, 32) P2V_LN_TAP(2, 32) P2V_LN_TAP(3, 32) default: return -1; }
+    }
+#undef P2V_LN_TAP
+    CHECK_LAUNCH();
+    return 0;
+  }
   if (wide) {
     switch (nch) {
       case 2: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<2, 64, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<2, 64, false>), grid, block, 0, st, a); break;

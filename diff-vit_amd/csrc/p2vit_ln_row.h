@@ -20,7 +20,8 @@ __device__ __forceinline__ int half_wave_sum(int v) {
 // generic per-element chain: every step of get_MN / the 'int' forward as written in the reference
 // os > 0: the output scale itself - the two quotients are IEEE divisions like the reference's; os == 0: multiply by io = 1/scale
 // (identical for powers of two)
-__device__ __forceinline__ float ln_elem_generic(float xq, float g, float bta, float io, float pm, float rs, float mos, float os) {
+// ln_elem_generic_o: the rounded integer x_q of layers.py:288, in front of post_mul and the clamp (what the value tap stores times out_scale)
+__device__ __forceinline__ float ln_elem_generic_o(float xq, float g, float bta, float io, float rs, float mos, float os) {
   const float A = os > 0.f ? (rs * g) / os : (rs * g) * io;        // (s1/std)*gamma / out_scale
   const float absA = fabsf(A);
   int N = 134 - (int)(__float_as_uint(absA) >> 23);                // 7 - floor(log2|A|)   (get_MN, layers.py:234-238)
@@ -29,7 +30,10 @@ __device__ __forceinline__ float ln_elem_generic(float xq, float g, float bta, f
   const float sM = copysignf(M, A);                                // A.sign() * M  (M == 0 when A == 0)
   const float tb = bta - mos * g;
   const float Bv = rintf(ldexpf(os > 0.f ? tb / os : tb * io, N)); // layers.py:283-286
-  const float o = rintf(ldexpf(sM * xq + Bv, -N));                 // layers.py:288
+  return rintf(ldexpf(sM * xq + Bv, -N));                          // layers.py:288
+}
+__device__ __forceinline__ float ln_elem_generic(float xq, float g, float bta, float io, float pm, float rs, float mos, float os) {
+  const float o = ln_elem_generic_o(xq, g, bta, io, rs, mos, os);
   return rintf(o * pm);                                            // * out_scale / cs_next / s_next (clamped by the packing)
 }
 
@@ -205,9 +209,24 @@ __device__ __forceinline__ void ln_scalars(int S1, unsigned S2, const LL& L, con
   const float tlim = __uint_as_float((((__float_as_uint(amin) >> 23) & 255u) + 15u) << 23);       // 2^22 * 2^-(134 - e_min)
   fast = L.pot && amin >= 0x1p-24f && rs * L.gmax < 256.f && (L.bmax + fabsf(mos) * L.gmax) * 1.01f < tlim;
 }
-template <int NCH, int LANES, class LL>
+// the value tap of a channel group (TAP forms only): o * out_scale[c] as fp32, o = the rounded integer in front of post_mul and the clamp
+// (layers.py:288-289: what a forward hook on the module sees).  out_scale = 1 / inv_out, exact for powers of two; ln.out_scale where given
+__device__ __forceinline__ void ln_tap_store(float* tap, int c, const p2v_ln& ln, const float (&o)[4]) {
+  float4 os;
+  if (ln.out_scale) {
+    os = *reinterpret_cast<const float4*>(ln.out_scale + c);
+  } else {
+    const float4 io = *reinterpret_cast<const float4*>(ln.inv_out + c);
+    os = make_float4(1.0f / io.x, 1.0f / io.y, 1.0f / io.z, 1.0f / io.w);
+  }
+  *reinterpret_cast<float4*>(tap + c) = make_float4(o[0] * os.x, o[1] * os.y, o[2] * os.z, o[3] * os.w);
+}
+
+// TAP: `tap` (the row's fp32 [C] values, or null for a row that is not stored) also receives o * out_scale; the codes are formed by the
+// same instructions on the same values as without it
+template <int NCH, int LANES, class LL, bool TAP = false>
 __device__ __forceinline__ void ln_apply(const float (&xq)[NCH][4], const LL& L, const p2v_ln& ln, int l32, float rs, float mos, bool fast,
-                                         unsigned (&outw)[NCH]) {
+                                         unsigned (&outw)[NCH], float* tap = nullptr) {
   if (fast) {
     // A2 = A * 2^16 (rs scaled once per row): sign * M * 2^-N * 2^16 = A2 with its low 16 mantissa bits cleared multiplies the SCALED x_q
     // (xq[][] = x_q * 2^-16, LN_XS) - the same exact product as before; t = beta*io - mos*gamma*io is unchanged; and the magic constant of the
@@ -224,6 +243,7 @@ __device__ __forceinline__ void ln_apply(const float (&xq)[NCH][4], const LL& L,
           p4[0] = pm_.x; p4[1] = pm_.y; p4[2] = pm_.z; p4[3] = pm_.w;
         }
         float q[4];
+        float ot[TAP ? 4 : 1];
 #pragma unroll
         for (int j = 0; j < 4; j += 2) {   // two channels at a time: only the 3-source fma is packed (measured on gfx950, tools/ubench/valu_rate:
           // a wave alone on its SIMD issues a 2-source fp32 op every ~4.9 cycles, a v_pk_mul/add_f32 every ~13, a 3-source v_fma_f32 every ~8, v_pk_fma_f32 ~13)
@@ -251,8 +271,14 @@ __device__ __forceinline__ void ln_apply(const float (&xq)[NCH][4], const LL& L,
             q[j] = rintf(o2[0]) * p4[j];
             q[j + 1] = rintf(o2[1]) * p4[j + 1];
           }
+          if constexpr (TAP) {
+            ot[j] = rintf(o2[0]);
+            ot[j + 1] = rintf(o2[1]);
+          }
         }
         outw[i] = pack4_rne_sat(q[0], q[1], q[2], q[3]);                            // the (last) rounding is the packing's
+        if constexpr (TAP)
+          if (tap && L.on[i]) ln_tap_store(tap, (l32 + LANES * i) * 4, ln, ot);
       }
     };
     if (L.pm_one) chain(std::integral_constant<bool, true>{});      // wave-uniform
@@ -269,8 +295,18 @@ __device__ __forceinline__ void ln_apply(const float (&xq)[NCH][4], const LL& L,
       if (ln.out_scale) ov = *reinterpret_cast<const float4*>(ln.out_scale + cc);
       const float o4[4] = {ov.x, ov.y, ov.z, ov.w};
       float q[4];
+      if constexpr (TAP) {
+        float ot[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) q[j] = ln_elem_generic(xq[i][j] * LN_XS_INV, g4[j], b4[j], i4[j], p4[j], rs, mos, o4[j]);
+        for (int j = 0; j < 4; ++j) {
+          ot[j] = ln_elem_generic_o(xq[i][j] * LN_XS_INV, g4[j], b4[j], i4[j], rs, mos, o4[j]);
+          q[j] = rintf(ot[j] * p4[j]);
+        }
+        if (tap && L.on[i]) ln_tap_store(tap, cc, ln, ot);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q[j] = ln_elem_generic(xq[i][j] * LN_XS_INV, g4[j], b4[j], i4[j], p4[j], rs, mos, o4[j]);
+      }
       outw[i] = pack4_sat(q[0], q[1], q[2], q[3]);
     }
   }
@@ -278,8 +314,9 @@ __device__ __forceinline__ void ln_apply(const float (&xq)[NCH][4], const LL& L,
 
 // One row: packed input codes wcur[i] (0 where the lane's channels lie past C) -> packed output codes outw[i].  Every lane of the
 // row group (32 or 64 lanes) must call it: the sums are cross-lane reductions.
-template <int NCH, int LANES, class LL>
-__device__ __forceinline__ void ln_row(const unsigned (&wcur)[NCH], const LL& L, const p2v_ln& ln, int C, int l32, unsigned (&outw)[NCH]) {
+template <int NCH, int LANES, class LL, bool TAP = false>
+__device__ __forceinline__ void ln_row(const unsigned (&wcur)[NCH], const LL& L, const p2v_ln& ln, int C, int l32, unsigned (&outw)[NCH],
+                                       float* tap = nullptr) {
   float xq[NCH][4], rs, mos;
   int S1;
   unsigned S2;
@@ -287,15 +324,16 @@ __device__ __forceinline__ void ln_row(const unsigned (&wcur)[NCH], const LL& L,
   ln_sums<NCH>(wcur, L, xq, S1, S2);
   ln_reduce<LANES>(S1, S2);
   ln_scalars<NCH>(S1, S2, L, ln, C, rs, mos, fast);
-  ln_apply<NCH, LANES>(xq, L, ln, l32, rs, mos, fast, outw);
+  ln_apply<NCH, LANES, LL, TAP>(xq, L, ln, l32, rs, mos, fast, outw, tap);
 }
 
 // R rows of a row group at once (round 3).  The row scalars - three IEEE divisions, a square root and the range tests, ~55 instructions
 // that every lane of the group would repeat per row - are computed ONCE for the R rows: lane l keeps the sums of row (l mod R), runs the
 // scalar chain on them, and row r's results are read back from lane r of the group (ds_bpermute).  Same operations on the same values
 // as ln_row, only in other lanes: bit-identical.
-template <int NCH, int LANES, int R, class LL>
-__device__ __forceinline__ void ln_rows(const unsigned (&wcur)[R][NCH], const LL& L, const p2v_ln& ln, int C, int l32, unsigned (&outw)[R][NCH]) {
+template <int NCH, int LANES, int R, class LL, bool TAP = false>
+__device__ __forceinline__ void ln_rows(const unsigned (&wcur)[R][NCH], const LL& L, const p2v_ln& ln, int C, int l32, unsigned (&outw)[R][NCH],
+                                        float* const* taps = nullptr) {
   static_assert((R & (R - 1)) == 0 && R <= 8, "rows per batch");
   float xq[R][NCH][4];
   int S1k = 0;
@@ -318,6 +356,6 @@ __device__ __forceinline__ void ln_rows(const unsigned (&wcur)[R][NCH], const LL
   for (int r = 0; r < R; ++r) {
     const float rs_r = __shfl(rs, r, LANES), mos_r = __shfl(mos, r, LANES);
     const bool fast_r = __shfl(fasti, r, LANES) != 0;
-    ln_apply<NCH, LANES>(xq[r], L, ln, l32, rs_r, mos_r, fast_r, outw[r]);
+    ln_apply<NCH, LANES, LL, TAP>(xq[r], L, ln, l32, rs_r, mos_r, fast_r, outw[r], TAP ? taps[r] : nullptr);
   }
 }

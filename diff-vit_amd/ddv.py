@@ -1,6 +1,6 @@
 """DDV model diff: ModelDiff's "decision distance vector" per layer (the reference's modeldiff_p2.py), on the fused engine.
 
-    compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True)     modeldiff_p2.py:84-116
+    compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True, stages='engine')     modeldiff_p2.py:84-116
     similarity(ddv_a, ddv_b)                 per-stage cosine of two DDVs (ModelDiff's metric)
     reference_similarity(ddv_a, ddv_b)       what calculate_and_print_similarities prints    modeldiff_p2.py:118-131
     AttackPGD / gen_adv_inputs(model, inputs, epsilon=0.3, step_size=0.01, num_steps=50)     modeldiff_p2.py:152-194
@@ -25,13 +25,22 @@ codes between proj / fc2 and the residual add: the RESID epilogue stores them ne
 dequantized or CPU Swin hooks the same-named modules (outputs of the window modules, [B * nW, ...], are regrouped per image).  A LIST
 ``bit_config`` raises ``NotImplementedError`` for a Swin: the reference's Swin has no per-layer widths (swin_quant.py:813-817).
 
-Not covered: for ViT / DeiT the reference's norm1 / norm2 / attn.qact3 / mlp.qact2 hook points (that stage list is unchanged); the QActs
-inside the Swin window kernel (qact_attn1, qact2, qact_table, the softmax); DDV on sliced streams; and forward hooks of your own on QAct /
-QIntLayerNorm modules of a fused model - they never fire, because the engine bypasses the module graph (hooks on QLinear / QConv2d are
-served, see ``cka``).
+``stages='full'`` (ViT / DeiT; a Swin model's list is already its full one) serves every hook point of the reference's ``add_hooks``
+(modeldiff_p2.py:50-82, 10 * depth + 10 keys, ``FULL_REFERENCE_KEYS``): on a fused model still ONE engine call (``p2v_forward_ddv_ex``,
+``P2V_DDV_STAGES_FULL``), which adds qact_input (the patch matrix), patch_embed.qact and qact_embed (the mid codes of the EMBED launch),
+per block norm1 / norm2 (the LayerNorm's unclamped integer times its out_scale, fp32, from the unfused LayerNorm launch), attn.qact3 /
+mlp.qact2 (the mid codes of the RESID launches) and ``norm`` over all rows.  ``qact_pos`` does not depend on the input: its entry is made
+here from the plan's calibration - the length-1 vector [1.0], or NaN when every code of the position embedding is zero, as numpy gives in
+the reference.  Any other state hooks the same-named modules.
+
+Not covered: the QActs inside the attention kernels (ViT: qact_attn1 and the softmax; Swin: qact_attn1, qact2, qact_table, the softmax); DDV
+on sliced streams; the FULL stages of an ``input_quant=False`` model on the engine (the reference's own ``add_hooks`` fails there: no
+qact_input); and forward hooks of your own on QAct / QIntLayerNorm modules of a fused model - they never fire, because the engine
+bypasses the module graph (hooks on QLinear / QConv2d are served, see ``cka``).
 
 ``python -m diff_vit_amd.ddv --model deit_small --bits 8 --n 50`` (or ``--model swin_tiny``; ``--bits mixed`` is refused for Swin) prints
-the float-vs-quantized similarity per stage on the synthetic data of ``harness`` and writes ``ddv_result/ddv.pkl``.  ``--inputs blackbox
+the float-vs-quantized similarity per stage on the synthetic data of ``harness`` and writes ``ddv_result/ddv.pkl``; ``--stages full``
+prints every hook point of the reference's list.  ``--inputs blackbox
 --mut-iters 1000`` takes the perturbed twins from ``profiling.gen_profiling_inputs_in_blackbox`` on (float model, quantized model) instead
 of PGD (the default, ``--inputs pgd``)."""
 import argparse
@@ -45,16 +54,17 @@ import torch.nn as nn
 from . import ops  # noqa: F401  (registers torch.ops.p2vit.*)
 
 
-def stage_names(depth, with_linear=True):
-    """the DDV stages in module order, the one list ``FrozenPlan.forward_ddv`` and the module-graph path share."""
-    names = ['qact1']
+def stage_names(depth, with_linear=True, full=False):
+    """the DDV stages in module order, the one list ``FrozenPlan.forward_ddv`` and the module-graph path share.  ``full``: plus the stages
+    behind the reference's remaining hook points (``P2V_DDV_STAGES_FULL``; qact_pos, which no input reaches, is not a stage)."""
+    names = (['qact_input', 'patch_embed.qact', 'qact_embed'] if full else []) + ['qact1']
     for i in range(depth):
         p = 'blocks.%d.' % i
-        names += ([p + 'attn.qkv'] if with_linear else []) + [p + 'attn.qact1', p + 'attn.qact2']
-        names += ([p + 'attn.proj'] if with_linear else []) + [p + 'qact2']
-        names += ([p + 'mlp.fc1'] if with_linear else []) + [p + 'mlp.qact1']
-        names += ([p + 'mlp.fc2'] if with_linear else []) + [p + 'qact4']
-    return names + ['qact2'] + (['head'] if with_linear else []) + ['act_out']
+        names += ([p + 'norm1'] if full else []) + ([p + 'attn.qkv'] if with_linear else []) + [p + 'attn.qact1', p + 'attn.qact2']
+        names += ([p + 'attn.proj'] if with_linear else []) + ([p + 'attn.qact3'] if full else []) + [p + 'qact2']
+        names += ([p + 'norm2'] if full else []) + ([p + 'mlp.fc1'] if with_linear else []) + [p + 'mlp.qact1']
+        names += ([p + 'mlp.fc2'] if with_linear else []) + ([p + 'mlp.qact2'] if full else []) + [p + 'qact4']
+    return names + (['norm'] if full else []) + ['qact2'] + (['head'] if with_linear else []) + ['act_out']
 
 
 def swin_stage_names(depths, with_linear=True):
@@ -75,17 +85,25 @@ def swin_stage_names(depths, with_linear=True):
     return names + ['qact2', 'qact3'] + (['head'] if lin else []) + ['act_out']
 
 
-def reference_keys(depth):
-    """hook name of modeldiff_p2.add_hooks -> stage name, for the stages both sides have (pos_drop is the identity behind qact1)."""
+def reference_keys(depth, full=False):
+    """hook name of modeldiff_p2.add_hooks -> stage name, for the stages both sides have (pos_drop is the identity behind qact1).
+    ``full``: all 10 * depth + 10 hook names onto the entries of ``compute_ddv(..., stages='full')`` (the PatchEmbed module returns its
+    qact's output: ``patch_embed`` and ``patch_embed_qact`` are one tensor)."""
     keys = {'pos_drop': 'qact1', 'final_qact2': 'qact2', 'head': 'head', 'act_out': 'act_out'}
+    per_block = [('attn_qkv', 'attn.qkv'), ('attn_proj', 'attn.proj'), ('qact2', 'qact2'), ('mlp_fc1', 'mlp.fc1'), ('mlp_fc2', 'mlp.fc2'),
+                 ('qact4', 'qact4')]
+    if full:
+        keys.update({'qact_input': 'qact_input', 'patch_embed': 'patch_embed.qact', 'patch_embed_qact': 'patch_embed.qact',
+                     'qact_embed': 'qact_embed', 'qact_pos': 'qact_pos', 'final_norm': 'norm'})
+        per_block += [('norm1', 'norm1'), ('attn_qact3', 'attn.qact3'), ('norm2', 'norm2'), ('mlp_qact2', 'mlp.qact2')]
     for i in range(depth):
-        for ref, ours in (('attn_qkv', 'attn.qkv'), ('attn_proj', 'attn.proj'), ('qact2', 'qact2'), ('mlp_fc1', 'mlp.fc1'),
-                          ('mlp_fc2', 'mlp.fc2'), ('qact4', 'qact4')):
+        for ref, ours in per_block:
             keys['block_%d_%s' % (i, ref)] = 'blocks.%d.%s' % (i, ours)
     return keys
 
 
 REFERENCE_KEYS = reference_keys(24)         # covers every ViT / DeiT depth of the factories; deeper models: reference_keys(depth)
+FULL_REFERENCE_KEYS = reference_keys(24, full=True)      # every hook of add_hooks, for compute_ddv(..., stages='full')
 
 
 def pair_cosine_cpu(a, b, scales=None):
@@ -133,6 +151,18 @@ def _graph_forward(model, x, bit_config):
     FLOPs, gd = [], []
     h = model.forward_features(x, FLOPs, gd, bit_config, False, False)
     return model.act_out(model.head(h, gd, bit_config[-1] if bit_config else None))
+
+
+def _with_qact_pos(names):
+    """the keys of ``compute_ddv(..., stages='full')``: the stages plus qact_pos where the reference's hook fires (behind qact_embed)"""
+    k = names.index('qact_embed') + 1
+    return names[:k] + ['qact_pos'] + names[k:]
+
+
+def _qact_pos_ddv(all_zero, device):
+    """the reference's DDV of qact_pos: the module runs on the position embedding (batch dimension 1) whatever the input, so the vector has
+    one entry, cos(v, v) / |cos(v, v)| = 1 - or 0/0 = NaN when every code is zero"""
+    return torch.tensor([float('nan') if all_zero else 1.0], dtype=torch.float64, device=device)
 
 
 def _hooked_outputs(model, x, bit_config, names, fused_state):
@@ -193,10 +223,14 @@ def _compute_ddv_swin(model, x, xa, bit_config, with_linear):
     return names, pair_cosine_cpu(a, b)
 
 
-def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True):
-    """modeldiff_p2.compute_ddv:84-116 for ``model`` under ``bit_config``: dict stage name -> fp64 tensor [n] (on the model's device)."""
+def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True, stages='engine'):
+    """modeldiff_p2.compute_ddv:84-116 for ``model`` under ``bit_config``: dict stage name -> fp64 tensor [n] (on the model's device).
+    ``stages='full'``: every hook point of the reference's list (module docstring); the ``qact_pos`` entry has length 1."""
     from .swin import SwinTransformer
     from .vit import VisionTransformer
+    if stages not in ('engine', 'full'):
+        raise ValueError("compute_ddv: stages must be 'engine' or 'full', not %r" % (stages,))
+    full = stages == 'full'
     if not isinstance(model, (SwinTransformer, VisionTransformer)):
         raise NotImplementedError('compute_ddv covers the ViT / DeiT and the Swin models')
     if isinstance(model, SwinTransformer) and isinstance(bit_config, (list, tuple)):
@@ -216,17 +250,29 @@ def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=T
             raise ValueError('None is not in list')              # bit_pool.index(None), vit_fquant.py:282
         if model._plan is None:
             model.freeze(dev)
-        _, names, sums = model._plan.forward_ddv(torch.cat((x, xa), 0), [int(b) for b in bit_config], with_linear)
+        _, names, sums = model._plan.forward_ddv(torch.cat((x, xa), 0), [int(b) for b in bit_config], with_linear, stages=stages)
+        pos = _qact_pos_ddv(model._plan.qact_pos_all_zero, dev) if full else None
     else:
-        names = stage_names(model.depth, with_linear)
-        a = _hooked_outputs(model, x, bit_config, names, fused_state)
-        b = _hooked_outputs(model, xa, bit_config, names, fused_state)
+        if full and not getattr(model, 'input_quant', True):
+            raise AttributeError("compute_ddv(stages='full'): the model has no qact_input (input_quant=False), as in the reference's add_hooks")
+        names = stage_names(model.depth, with_linear, full)
+        hooked = _with_qact_pos(names) if full else names
+        a = _hooked_outputs(model, x, bit_config, hooked, fused_state)
+        b = _hooked_outputs(model, xa, bit_config, hooked, fused_state)
+        pos = None
+        if full:      # qact_pos ran on the position embedding, batch dimension 1: a pair of its own
+            k = hooked.index('qact_pos')
+            pa, pb = [a.pop(k)], [b.pop(k)]
+            pos = ddv_from_sums(torch.ops.p2vit.pair_cosine(pa, pb, [None]) if dev.type == 'cuda' else pair_cosine_cpu(pa, pb))[0]
         if dev.type == 'cuda':
             sums = torch.ops.p2vit.pair_cosine(a, b, [None] * len(a))
         else:
             sums = pair_cosine_cpu(a, b)
     d = ddv_from_sums(sums)
-    return {nm: d[k] for k, nm in enumerate(names)}
+    out = {nm: d[k] for k, nm in enumerate(names)}
+    if full:
+        out = {nm: (pos if nm == 'qact_pos' else out[nm]) for nm in _with_qact_pos(names)}
+    return out
 
 
 def similarity(ddv_a, ddv_b):
@@ -316,6 +362,8 @@ def main(argv=None):
     p.add_argument('--bits', default='8', choices=['8', '4', 'mixed'])
     p.add_argument('--n', default=50, type=int, help='seed samples')
     p.add_argument('--steps', default=50, type=int, help='PGD steps')
+    p.add_argument('--stages', default='engine', choices=['engine', 'full'],
+                   help='full: every hook point of the reference\'s add_hooks (ViT / DeiT; a Swin list is already its full one)')
     p.add_argument('--inputs', default='pgd', choices=['pgd', 'blackbox'],
                    help='the perturbed twins: PGD on the float model, or ModelDiff\'s black-box search on (float, quantized)')
     p.add_argument('--mut-iters', default=1000, type=int, help='iterations of the black-box search (--inputs blackbox)')
@@ -352,8 +400,8 @@ def main(argv=None):
     else:
         torch.manual_seed(args.seed)
         adv = gen_adv_inputs(fp, x, num_steps=args.steps)
-    d_fp = compute_ddv(fp, x, adv, None)
-    d_q = compute_ddv(q, x, adv, bits)
+    d_fp = compute_ddv(fp, x, adv, None, stages=args.stages)
+    d_q = compute_ddv(q, x, adv, bits, stages=args.stages)
     sim, ref = similarity(d_fp, d_q), reference_similarity(d_fp, d_q)
     for k in d_fp:
         print('%-24s cosine %+.6f   sign agreement %.2f%%' % (k, sim[k], ref[k]))

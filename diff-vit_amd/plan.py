@@ -178,6 +178,10 @@ class FrozenPlan:
         self.inv_s_input = float(1.0 / s_in) if self.input_quant else 0.0
         E.check(L.p2v_plan_set_embed(self._handle, self.inv_s_input, C.byref(epi),
                                      E.ptr(self._dev(cls_codes, torch.int8))))
+        # the FULL DDV stages: the class row of the qact_embed plane, and whether qact_pos holds anything but zeros (ddv.compute_ddv)
+        if hasattr(L, 'p2v_plan_set_embed_tap_cls'):      # (additive: side builds of older revisions lack it)
+            E.check(L.p2v_plan_set_embed_tap_cls(self._handle, E.ptr(self._dev(_q8(W['cls_token'].reshape(D), s_e), torch.int8))))
+        self.qact_pos_all_zero = not bool((_q8(W['pos_embed'], s_p) != 0).any())
         # ---- blocks ----------------------------------------------------------------------------
         for i in range(self.depth):
             p = 'blocks.%d.' % i
@@ -415,40 +419,55 @@ class FrozenPlan:
             bufs[0] = bufs[0].view(B, g, g, self.D).permute(0, 3, 1, 2)
         return out, bufs
 
-    def ddv_stage_names(self, with_linear=False):
+    def ddv_stage_names(self, with_linear=False, stages='engine'):
         """names of the ``forward_ddv`` stages in module order (``ddv.stage_names``: the oracle's tap names, plus the QLinear outputs)."""
         from .ddv import stage_names
-        return stage_names(self.depth, with_linear)
+        if stages not in ('engine', 'full'):
+            raise ValueError("forward_ddv: stages must be 'engine' or 'full', not %r" % (stages,))
+        return stage_names(self.depth, with_linear, stages == 'full')
 
     def ddv_tap_bytes(self, n):
         """bytes of the one fp32 buffer ``forward_ddv(with_linear=True)`` needs for n pairs: the largest single tap of 2n images."""
         return int(E.lib().p2v_ddv_tap_scratch_bytes(self._handle, n))
 
-    def forward_ddv(self, images_2n, bit_config, with_linear=False):
+    def forward_ddv(self, images_2n, bit_config, with_linear=False, stages='engine'):
         """p2v_forward_ddv: ``images_2n`` holds n clean images followed by their n perturbed twins.  Returns (logits [2n, classes],
         stage names, sums): sums is fp64 [stages, n, 3] = (sum a.b, sum a.a, sum b.b) of every stage's activation on image i and on
         image n + i, reduced from the int8 codes between the launches of the ONE forward (``ddv.ddv_from_sums`` turns them into a
-        DDV).  The only fp32 activation memory is one tap of 2n images (``ddv_tap_bytes``), and only with ``with_linear``."""
+        DDV).  The only fp32 activation memory is one tap of 2n images (``ddv_tap_bytes``), and only with ``with_linear``.
+        ``stages='full'`` (``P2V_DDV_STAGES_FULL``): also the stages behind the reference's remaining hook points - the stem's codes, the
+        LayerNorm values, the mid codes of proj / fc2 - in the same one call; the tap buffer is then needed either way."""
         images, cfg = self._check(images_2n, bit_config)
         B = images.shape[0]
         if B % 2:
             raise AssertionError('forward_ddv takes n clean images followed by their n perturbed twins: %d images' % B)
         n = B // 2
         L = E.lib()
-        names = self.ddv_stage_names(with_linear)
-        assert len(names) == L.p2v_ddv_stage_count(self._handle, int(with_linear))
+        names = self.ddv_stage_names(with_linear, stages)
+        full = stages == 'full'
+        stage_set = E.DDV_STAGES_FULL if full else E.DDV_STAGES_ENGINE
+        if full and not self.input_quant:
+            raise NotImplementedError("forward_ddv(stages='full'): no qact_input stage on an input_quant=False plan")
+        if full and not hasattr(L, 'p2v_forward_ddv_ex'):
+            raise RuntimeError("forward_ddv(stages='full'): libp2vit_hip.so lacks p2v_forward_ddv_ex: rebuild")
+        assert len(names) == (L.p2v_ddv_stage_count_ex(self._handle, int(with_linear), stage_set) if full
+                              else L.p2v_ddv_stage_count(self._handle, int(with_linear)))
         with torch.cuda.device(self.device):
-            nbytes = L.p2v_ddv_workspace_bytes(self._handle, n)
+            nbytes = L.p2v_ddv_workspace_bytes_ex(self._handle, n, stage_set) if full else L.p2v_ddv_workspace_bytes(self._handle, n)
             if self._ws is None or self._ws.numel() < nbytes:
                 self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
                 self._ws_batch = max(self._ws_batch, B)
             ws = self._ws
             out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
             sums = torch.empty(len(names), n, 3, dtype=torch.float64, device=self.device)
-            tap = torch.empty(self.ddv_tap_bytes(n), dtype=torch.uint8, device=self.device) if with_linear else None
-            E.check(L.p2v_forward_ddv(self._handle, E.ptr(images), n, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(),
-                                      int(with_linear), E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(sums),
-                                      E.stream_ptr(self.device)))
+            tap = torch.empty(self.ddv_tap_bytes(n), dtype=torch.uint8, device=self.device) if (with_linear or full) else None
+            if full:
+                E.check(L.p2v_forward_ddv_ex(self._handle, E.ptr(images), n, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(),
+                                             int(with_linear), stage_set, E.ptr(tap), tap.numel(), E.ptr(sums), E.stream_ptr(self.device)))
+            else:
+                E.check(L.p2v_forward_ddv(self._handle, E.ptr(images), n, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(),
+                                          int(with_linear), E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(sums),
+                                          E.stream_ptr(self.device)))
         return out, names, sums
 
     def slice_sizes(self, batch, n_streams=3):

@@ -26,13 +26,13 @@
  *     contraction walks through zero weight columns - may hold anything: it never reaches a result.
  *     (tests/test_kernel_edges_gpu.py runs the per-operator entry points listed below into sentinel-filled buffers, and the class-token
  *     fill of p2v_forward on a sentinel-filled workspace.)
- *     The whole-model entry points (p2v_forward, p2v_forward_u8, p2v_forward_taps, p2v_forward_linear_taps, p2v_forward_ddv) compose
+ *     The whole-model entry points (p2v_forward, p2v_forward_u8, p2v_forward_taps, p2v_forward_linear_taps, p2v_forward_ddv / _ex) compose
  *     these launches inside the caller's workspace, and two statements hold for them:
  *       (1) a forward's result - logits, taps, sums - does not depend on what the workspace holds on entry: it may be uninitialised, or
  *           left over from another batch size, bit list or entry point.  Every byte a launch reads was written by an earlier launch of the
  *           same call or meets a zero weight column (the k-tile tail of a width that is no multiple of 64; the rows the class-row branch
  *           of the last block leaves stale are not read);
- *       (2) a forward writes nothing outside [workspace, workspace + p2v_workspace_bytes) - p2v_ddv_workspace_bytes for p2v_forward_ddv -
+ *       (2) a forward writes nothing outside [workspace, workspace + p2v_workspace_bytes) - p2v_ddv_workspace_bytes for p2v_forward_ddv / _ex -
  *           and outside its dense outputs (logits [batch][classes], each tap at its stated extent, sums, tap_scratch up to
  *           p2v_ddv_tap_scratch_bytes).  Inside the workspace the alignment gaps between the seven buffers and the trailing 256 bytes are
  *           never written.  Each launch of a stop_after >= 0 run, where the last block computes every row, writes exactly the
@@ -261,6 +261,10 @@ int p2v_plan_set_linear(p2v_plan* plan, int layer, int bits, const p2v_linear* l
  * needed: activation scales do not depend on the weight bits); cls row codes [D] after qact1. */
 int p2v_plan_set_embed(p2v_plan* plan, float inv_s_input, const p2v_epilogue* embed_epi,
                        const int8_t* cls_row_codes /* dev [D] */);
+/* Optional, additive (found by its symbol): the codes of the class row under qact_embed, clamp(round(cls_token / s_embed)), dev int8 [D] -
+ * the constant row 0 of the `qact_embed` stage of P2V_DDV_STAGES_FULL (p2v_forward_ddv_ex fills it into the stage's plane with the
+ * class-token fill kernel).  The array must outlive the plan.  Nothing else reads it. */
+int p2v_plan_set_embed_tap_cls(p2v_plan* plan, const int8_t* cls_embed_codes /* dev [D] */);
 
 /* per block, per bit-pool index (0: 4-bit, 1: 8-bit) of qkv (for ln1/attn side) and of fc1 (for ln2 side):
  * the reference keeps best_scale/best_act_scale per bit (vit_fquant.py:282-292, layers_quant.py:305-313). */
@@ -394,13 +398,27 @@ int p2v_u8_patchify(const uint8_t* img, int layout, const void* lut_i8, int batc
  * between the layer and the residual add (attn.qact4 / mlp.qact2 of Swin, attn.qact3 / mlp.qact2 of ViT): q3 = clamp(round((acc *
  * colscale[n] + bias[n]) / s_mid[n])), the first rounding of the RESID formula below, int8 [M][ldo].  A tapped RESID launch runs the generic
  * chain of the tiled kernel whatever resid_tab says (same codes, `out` byte-identical with and without the tap); out and out_codes 16-byte
- * aligned, int8-stored weights (P2V_E_UNSUPPORTED for packed4).  Other epilogues ignore out_codes.
+ * aligned, int8-stored weights (P2V_E_UNSUPPORTED for packed4: p2v_gemm_resid_tap below takes both).  Other epilogues ignore out_codes.
  * K is a multiple of 64 and MAY exceed lda (a width that is not a multiple of 64: the weight columns [width, K) are zero): the
  * contraction then walks into the next row, so (M-1)*lda + K bytes of A must be readable.  ldo >= N.  P2V_E_SHAPE otherwise.
  * Written: columns [0, N) of rows [0, M) of `out` (and of out_codes, same ldo) - never the columns [N, ldo) - and tap_out as a dense
  * [M][N]; P2V_EPI_EMBED: columns [0, N) of the rows b*(patches+1) + 1 + p, never a class-token row b*(patches+1). */
 int p2v_gemm_i8(int epilogue_kind, const int8_t* A, int lda, int M, int K, int N, const p2v_linear* lin,
                 const p2v_epilogue* epi, void* out, int ldo, int8_t* out_codes, void* stream);
+
+/* Additive (found by its symbol): p2v_gemm_i8(P2V_EPI_RESID, ..., out_codes) for int8-stored AND packed int4 weights (p2v_linear.packed4),
+ * at both tile heights: the ViT / DeiT plans keep their 4-bit layers packed.  Same results and footprint as described above: `out`
+ * byte-identical with and without the tap, out_codes = q3, columns [N, ldo) of both never written.  p2v_gemm_i8 itself keeps refusing
+ * packed4 for a tapped launch (its callers' contract); the few-rows kernel has no tap (the tiled kernel runs, whatever M). */
+int p2v_gemm_resid_tap(const int8_t* A, int lda, int M, int K, int N, const p2v_linear* lin, const p2v_epilogue* epi, int8_t* out, int ldo,
+                       int8_t* out_codes, void* stream);
+
+/* Additive (found by its symbol): p2v_gemm_i8(P2V_EPI_EMBED, ...) that also stores the first two roundings of the EMBED chain, taken from
+ * the registers that feed the next step: pe_codes = clamp(round(y * inv_s_pe)) (PatchEmbed.qact) and embed_codes = clamp(round(pe_codes *
+ * pe_to_embed)) (qact_embed), int8 [rows of out][ldo] in the token layout of `out`: columns [0, N) of the rows b*(patches+1) + 1 + p, never
+ * a class-token row, never the columns [N, ldo).  `out` is byte-identical to the launch without the taps.  All three 16-byte aligned. */
+int p2v_gemm_embed_tap(const int8_t* A, int lda, int M, int K, int N, const p2v_linear* lin, const p2v_epilogue* epi, int8_t* out, int ldo,
+                       int8_t* pe_codes, int8_t* embed_codes, void* stream);
 
 /* rows x C int8 -> rows x C int8; row r of the input starts at x + r*row_stride (lets the final norm
  * touch only the cls rows, vit_fquant.py:766-767).  C: a multiple of 4 up to 4096 (P2V_E_SHAPE beyond, before any launch; see the limits above for the bound
@@ -409,6 +427,14 @@ int p2v_gemm_i8(int epilogue_kind, const int8_t* A, int lda, int M, int K, int N
  * [C, out_stride) of an output row and rows >= `rows` are not written. */
 int p2v_int_layernorm(const int8_t* x, long long row_stride, int rows, int C, const p2v_ln* ln,
                       int8_t* out, long long out_stride, void* stream);
+
+/* Additive (found by its symbol): p2v_int_layernorm that also writes what a forward hook on the QIntLayerNorm module sees (layers.py:
+ * 288-289): tap_out[r][c] = o * out_scale[c] as fp32, o = the rounded integer of the LayerNorm in front of post_mul and of the clamp to int8
+ * (|o| may pass 127), out_scale[c] = ln->out_scale[c] where given, else 1 / inv_out[c] (exact for powers of two).  tap_out: dev fp32, dense
+ * [rows][C], 16-byte aligned.  `out` is byte-identical to p2v_int_layernorm's, on the generic and on the fast chain, with and without
+ * ln->pre.  C up to 2048 (P2V_E_UNSUPPORTED beyond); the other conditions are p2v_int_layernorm's. */
+int p2v_int_layernorm_tap(const int8_t* x, long long row_stride, int rows, int C, const p2v_ln* ln,
+                          int8_t* out, long long out_stride, float* tap_out, void* stream);
 
 /* p2v_int_layernorm followed by p2v_gemm_i8 (REQUANT or GELU) in ONE launch: norm1 -> qkv -> qact1 and norm2 -> fc1 -> GELU -> qact1
  * (vit_fquant.py:431-434,284-293,307; layers_quant.py:305-316,331-333).  The LayerNorm output codes stay in LDS; ln_out (optional,
@@ -627,6 +653,32 @@ size_t p2v_ddv_workspace_bytes(const p2v_plan* plan, int n);
 size_t p2v_ddv_tap_scratch_bytes(const p2v_plan* plan, int n);
 int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
                     size_t ws_bytes, int with_linear, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream);
+
+/* The stage set (additive; the three functions above are the stage_set = P2V_DDV_STAGES_ENGINE case of these, launch for launch).
+ * P2V_DDV_STAGES_FULL serves every hook point of modeldiff_p2.add_hooks but qact_pos (input-independent: its DDV is the constant [1.0]).
+ * It adds, in execution order:
+ *   qact_input, patch_embed.qact, qact_embed       in front of qact1: the patch matrix (a permutation of the image's codes plus zero columns);
+ *                                                  the two mid-code planes of the EMBED launch (p2v_gemm_embed_tap) in "qkv" - patch_embed.qact
+ *                                                  over the patch rows [patches][D], qact_embed over [tokens][D] with the constant class row of
+ *                                                  p2v_plan_set_embed_tap_cls filled in; one scale each (exact integer sums)
+ *   blocks.i.norm1 / norm2                         in front of attn.qkv / mlp.fc1: the LayerNorm's UNCLAMPED integer times out_scale, fp32
+ *                                                  (p2v_int_layernorm_tap) - the pair runs unfused: LayerNorm into "ln", then the GEMM
+ *   blocks.i.attn.qact3 / mlp.qact2                between attn.proj / mlp.fc2 and qact2 / qact4: the mid codes of the RESID launch
+ *                                                  (out_codes of p2v_gemm_i8) in "ln", per-channel scales s_mid
+ *   norm                                           in front of qact2: the final norm once more over all 2n * tokens rows (the hook sits in
+ *                                                  front of [:, 0]); the class-row launch that feeds the head stays
+ * = 4 * depth + 4 more: 9 * depth + 7 stages, 13 * depth + 8 with the linear outputs.  The fp32 LayerNorm values go through tap_scratch (each
+ * reduced before the next tap overwrites it; p2v_ddv_tap_scratch_bytes covers them), so FULL needs tap_scratch even with with_linear == 0.
+ * The workspace is the same size for both sets; the logits are byte-equal to p2v_forward's.
+ * Refused before any launch: an unknown stage_set (P2V_E_ARG); FULL on a plan without an input QAct (inv_s_input == 0: P2V_E_UNSUPPORTED,
+ * there is no qact_input stage) or without p2v_plan_set_embed_tap_cls (P2V_E_STATE); FULL with a NULL or short tap_scratch
+ * (P2V_E_WORKSPACE). */
+enum { P2V_DDV_STAGES_ENGINE = 0, P2V_DDV_STAGES_FULL = 1 };
+int p2v_ddv_stage_count_ex(const p2v_plan* plan, int with_linear, int stage_set);
+size_t p2v_ddv_workspace_bytes_ex(const p2v_plan* plan, int n, int stage_set);      /* 0 for an unknown stage_set */
+int p2v_forward_ddv_ex(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                       size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, double* sums,
+                       void* stream);
 
 /* ---- Scoring of the logits (additive: no structure, existing entry point or P2V_ABI_VERSION changes; a binding finds it by its symbols) --
  * Precision@k and the cross-entropy loss on the device, with a DEFINED tie rule.  The logits are 8-bit codes times a power of two, so the

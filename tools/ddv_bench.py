@@ -1,13 +1,16 @@
 """Times a DDV of the quantized model on the GPU (not bench.py): n clean + n perturbed images, [8] * L, median of --reps, one JSON line
 per model.
 
-    python tools/ddv_bench.py [--n 50] [--reps 10] [--models deit_small,vit_base]
+    python tools/ddv_bench.py [--n 50] [--reps 10] [--models deit_small,vit_base] [--stages full]
     python tools/ddv_bench.py --swin swin_base [--n 50] [--reps 10]        the Swin lines (below), instead of the ViT / DeiT ones
 
   (a)  forward_ms                 FrozenPlan.forward of the 2n images (one stream; the last block on the class rows only)
        forward_all_rows_ms        the same with the switch cls_rows = 0: every row of the last block, what every tap entry point computes
   (b)  ddv_int8_ms                FrozenPlan.forward_ddv: the 5 * depth + 3 stages reduced from the live int8 buffers
   (c)  ddv_linear_ms              forward_ddv(with_linear=True): + the 4 * depth + 1 linear outputs through ONE fp32 tap buffer
+       --stages full adds         ddv_full_int8_ms / ddv_full_linear_ms: forward_ddv(stages='full'), the 9 * depth + 7 / 13 * depth + 8 stages
+                                  of P2V_DDV_STAGES_FULL (every hook point of the reference's list), and forward_unfused_all_rows_ms: the
+                                  plain forward with cls_rows = 0 and ln_gemm = 0, the launch sequence the FULL call runs its stages between
   (d)  taps_torch_ms              what there was before: forward_linear_taps (all fp32 taps resident) + torch cosine_similarity per tap
        reduction                  bytes the reductions of (b) read (both operands of every stage), the time they add to the all-rows
                                   forward, and the rate; `standalone`: ONE grouped p2v_pair_cosine over buffers of the same shapes,
@@ -52,7 +55,7 @@ def timed(fn, reps):
     return float(np.median(ts))
 
 
-def run(model, n, reps):
+def run(model, n, reps, full=False):
     g = np.load(os.path.join(ROOT, 'tests', 'golden', model + '.npz'))
     arch = dva.synth.ARCHS[model]
     sd = dva.synth.vit_state_dict(arch, int(g['seed']))
@@ -75,6 +78,21 @@ def run(model, n, reps):
         return [F.cosine_similarity(t[:n].reshape(n, -1), t[n:].reshape(n, -1), dim=1) for t in taps[1:]] + \
                [F.cosine_similarity(logits[:n], logits[n:], dim=1)]
     t_d = timed(taps_torch, reps)
+    extra = {}
+    if full:
+        lib.p2v_set_tuning(b'cls_rows', 0)
+        lib.p2v_set_tuning(b'ln_gemm', 0)
+        t_unfused = timed(lambda: plan.forward(x, bits), reps)
+        lib.p2v_set_tuning(b'ln_gemm', int(os.environ.get('P2V_LN_GEMM', '1') != '0'))
+        lib.p2v_set_tuning(b'cls_rows', cls_rows)
+        t_fb = timed(lambda: plan.forward_ddv(x, bits, False, stages='full'), reps)
+        t_fc = timed(lambda: plan.forward_ddv(x, bits, True, stages='full'), reps)
+        extra = {'stages_full_int8': 9 * arch['depth'] + 7, 'stages_full_linear': 13 * arch['depth'] + 8,
+                 'forward_unfused_all_rows_ms': round(t_unfused, 3), 'ddv_full_int8_ms': round(t_fb, 3), 'ddv_full_linear_ms': round(t_fc, 3),
+                 'ddv_full_int8_over_ddv_int8': round(t_fb / t_b, 3), 'ddv_full_linear_over_ddv_linear': round(t_fc / t_c, 3),
+                 'ddv_full_linear_over_taps_torch': round(t_fc / t_d, 3),
+                 'us_per_added_stage': {'int8': round((t_fb - t_b) * 1e3 / (4 * arch['depth'] + 4), 2),
+                                        'linear': round((t_fc - t_c) * 1e3 / (4 * arch['depth'] + 4), 2)}}
     T, D, Hd = plan.tokens, plan.D, plan.hidden
     per_block = [(T, 3 * D), (T, D), (T, D), (T, Hd), (T, D)]
     shapes = [(T, D)] + per_block * arch['depth'] + [(1, D)]
@@ -91,7 +109,7 @@ def run(model, n, reps):
             'reduction': {'MB_read': round(nbytes / 1e6, 1), 'added_ms': round(t_b - t_all, 3),
                           'TBps_in_forward': round(nbytes / max(t_b - t_all, 1e-6) / 1e9, 2),
                           'standalone_ms': round(t_alone, 3), 'standalone_TBps': round(2.0 * n * sum(r * c for r, c in shapes) / t_alone / 1e9, 2),
-                          'hbm_TBps': {'peak': 8.0, 'measured_copy': 6.29}}}
+                          'hbm_TBps': {'peak': 8.0, 'measured_copy': 6.29}}, **extra}
 
 
 def run_swin(name, n, reps):
@@ -147,13 +165,14 @@ def main():
     p.add_argument('--n', type=int, default=50)
     p.add_argument('--reps', type=int, default=10)
     p.add_argument('--models', default='deit_small,vit_base')
+    p.add_argument('--stages', default='engine', choices=['engine', 'full'], help='full: also time forward_ddv(stages="full") (ViT / DeiT)')
     p.add_argument('--swin', default=None, help='a Swin factory name of harness.str2model (swin_base): the Swin lines instead')
     a = p.parse_args()
     if a.swin:
         print(json.dumps(run_swin(a.swin, a.n, a.reps)), flush=True)
         return
     for m in a.models.split(','):
-        print(json.dumps(run(m, a.n, a.reps)), flush=True)
+        print(json.dumps(run(m, a.n, a.reps, a.stages == 'full')), flush=True)
 
 
 if __name__ == '__main__':
