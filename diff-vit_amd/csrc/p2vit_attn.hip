@@ -24,7 +24,7 @@
 // ... and when kb*16 + 12 + r < NT it is a real key in every lane: no padding test
 #define WA_PAD(kb, r) (!(NT > 0 && (kb) * 16 + 12 + (r) < NT))
 template <int NT, bool TAP>
-__global__ __launch_bounds__(256, 3) void k_window_attention(WinAttnArgs a) {
+__global__ __launch_bounds__(256, 3) void k_window_attention(std::conditional_t<TAP, WinAttnArgs, WinAttnKArgs> a) {
   constexpr int VSTRIDE = WA_KEYS + 4;                                         // bf16 elements
   __shared__ __attribute__((aligned(16))) int8_t sK[4][WA_KEYS * WA_HD];
   __shared__ __attribute__((aligned(16))) unsigned short sVt[4][WA_HD * VSTRIDE];
@@ -206,8 +206,13 @@ __global__ __launch_bounds__(256, 3) void k_window_attention(WinAttnArgs a) {
       const double Sd = (double)(float)S;
       const float ratio = rintf((float)(Sd * lutFR[d]));
       const int E = (int)((__float_as_uint(ratio) + 0x00400000u) >> 23);         // biased exponent of 2^k
-      if (TAP && valid)
-        a.probs_k[((((long long)b * nW + w) * a.H + head) * N + (N - 1)) * N + j] = (int8_t)(E - 127 > 16 ? 16 : E - 127);
+      if constexpr (TAP) if (valid) {
+        const long long trow = (((long long)b * nW + w) * a.H + head) * N + (N - 1);
+        if (a.probs_k) a.probs_k[trow * N + j] = (int8_t)(E - 127 > 16 ? 16 : E - 127);
+        if (a.probs_kp) a.probs_kp[trow * a.pitch + j] = (int8_t)(E - 127 > 16 ? 16 : E - 127);
+        if (a.attn1_codes) a.attn1_codes[trow * a.pitch + j] = (int8_t)(int)a1;
+        if (a.qact2_codes) a.qact2_codes[trow * a.pitch + j] = (int8_t)(int)a2;
+      }
       sP[wave][g][l15] = (unsigned short)((E < 143 && l15 < 13) ? (143 - E) << 7 : 0);     // 2^-k * 2^-111 as bf16 (lis_prob_pair), 0 from k = 16 (and for padding: sum / 1 >= 2^32)
       __builtin_amdgcn_wave_barrier();
       asm volatile("" ::: "memory");
@@ -227,6 +232,11 @@ __global__ __launch_bounds__(256, 3) void k_window_attention(WinAttnArgs a) {
             const float a1 = __builtin_amdgcn_fmed3f(rintf((float)X * x_mul), -128.f, 127.f);     // ONE rounding, then qact_attn1
             const float a2 = __builtin_amdgcn_fmed3f(rintf(__builtin_fmaf(a1, a1_mul, trow[-linj[kb][r]])), -128.f, 127.f);   // qact2
             float xi = a2;
+            if constexpr (TAP) if (qi < N && kb * 16 + 4 * g + r < N) {          // the two QActs in front of the mask, from the registers that feed the next step
+              const long long at = ((((long long)b * nW + w) * a.H + head) * N + qi) * a.pitch + kb * 16 + 4 * g + r;
+              if (a.attn1_codes) a.attn1_codes[at] = (int8_t)(int)a1;
+              if (a.qact2_codes) a.qact2_codes[at] = (int8_t)(int)a2;
+            }
             if (MASK) xi -= regj[kb][r] != reg_i ? m100 : 0.f;
             if (WA_PAD(kb, r)) xi = kb * 16 + 4 * g + r < N ? xi : -3.0e9f;
             xs[kb][r] = xi;
@@ -269,9 +279,11 @@ __global__ __launch_bounds__(256, 3) void k_window_attention(WinAttnArgs a) {
             }
             // correctly rounded fp32 quotient, as in k_lis_attention; a padding key (entry 257: reciprocal 1) gives sum / 1 >= 2^32 -> k clamps -> 0
             ratio[e] = rintf((float)(Sd * lutFR[s1[kb][r]]));
-            if (TAP && qi < N && kb * 16 + 4 * g + r < N) {
+            if constexpr (TAP) if (qi < N && kb * 16 + 4 * g + r < N) {
               const int k = (int)((__float_as_uint(ratio[e]) + 0x00400000u) >> 23) - 127;
-              a.probs_k[((((long long)b * nW + w) * a.H + head) * N + qi) * N + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
+              const long long trow = (((long long)b * nW + w) * a.H + head) * N + qi;
+              if (a.probs_k) a.probs_k[trow * N + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
+              if (a.probs_kp) a.probs_kp[trow * a.pitch + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
             }
           }
           pk[e2] = lis_prob_pair(ratio[0], ratio[1]);            // 2^-k * 2^-111 as bf16, 0 from k = 16 on (see k_lis_attention)
@@ -312,10 +324,10 @@ int p2v_launch_window_attention(const WinAttnArgs& a, hipStream_t st) {
   const int hgroups = (a.H + 3) / 4;
   const dim3 grid((unsigned)(a.B * a.wa.n_windows * hgroups));
   if (a.wa.ws == 7) {
-    if (a.probs_k) hipLaunchKernelGGL((k_window_attention<49, true>), grid, dim3(256), 0, st, a);
+    if (a.tapped()) hipLaunchKernelGGL((k_window_attention<49, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_window_attention<49, false>), grid, dim3(256), 0, st, a);
   } else {
-    if (a.probs_k) hipLaunchKernelGGL((k_window_attention<0, true>), grid, dim3(256), 0, st, a);
+    if (a.tapped()) hipLaunchKernelGGL((k_window_attention<0, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_window_attention<0, false>), grid, dim3(256), 0, st, a);
   }
   CHECK_LAUNCH();
@@ -343,7 +355,7 @@ int p2v_launch_attention(const AttnArgs& a, int head_dim, hipStream_t st) {
     const float m2 = a.at.s_qkv_sq * a.at.inv_s_attn;
     if (!(m2 > 0.f) || frexpf(m2, &ex) != 0.5f) return -2;
   }
-  switch (p2v_attention_kernel_of(head_dim, a.N, a.probs_k != nullptr)) {
+  switch (p2v_attention_kernel_of(head_dim, a.N, a.tapped())) {
     case P2V_KERNEL_RESIDENT: break;
     case P2V_KERNEL_PACKED: return p2v_launch_attention_packed(a, st);
     case P2V_KERNEL_STREAMING: return p2v_launch_attention_stream(a, head_dim, st);

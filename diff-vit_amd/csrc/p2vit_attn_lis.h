@@ -71,7 +71,7 @@ extern unsigned long long* g_gemm_stamps;
 // HD: any multiple of 16 up to 128 (round 4; instantiated for 32, 48, 64, 80, 96, 128): the score of a key block is the sum of NQ = ceil(HD / 64)
 // 64-deep MFMAs (lane group g holds chunk 4 j + g of the row in step j, zero past the row), the P.V product runs over HD / 16 output tiles.
 template <int HD, int NKP, bool TAP, bool ISH>
-__global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 : 2))) void k_lis_attention(AttnArgs a) {
+__global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 : 2))) void k_lis_attention(std::conditional_t<TAP, AttnArgs, AttnKArgs> a) {
   static_assert(HD % 16 == 0 && HD >= 16 && HD <= 128, "head_dim");
   constexpr int KROWS = NKP * 32;
   constexpr int NKB = NKP * 2;                  // 16-key blocks
@@ -204,6 +204,7 @@ __global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 :
 #endif
     AT_STAMP(stamp_base);
     long long S = 0;
+    [[maybe_unused]] int rowmax = 0;                    // TAP: the row maximum of the qact_attn1 codes (a score slot holds ebase + 8 * (rowmax - code))
     if (ISH) {
       // codes = clamp(rne(score * 2^-p)): (float)score * 2^-p is exact, so torch.round of it is the integer round-half-even shift
       // (s + 2^(p-1) - 1 + bit p of s) >> p.  Row max of the codes; d = max - code; padded keys get a code far below every real one.
@@ -228,6 +229,7 @@ __global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 :
         o = __shfl_xor(mx, 32);
         mx = o > mx ? o : mx;
       }
+      if (TAP) rowmax = mx;
       const int mx8 = (mx << 3) + ebase;
 #pragma unroll
       for (int kb = 0; kb < NKB; ++kb) {
@@ -263,6 +265,7 @@ __global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 :
       mn = o < mn ? o : mn;
     }
     // d = max - code = nc - mn in [0, 255]; s[][] := 8*d, the byte offset into both tables (256 = sentinel of padding)
+    if (TAP) rowmax = -mn;
     const int neg8mn = -8 * mn + ebase;
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
@@ -307,9 +310,14 @@ __global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 :
           // fp32 rounds to the same side.  (v_mul_f64 + v_cvt_f32_f64 replace v_mul_f32 + four 3-source v_fma_f32.)
           const double rd = ((lds_f64p)(uintptr_t)(unsigned)s[kb][r])[258];          // the reciprocal table starts 258 entries behind exp_int
           ratio[e] = rintf((float)(Sd * rd));
-          if (TAP && s[kb][r] < ebase + 2048 && qrow < N) {
+          if constexpr (TAP) if (s[kb][r] < ebase + 2048 && qrow < N) {
             int k = (int)((__float_as_uint(ratio[e]) + 0x00400000u) >> 23) - 127;   // log_round, layers.py:323-329
-            a.probs_k[(((long long)b * a.H + head) * N + qrow) * N + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
+            const int key = kb * 16 + 4 * g + r;
+            const long long trow = ((long long)b * a.H + head) * N + qrow;
+            if (a.probs_k) a.probs_k[trow * N + key] = (int8_t)(k > 16 ? 16 : k);
+            if (a.probs_kp) a.probs_kp[trow * a.pitch + key] = (int8_t)(k > 16 ? 16 : k);
+            // the qact_attn1 code back from its table offset: code = rowmax - d, nothing is recomputed
+            if (a.score_codes) a.score_codes[trow * a.pitch + key] = (int8_t)(rowmax - ((s[kb][r] - ebase) >> 3));
           }
         }
         pk[e2] = lis_prob_pair(ratio[0], ratio[1]);              // 2^-k * 2^-111 as bf16, 0 from k = 16 on
@@ -378,7 +386,7 @@ static int launch_attn_t(const AttnArgs& a_, hipStream_t st) {
     hipLaunchKernelGGL((k_lis_attention<HD, NKB, TAP_, ISH_>), grid, block, smem, st, a);                                    \
   } while (0)
   if constexpr (!ISH_OK) a.pshift = 0;
-  if (a.probs_k) {
+  if (a.tapped()) {
     if constexpr (ISH_OK) { if (a.pshift) { P2V_ATTN_LAUNCH(true, true); CHECK_LAUNCH(); return 0; } }
     P2V_ATTN_LAUNCH(true, false);
   } else {

@@ -41,7 +41,7 @@
 #include "p2vit_attn_lis.h"
 
 template <int NG>
-__global__ __launch_bounds__(512, 2) void k_lis_attention_packed(AttnArgs a) {
+__global__ __launch_bounds__(512, 2) void k_lis_attention_packed(AttnKArgs a) {
   static_assert(NG >= 1 && NG * 64 <= P2V_MAX_TOKENS_PACKED, "key groups");
   constexpr int HD = 64, KROWS = NG * 64, NDT = HD / 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

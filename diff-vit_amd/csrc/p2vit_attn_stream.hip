@@ -17,7 +17,7 @@
 #define AS_VSTRIDE 36          // bf16 elements per channel row of the staged V^T pair (32 keys + 4: conflict-free b64 reads)
 
 template <int HD, bool TAP>
-__global__ __launch_bounds__(64) void k_lis_attention_stream(AttnArgs a) {
+__global__ __launch_bounds__(64) void k_lis_attention_stream(std::conditional_t<TAP, AttnArgs, AttnKArgs> a) {
   static_assert(HD % 16 == 0 && HD >= 16 && HD <= 128, "head_dim");
   constexpr int CH = HD / 16, NQ = (CH + 3) / 4, NDT = HD / 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -135,9 +135,12 @@ __global__ __launch_bounds__(64) void k_lis_attention_stream(AttnArgs a) {
         const int nc = (int)(((half ? pc1 : pc0) >> (8 * r)) & 255u) - 127;
         const int d = key < N ? nc - mn : 256;
         ratio[e] = rintf((float)(Sd * lutFR[d]));                                     // correctly rounded fp32 quotient, see k_lis_attention
-        if (TAP && key < N && qrow < N) {
+        if constexpr (TAP) if (key < N && qrow < N) {
           const int k = (int)((__float_as_uint(ratio[e]) + 0x00400000u) >> 23) - 127; // log_round, layers.py:323-329
-          a.probs_k[(((long long)b * a.H + head) * N + qrow) * N + key] = (int8_t)(k > 16 ? 16 : k);
+          const long long trow = ((long long)b * a.H + head) * N + qrow;
+          if (a.probs_k) a.probs_k[trow * N + key] = (int8_t)(k > 16 ? 16 : k);
+          if (a.probs_kp) a.probs_kp[trow * a.pitch + key] = (int8_t)(k > 16 ? 16 : k);
+          if (a.score_codes) a.score_codes[trow * a.pitch + key] = (int8_t)(-nc);       // the qact_attn1 code (pass 1 keeps its negation)
         }
       }
       pk[e2] = lis_prob_pair(ratio[0], ratio[1]);
@@ -175,7 +178,7 @@ static int launch_stream_t(const AttnArgs& a, hipStream_t st) {
     CHECK_LAUNCH();
     return 0;
   };
-  return a.probs_k ? launch(&k_lis_attention_stream<HD, true>) : launch(&k_lis_attention_stream<HD, false>);
+  return a.tapped() ? launch(&k_lis_attention_stream<HD, true>) : launch(&k_lis_attention_stream<HD, false>);
 }
 
 // tokens beyond p2v_max_tokens(head_dim), up to P2V_MAX_TOKENS_STREAMED

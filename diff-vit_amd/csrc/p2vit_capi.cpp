@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <memory>
 #include <vector>
 
@@ -568,12 +569,16 @@ struct DdvCtx {
   float* tap;                     // the one fp32 tap buffer of with_linear, or null
   int stage;
   float* scratch = nullptr;       // P2V_DDV_STAGES_FULL: the same buffer, for the fp32 LayerNorm values (set whatever with_linear says); null = the engine stages
+  int8_t* attn = nullptr;         // P2V_DDV_STAGES_ATTN: the two planes of one block's attention taps (p2v_ddv_attn_scratch_bytes); null = no such stages
 };
 // sample_stride (elements): 0 = the samples are dense, rows * cols apart; else e.g. the patch rows of a [T][cols] token layout
-static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st, long long sample_stride = 0) {
+// row_stride (elements): 0 = dense rows; else the pitch of the attention planes
+static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st, long long sample_stride = 0,
+                      long long row_stride = 0) {
   const size_t esz = dtype == P2V_COS_F32 ? 4 : 1;
-  if (!sample_stride) sample_stride = (long long)rows * cols;
-  const p2v_cos_layer l{base, reinterpret_cast<const char*>(base) + (size_t)c->n * sample_stride * esz, scale, sample_stride, cols, rows, cols, dtype};
+  if (!row_stride) row_stride = cols;
+  if (!sample_stride) sample_stride = (long long)rows * row_stride;
+  const p2v_cos_layer l{base, reinterpret_cast<const char*>(base) + (size_t)c->n * sample_stride * esz, scale, sample_stride, row_stride, rows, cols, dtype};
   const CosDesc d = p2v_cos_desc(l, c->n, 0);        // (logits / head rows of a class count that is no multiple of 4: d.vec = 0, scalar loads)
   if ((long long)c->n * d.nsplit > c->slots)
     return fail(P2V_E_WORKSPACE, "p2v_forward_ddv: a stage of %d x %d needs %lld partials, the workspace holds %lld", rows, cols,
@@ -690,9 +695,20 @@ struct Fwd {
     if ((rc = ln_linear(P2V_K_LN_GEMM_QKV, P2V_K_GEMM_QKV, P2V_EPI_REQUANT, D, M, b.ln1[bq], qkv, eq, 3 * D, QKV, false))) return rc;
     if ((rc = ddv_tap(T, 3 * D)) || (rc = ddv_i8(QKV, T, 3 * D, nullptr))) return rc;                           // attn.qkv, attn.qact1
     // scores -> qact_attn1 -> log-int-softmax -> @v -> qact2                  vit_fquant.py:309-326
-    AttnArgs at{QKV, batch, T, p->d.num_heads, b.attn, ATT, nullptr};
+    AttnArgs at{{QKV, batch, T, p->d.num_heads, b.attn, ATT, nullptr}};
     at.nq = rs.nq;
+    int8_t* planes = (!done && o.ddv) ? o.ddv->attn : nullptr;              // P2V_DDV_STAGES_ATTN: the tapped launch, both planes of this block
+    const int pitch = round_up(T, 16), HT = p->d.num_heads * T;
+    if (planes) {
+      at.score_codes = planes;
+      at.probs_kp = planes + (size_t)batch * HT * pitch;
+      at.pitch = pitch;
+    }
     if ((rc = step(P2V_K_ATTENTION, [&] { return launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"); }))) return rc;
+    if (planes && !done &&
+        ((rc = ddv_reduce(o.ddv, at.score_codes, HT, T, P2V_COS_I8, nullptr, st, 0, pitch)) ||                      // attn.qact_attn1
+         (rc = ddv_reduce(o.ddv, at.probs_kp, HT, T, P2V_COS_LOG2K, nullptr, st, 0, pitch))))                        // attn.log_int_softmax
+      return rc;
     if ((rc = ddv_i8(ATT, T, D, nullptr))) return rc;                                                            // attn.qact2
     // proj -> qact3 -> + x -> Block.qact2, in place on x                      vit_fquant.py:334-338,431
     p2v_epilogue ep = b.proj_epi;
@@ -1063,16 +1079,36 @@ int p2v_ln_gemm_fusable(int kind, int C, int N, int cells) {
 }
 
 // both attention entry points; query_rows 0 (below min_rows for the entry point that takes a count): every row
+// the pitched tap planes of the two _taps entry points: checked only when one is given
+static int check_tap_planes(const char* who, int row, int pitch, std::initializer_list<const void*> planes) {
+  bool any = false;
+  for (const void* q : planes) any = any || q;
+  if (!any) return P2V_OK;
+  if (pitch < row || pitch % 16) return fail(P2V_E_ARG, "%s: pitch %d must be a multiple of 16 and at least the row length %d", who, pitch, row);
+  for (const void* q : planes)
+    if ((uintptr_t)q % 16) return fail(P2V_E_ARG, "%s: the tap planes must be 16-byte aligned", who);
+  return P2V_OK;
+}
+
 static int lis_attention(const char* who, const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int min_rows,
-                         int query_rows, int8_t* out, int8_t* probs_k, void* stream) {
+                         int query_rows, int8_t* out, int8_t* probs_k, void* stream, int8_t* score_codes = nullptr, int8_t* probs_kp = nullptr,
+                         int pitch = 0) {
   if (!qkv || !at || !out) return fail(P2V_E_ARG, "%s: null argument", who);
   if (batch <= 0 || tokens <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad attention shape");
   if (query_rows < min_rows || query_rows > tokens) return fail(P2V_E_SHAPE, "%s: query_rows %d outside 1 .. %d", who, query_rows, tokens);
   const int rc = check_attn(who, *at);
   if (rc != P2V_OK) return rc;
-  AttnArgs a{qkv, batch, tokens, heads, *at, out, probs_k};
+  const int rp = check_tap_planes(who, tokens, pitch, {score_codes, probs_kp});
+  if (rp != P2V_OK) return rp;
+  AttnArgs a{{qkv, batch, tokens, heads, *at, out, probs_k}};
   a.nq = query_rows;
+  a.score_codes = score_codes; a.probs_kp = probs_kp; a.pitch = pitch;
   return launch_rc(p2v_launch_attention(a, head_dim, (hipStream_t)stream), "lis_attention");
+}
+
+int p2v_lis_attention_taps(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int8_t* out,
+                           int8_t* score_codes, int8_t* probs_k, int pitch, void* stream) {
+  return lis_attention("p2v_lis_attention_taps", qkv, batch, tokens, heads, head_dim, at, 0, 0, out, nullptr, stream, score_codes, probs_k, pitch);
 }
 
 int p2v_lis_attention(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int8_t* out,
@@ -1099,8 +1135,8 @@ int p2v_avgpool_quant(const int8_t* x, int batch, int tokens, int C, float s_in,
   return launch_rc(p2v_launch_avgpool_quant(x, batch, tokens, C, s_in, inv_s_out, out, (hipStream_t)stream), "avgpool_quant");
 }
 
-int p2v_window_attention(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
-                         int8_t* out, int8_t* probs_k, void* stream) {
+static int window_attention(const char* who, const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                            int8_t* out, int8_t* probs_k, void* stream, int8_t* attn1_codes, int8_t* qact2_codes, int8_t* probs_kp, int pitch) {
   if (!qkv || !wa || !out || !wa->table_codes || !wa->win_index) return fail(P2V_E_ARG, "p2v_window_attention: null argument");
   if (batch <= 0 || tokens_per_image <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad window attention shape");
   if (head_dim != 32) return fail(P2V_E_UNSUPPORTED, "window attention: head_dim must be 32");
@@ -1121,8 +1157,22 @@ int p2v_window_attention(const int8_t* qkv, int batch, int tokens_per_image, int
   if (wa->s_q2 > 1.0f) return fail(P2V_E_UNSUPPORTED, "window attention: qact2 scale above 1 (the -100 mask would not be an integer)");
   if (wa->s_q1 / wa->s_q3 > 0x1p15f || wa->s_q1 / wa->s_q3 < 0x1p-40f)
     return fail(P2V_E_UNSUPPORTED, "window attention: qact1 scale / qact3 scale must lie in [2^-40, 2^15]");
-  WinAttnArgs a{qkv, batch, tokens_per_image, heads, *wa, out, probs_k};
+  const int rp = check_tap_planes(who, wa->ws * wa->ws, pitch, {attn1_codes, qact2_codes, probs_kp});
+  if (rp != P2V_OK) return rp;
+  WinAttnArgs a{{qkv, batch, tokens_per_image, heads, *wa, out, probs_k}};
+  a.attn1_codes = attn1_codes; a.qact2_codes = qact2_codes; a.probs_kp = probs_kp; a.pitch = pitch;
   return launch_rc(p2v_launch_window_attention(a, (hipStream_t)stream), "window_attention");
+}
+
+int p2v_window_attention(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                         int8_t* out, int8_t* probs_k, void* stream) {
+  return window_attention("p2v_window_attention", qkv, batch, tokens_per_image, heads, head_dim, wa, out, probs_k, stream, nullptr, nullptr, nullptr, 0);
+}
+
+int p2v_window_attention_taps(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                              int8_t* out, int8_t* attn1_codes, int8_t* qact2_codes, int8_t* probs_k, int pitch, void* stream) {
+  return window_attention("p2v_window_attention_taps", qkv, batch, tokens_per_image, heads, head_dim, wa, out, nullptr, stream, attn1_codes,
+                          qact2_codes, probs_k, pitch);
 }
 
 // the layer output fmaf(acc, colscale, bias) as dense fp32 (P2V_OP_GEMM_F32): what a QLinear / QConv2d hook sees.  The public p2v_gemm_i8
@@ -1138,7 +1188,7 @@ static int gemm_f32_op(const p2v_op& o, void* stream) {
 static int cos_check(const p2v_cos_layer* layers, int n_layers, int n, const char* what);
 static p2v_cos_layer cos_op_layer(const p2v_op& o) {
   const long long sample = (long long)(((unsigned long long)(unsigned)o.i3 << 32) | (unsigned)o.i2);
-  const size_t esz = o.i1 == P2V_COS_I8 ? 1 : 4;
+  const size_t esz = o.i1 == P2V_COS_F32 ? 4 : 1;
   const char* a = reinterpret_cast<const char*>(o.in);
   return p2v_cos_layer{a, a ? a + (size_t)(o.i0 > 0 ? o.i0 : 0) * (size_t)(sample > 0 ? sample : 0) * esz : nullptr, o.lin.colscale, sample, o.lda, o.M, o.N, o.i1};
 }
@@ -1173,7 +1223,9 @@ static int run_one_op(const p2v_op& o, void* stream) {
     case P2V_OP_LAYERNORM:
       return p2v_int_layernorm((const int8_t*)o.in, o.lda, o.M, o.N, &o.ln, (int8_t*)o.out, o.ldo, stream);
     case P2V_OP_WINATTN:
-      return p2v_window_attention((const int8_t*)o.in, o.i0, o.i1, o.i2, o.i3, &o.wa, (int8_t*)o.out, nullptr, stream);
+      // (additive) the planes of p2v_window_attention_taps in members this kind did not read before: all NULL = the untapped launch
+      return p2v_window_attention_taps((const int8_t*)o.in, o.i0, o.i1, o.i2, o.i3, &o.wa, (int8_t*)o.out, const_cast<int8_t*>(o.lin.w_codes),
+                                       const_cast<int8_t*>(o.lin.w_frag), reinterpret_cast<int8_t*>(o.ep.tap_out), o.ldo, stream);
     case P2V_OP_MERGE:
       return p2v_patch_merge_gather((const int8_t*)o.in, o.i0, o.i1, o.i2, o.i3, (int8_t*)o.out, stream);
     case P2V_OP_AVGPOOL:
@@ -1343,16 +1395,20 @@ static int cos_check(const p2v_cos_layer* layers, int n_layers, int n, const cha
   for (int l = 0; l < n_layers; ++l) {
     const p2v_cos_layer& a = layers[l];
     if (!a.a || !a.b) return fail(P2V_E_ARG, "%s: layer %d has a null operand", what, l);
-    if (a.dtype != P2V_COS_I8 && a.dtype != P2V_COS_F32) return fail(P2V_E_ARG, "%s: layer %d: dtype %d (0 = int8, 1 = fp32)", what, l, a.dtype);
+    if (a.dtype != P2V_COS_I8 && a.dtype != P2V_COS_F32 && a.dtype != P2V_COS_LOG2K)
+      return fail(P2V_E_ARG, "%s: layer %d: dtype %d (0 = int8, 1 = fp32, 3 = log2 exponents)", what, l, a.dtype);
+    if (a.scale && a.dtype == P2V_COS_LOG2K) return fail(P2V_E_ARG, "%s: layer %d: the log2-exponent form takes no scales", what, l);
     if (a.rows < 1 || a.cols < 1) return fail(P2V_E_SHAPE, "%s: layer %d: %d rows x %d cols", what, l, a.rows, a.cols);
     if (a.row_stride < a.cols) return fail(P2V_E_ARG, "%s: layer %d: row_stride %lld < cols %d", what, l, a.row_stride, a.cols);
     if (a.sample_stride < 0) return fail(P2V_E_ARG, "%s: layer %d: negative sample_stride %lld", what, l, a.sample_stride);
     if (a.scale && a.dtype != P2V_COS_I8) return fail(P2V_E_UNSUPPORTED, "%s: layer %d: per-channel scales go with int8 codes", what, l);
-    const long long esz = a.dtype == P2V_COS_I8 ? 1 : 4;
+    const long long esz = a.dtype == P2V_COS_F32 ? 4 : 1;
     if ((uintptr_t)a.a % 16 || (uintptr_t)a.b % 16 || a.sample_stride * esz % 16 || a.row_stride * esz % 16)
       return fail(P2V_E_ARG, "%s: layer %d: pointers and strides must be multiples of 16 bytes", what, l);
     if (a.dtype == P2V_COS_I8 && (long long)a.rows * a.cols >= (1LL << 39))
       return fail(P2V_E_UNSUPPORTED, "%s: layer %d: %d x %d codes per sample leave the exact fp64 range", what, l, a.rows, a.cols);
+    if (a.dtype == P2V_COS_LOG2K && (long long)a.rows * a.cols >= (1LL << 33))       // 2^30 per element: the int64 sums cannot overflow below this
+      return fail(P2V_E_UNSUPPORTED, "%s: layer %d: %d x %d exponents per sample", what, l, a.rows, a.cols);
   }
   return P2V_OK;
 }
@@ -1484,6 +1540,13 @@ int p2v_ddv_stage_count_ex(const p2v_plan* plan, int with_linear, int stage_set)
   return 5 * plan->d.depth + 3 + (with_linear ? 4 * plan->d.depth + 1 : 0) + (stage_set == P2V_DDV_STAGES_FULL ? 4 * plan->d.depth + 4 : 0);
 }
 int p2v_ddv_stage_count(const p2v_plan* plan, int with_linear) { return p2v_ddv_stage_count_ex(plan, with_linear, P2V_DDV_STAGES_ENGINE); }
+int p2v_ddv_stage_count_ex2(const p2v_plan* plan, int with_linear, int stage_set) {
+  if (!plan) return fail(P2V_E_ARG, "p2v_ddv_stage_count: null plan");
+  if (stage_set < 0 || stage_set > (P2V_DDV_STAGES_FULL | P2V_DDV_STAGES_ATTN))
+    return fail(P2V_E_ARG, "p2v_ddv_stage_count_ex2: unknown stage_set %d (ENGINE = 0 or FULL = 1, optionally | P2V_DDV_STAGES_ATTN = 2)", stage_set);
+  const int base = p2v_ddv_stage_count_ex(plan, with_linear, stage_set & ~P2V_DDV_STAGES_ATTN);
+  return base < 0 ? base : base + ((stage_set & P2V_DDV_STAGES_ATTN) ? 2 * plan->d.depth : 0);
+}
 
 // workgroups of the largest stage: p2v_cos_desc gives a sample at most 2048 / n (>= 1) splits while its rows stay below 2^16 per split -
 // true of every stage here (at most 4096 tokens); ddv_reduce checks each stage against this count before it launches
@@ -1504,8 +1567,15 @@ size_t p2v_ddv_tap_scratch_bytes(const p2v_plan* plan, int n) {
   return (tok > head ? tok : head) * sizeof(float);
 }
 
-int p2v_forward_ddv_ex(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
-                       size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream) {
+// bytes of the two attention planes (score codes, exponents) of the 2n images of ONE block, rows pitched to whole 16-byte groups
+size_t p2v_ddv_attn_scratch_bytes(const p2v_plan* plan, int n) {
+  if (!plan || n <= 0 || n > (1 << 29)) return 0;
+  return (size_t)2 * 2 * n * plan->d.num_heads * plan->tokens * round_up(plan->tokens, 16);
+}
+
+static int forward_ddv_impl(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                            size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, int8_t* attn_scratch,
+                            double* sums, void* stream) {
   if (!plan || !sums || !ws) return fail(P2V_E_ARG, "p2v_forward_ddv: null argument");
   if (stage_set != P2V_DDV_STAGES_ENGINE && stage_set != P2V_DDV_STAGES_FULL)
     return fail(P2V_E_ARG, "p2v_forward_ddv_ex: unknown stage_set %d (P2V_DDV_STAGES_ENGINE = 0, P2V_DDV_STAGES_FULL = 1)", stage_set);
@@ -1529,6 +1599,7 @@ int p2v_forward_ddv_ex(p2v_plan* plan, const float* images, int n, const int8_t*
   DdvCtx ctx{n, reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + fwd), ddv_partial_slots(n), sums,
              with_linear ? tap_scratch : nullptr, 0};
   ctx.scratch = full ? tap_scratch : nullptr;
+  ctx.attn = attn_scratch;
   std::vector<float*> taps;
   if (with_linear) {
     taps.assign(plan->n_layers, tap_scratch);      // every linear output goes through the one buffer; the patch embedding is no DDV stage
@@ -1537,6 +1608,31 @@ int p2v_forward_ddv_ex(p2v_plan* plan, const float* images, int n, const int8_t*
   FwdOpts o;
   o.images = images; o.ddv = &ctx; o.lin_tap = with_linear ? taps.data() : nullptr;
   return forward_impl(plan, 2 * n, bit_config, n_cfg, logits, ws, fwd, stream, o);
+}
+
+int p2v_forward_ddv_ex(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                       size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream) {
+  return forward_ddv_impl(plan, images, n, bit_config, n_cfg, logits, ws, ws_bytes, with_linear, stage_set, tap_scratch, tap_scratch_bytes, nullptr,
+                          sums, stream);
+}
+
+// the stage sets with P2V_DDV_STAGES_ATTN or-ed on: the flag's own refusals first (before any launch), the rest is p2v_forward_ddv_ex's
+int p2v_forward_ddv_ex2(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                        size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, int8_t* attn_scratch,
+                        size_t attn_scratch_bytes, double* sums, void* stream) {
+  if (stage_set < 0 || stage_set > (P2V_DDV_STAGES_FULL | P2V_DDV_STAGES_ATTN))
+    return fail(P2V_E_ARG, "p2v_forward_ddv_ex2: unknown stage_set %d (ENGINE = 0 or FULL = 1, optionally | P2V_DDV_STAGES_ATTN = 2)", stage_set);
+  if (!(stage_set & P2V_DDV_STAGES_ATTN))
+    return forward_ddv_impl(plan, images, n, bit_config, n_cfg, logits, ws, ws_bytes, with_linear, stage_set, tap_scratch, tap_scratch_bytes, nullptr,
+                            sums, stream);
+  if (!plan) return fail(P2V_E_ARG, "p2v_forward_ddv_ex2: null argument");
+  const size_t need = p2v_ddv_attn_scratch_bytes(plan, n);
+  if (n <= 0 || !need) return fail(P2V_E_SHAPE, "p2v_forward_ddv: n = %d pairs", n);
+  if (!attn_scratch) return fail(P2V_E_ARG, "p2v_forward_ddv_ex2: P2V_DDV_STAGES_ATTN needs attn_scratch (%zu bytes)", need);
+  if ((uintptr_t)attn_scratch % 16) return fail(P2V_E_ARG, "p2v_forward_ddv_ex2: attn_scratch must be 16-byte aligned");
+  if (attn_scratch_bytes < need) return fail(P2V_E_WORKSPACE, "p2v_forward_ddv_ex2: attn_scratch %zu < %zu bytes", attn_scratch_bytes, need);
+  return forward_ddv_impl(plan, images, n, bit_config, n_cfg, logits, ws, ws_bytes, with_linear, stage_set & ~P2V_DDV_STAGES_ATTN, tap_scratch,
+                          tap_scratch_bytes, attn_scratch, sums, stream);
 }
 
 int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,

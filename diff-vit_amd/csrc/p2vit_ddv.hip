@@ -8,6 +8,8 @@
 //                     int8, scale[cols]  per-channel int32 sums over the thread's rows (<= 2^16 rows * 2^14: the splitting guarantees it),
 //                                        then sum_c (double)s_c * (double)s_c * S_c in channel order, fp64
 //                     fp32               fp64 products (exact) and fp64 accumulation in row order
+//                     log2 exponents     (P2V_COS_LOG2K) a byte k is the probability 2^-k (0 from k = 16 on): the integer 2^(15-k), products
+//                                        <= 2^30 into int64, the same tree and splits; converted once and scaled by 2^-30
 //                   The 256 per-thread values are added over a fixed LDS tree and stored as the split's partial (int64 bits for the
 //                   exact form, fp64 otherwise).
 //   k_cos_combine   one thread per (stage, sample): the split partials in split order; int64 -> fp64 once for the exact form.
@@ -76,7 +78,7 @@ __device__ __forceinline__ void cos_partial_body(const CosDesc& d, long long loc
   __shared__ union { double d[3][256]; long long i[3][256]; } red;      // one tree buffer: int64 for the exact form, fp64 otherwise
   const int sample = (int)(local / d.nsplit), split = (int)(local % d.nsplit);
   const int r0 = split * d.rows_per_split, r1 = min(d.rows, r0 + d.rows_per_split);
-  const int per = d.dtype == 0 ? 16 : 4;                         // elements of a 16-byte column group
+  const int per = d.dtype == P2V_COS_F32 ? 4 : 16;               // elements of a 16-byte column group
   const int ncg = (d.cols + per - 1) / per;
   const int cgt = min(ncg, 256), lanes = 256 / cgt;              // column groups side by side, row lanes behind each other
   const int t = threadIdx.x, cgl = t % cgt, rl = t / cgt;
@@ -101,6 +103,32 @@ __device__ __forceinline__ void cos_partial_body(const CosDesc& d, long long loc
             bb = COS_DOT4(vb[q], vb[q], bb);
           }
           sab += ab; saa += aa; sbb += bb;
+        }
+      }
+    cos_block_sum(red.i, sab, saa, sbb, out);
+    return;
+  }
+  if (d.dtype == P2V_COS_LOG2K) {
+    // exponents of the log2 softmax: p = 2^-k, k <= 15, else 0.  In units of 2^-15 the value is the integer 1 << (15 - k), the product of two at
+    // most 2^30: sixteen of them fit a uint64 many times over, and the sample's sum stays below 2^53 (p2vit.h says why)
+    long long sab = 0, saa = 0, sbb = 0;
+    const int8_t* A = reinterpret_cast<const int8_t*>(d.a) + s_off;
+    const int8_t* B = reinterpret_cast<const int8_t*>(d.b) + s_off;
+    if (active)
+      for (int cg = cgl; cg < ncg; cg += cgt) {
+        const int c0 = cg * 16, valid = min(16, d.cols - c0);
+#pragma unroll 2
+        for (int r = r0 + rl; r < r1; r += lanes) {
+          const long long o = (long long)r * d.row_stride + c0;
+          const v4i va = cos_load_i8(A + o, valid, vec), vb = cos_load_i8(B + o, valid, vec);
+          unsigned long long ab = 0, aa = 0, bb = 0;
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const unsigned ka = ((unsigned)va[j >> 2] >> (8 * (j & 3))) & 255u, kb = ((unsigned)vb[j >> 2] >> (8 * (j & 3))) & 255u;
+            const unsigned long long x = (j < valid && ka < 16u) ? 1ull << (15 - ka) : 0ull, y = (j < valid && kb < 16u) ? 1ull << (15 - kb) : 0ull;
+            ab += x * y; aa += x * x; bb += y * y;
+          }
+          sab += (long long)ab; saa += (long long)aa; sbb += (long long)bb;
         }
       }
     cos_block_sum(red.i, sab, saa, sbb, out);
@@ -156,13 +184,14 @@ __device__ __forceinline__ void cos_partial_body(const CosDesc& d, long long loc
 __device__ __forceinline__ void cos_combine_body(const CosDesc& d, int sample, const unsigned long long* __restrict__ partials,
                                                  double* __restrict__ out) {
   const unsigned long long* p = partials + (d.item0 + (long long)sample * d.nsplit) * 3;
-  if (d.dtype == 0 && !d.scale) {
+  if ((d.dtype == 0 && !d.scale) || d.dtype == P2V_COS_LOG2K) {
     long long s[3] = {0, 0, 0};
     for (int k = 0; k < d.nsplit; ++k)
 #pragma unroll
       for (int q = 0; q < 3; ++q) s[q] += (long long)p[3 * k + q];
+    const double unit = d.dtype == P2V_COS_LOG2K ? 0x1p-30 : 1.0;   // the exponent form counts in units of 2^-15 per value: a power of two, exact
 #pragma unroll
-    for (int q = 0; q < 3; ++q) out[q] = (double)s[q];              // exact: |s| < 2^53 (checked by the host)
+    for (int q = 0; q < 3; ++q) out[q] = (double)s[q] * unit;       // exact: |s| < 2^53 (checked by the host)
     return;
   }
   double s[3] = {0.0, 0.0, 0.0};

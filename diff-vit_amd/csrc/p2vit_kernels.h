@@ -45,7 +45,9 @@ struct LnArgs {
   float* tap_out;       // optional: fp32 [rows][C], the unclamped integer output times out_scale (k_int_layernorm's TAP form, C <= 2048)
 };
 
-struct AttnArgs {
+// AttnKArgs is the kernel argument of every UNTAPPED attention instantiation: its layout stays as it is, so that those kernels compile to
+// the code they had; the tapped instantiations take AttnArgs, which the host side passes around (it converts to its base at the launch)
+struct AttnKArgs {
   const int8_t* qkv;
   int B, N, H;
   p2v_attn at;
@@ -57,13 +59,30 @@ struct AttnArgs {
   unsigned long long* stamps;   // diagnostic build only: 16 cycle stamps per workgroup (wave 0) or null
 #endif
 };
+struct AttnArgs : AttnKArgs {
+  // pitched taps (p2v_lis_attention_taps; each optional): [B][H][N][pitch] int8, pitch >= N a multiple of 16; only the columns [0, N) of a
+  // row are written.  Any of them (or probs_k) selects the TAP instantiation
+  int8_t* score_codes;  // qact_attn1 codes of every (query, key) pair
+  int8_t* probs_kp;     // the exponents of probs_k in the pitched layout
+  int pitch;
+  bool tapped() const { return probs_k || score_codes || probs_kp; }
+};
 
-struct WinAttnArgs {
+struct WinAttnKArgs {      // the untapped instantiations' argument, as AttnKArgs
   const int8_t* qkv;
   int B, T, H;          // images, tokens per image, heads
   p2v_winattn wa;
   int8_t* out;
   int8_t* probs_k;
+};
+struct WinAttnArgs : WinAttnKArgs {
+  // pitched taps (p2v_window_attention_taps; each optional): [B][n_windows][H][N][pitch] int8, pitch >= N a multiple of 16; only the
+  // columns [0, N) of a row are written.  Any of them (or probs_k) selects the TAP instantiation
+  int8_t* attn1_codes;  // qact_attn1 codes
+  int8_t* qact2_codes;  // qact2 codes: behind the bias-table add, in front of the mask
+  int8_t* probs_kp;     // the exponents of probs_k in the pitched layout
+  int pitch;
+  bool tapped() const { return probs_k || attn1_codes || qact2_codes || probs_kp; }
 };
 int p2v_launch_patch_merge_gather(const int8_t* x, int B, int H, int W, int C, int8_t* out, hipStream_t st);
 int p2v_launch_avgpool_quant(const int8_t* x, int B, int T, int C, float s_in, float inv_s_out, int8_t* out, hipStream_t st);
@@ -128,7 +147,7 @@ int p2v_launch_cka_grams(const std::vector<CkaDesc>& descs, const CkaLayout& w, 
 int p2v_launch_hsic(const float* g1, int l1, const float* g2, int l2, int n, void* acc, void* self1, void* self2, int dtype, hipStream_t st);
 
 // pair-cosine sums of the DDV model diff (p2vit_ddv.hip): one record per stage
-#define P2V_COS_I8_DEQ 2   // internal dtype of p2v_launch_pair_cosine_one: int8 codes, every value the fp32 product RN(code * scale[c]) (scale required)
+#define P2V_COS_I8_DEQ 64  // internal dtype of p2v_launch_pair_cosine_one: int8 codes, every value the fp32 product RN(code * scale[c]) (scale required)
 struct CosDesc {
   const void* a;
   const void* b;
@@ -136,7 +155,7 @@ struct CosDesc {
   long long sample_stride, row_stride;   // in elements
   long long item0;       // first workgroup of the stage in k_cos_partial's grid (0 for a stage launched alone)
   int rows, cols;
-  int dtype;             // P2V_COS_I8 / P2V_COS_F32
+  int dtype;             // P2V_COS_I8 / P2V_COS_F32 / P2V_COS_LOG2K (p2v_launch_pair_cosine_one: also P2V_COS_I8_DEQ)
   int vec;               // pointers and strides are 16-byte aligned: whole column groups are read with one 16-byte load
   int nsplit;            // workgroups per sample
   int rows_per_split;

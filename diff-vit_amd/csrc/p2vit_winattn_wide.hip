@@ -48,7 +48,7 @@ struct WinWide {
 };
 
 template <int WS, bool TAP>
-__global__ __launch_bounds__(256, 2) void k_window_attention_wide(WinAttnArgs a) {
+__global__ __launch_bounds__(256, 2) void k_window_attention_wide(std::conditional_t<TAP, WinAttnArgs, WinAttnKArgs> a) {
   typedef WinWide<WS> G;
   constexpr int N = G::N, NKB = G::NKB, NP = G::NP, KR = G::KR, VR = G::VR, VSTRIDE = G::VSTRIDE, TSZ = G::TSZ;
   static_assert(WS >= 9 && WS <= 12, "window size");
@@ -249,6 +249,11 @@ __global__ __launch_bounds__(256, 2) void k_window_attention_wide(WinAttnArgs a)
           const float a1 = xs[kb][r];
           const float a2 = __builtin_amdgcn_fmed3f(rintf(__builtin_fmaf(a1, a1_mul, trow[-(int)(WW_META(kb, r) & 1023u)])), -128.f, 127.f);   // qact2
           float xi = a2;
+          if constexpr (TAP) if (qi < N && kb * 16 + 4 * g + r < N) {            // the two QActs in front of the mask, from the registers that feed the next step
+            const long long at = ((((long long)b * nW + w) * a.H + head) * N + qi) * a.pitch + kb * 16 + 4 * g + r;
+            if (a.attn1_codes) a.attn1_codes[at] = (int8_t)(int)a1;
+            if (a.qact2_codes) a.qact2_codes[at] = (int8_t)(int)a2;
+          }
           if (MASK) xi -= (WW_META(kb, r) >> 10) != reg_i ? m100 : 0.f;
           if (WW_PAD(kb, r)) xi = kb * 16 + 4 * g + r < N ? xi : -3.0e9f;
           xs[kb][r] = xi;
@@ -295,9 +300,11 @@ __global__ __launch_bounds__(256, 2) void k_window_attention_wide(WinAttnArgs a)
           }
           // correctly rounded fp32 quotient, as in k_lis_attention; a padding key (entry 257: reciprocal 1) gives sum / 1 >= 2^32 -> k clamps -> 0
           ratio[e] = rintf((float)(Sd * lutFR[s1[kb][r]]));
-          if (TAP && qi < N && kb * 16 + 4 * g + r < N) {
+          if constexpr (TAP) if (qi < N && kb * 16 + 4 * g + r < N) {
             const int k = (int)((__float_as_uint(ratio[e]) + 0x00400000u) >> 23) - 127;
-            a.probs_k[((((long long)b * nW + w) * a.H + head) * N + qi) * N + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
+            const long long trow = (((long long)b * nW + w) * a.H + head) * N + qi;
+            if (a.probs_k) a.probs_k[trow * N + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
+            if (a.probs_kp) a.probs_kp[trow * a.pitch + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
           }
         }
         pk[e2] = lis_prob_pair(ratio[0], ratio[1]);              // 2^-k * 2^-111 as bf16, 0 from k = 16 on (see k_lis_attention)
@@ -357,7 +364,7 @@ static int launch_winattn_wide_t(const WinAttnArgs& a, hipStream_t st) {
     }                                                                                                                        \
     hipLaunchKernelGGL((k_window_attention_wide<WS, TAP_>), grid, dim3(256), smem, st, a);                                   \
   } while (0)
-  if (a.probs_k) P2V_WW_LAUNCH(true);
+  if (a.tapped()) P2V_WW_LAUNCH(true);
   else P2V_WW_LAUNCH(false);
 #undef P2V_WW_LAUNCH
   CHECK_LAUNCH();

@@ -1,6 +1,6 @@
 """DDV model diff: ModelDiff's "decision distance vector" per layer (the reference's modeldiff_p2.py), on the fused engine.
 
-    compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True, stages='engine')     modeldiff_p2.py:84-116
+    compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True, stages='engine', attention=False)     modeldiff_p2.py:84-116
     similarity(ddv_a, ddv_b)                 per-stage cosine of two DDVs (ModelDiff's metric)
     reference_similarity(ddv_a, ddv_b)       what calculate_and_print_similarities prints    modeldiff_p2.py:118-131
     AttackPGD / gen_adv_inputs(model, inputs, epsilon=0.3, step_size=0.01, num_steps=50)     modeldiff_p2.py:152-194
@@ -33,14 +33,23 @@ mlp.qact2 (the mid codes of the RESID launches) and ``norm`` over all rows.  ``q
 here from the plan's calibration - the length-1 vector [1.0], or NaN when every code of the position embedding is zero, as numpy gives in
 the reference.  Any other state hooks the same-named modules.
 
-Not covered: the QActs inside the attention kernels (ViT: qact_attn1 and the softmax; Swin: qact_attn1, qact2, qact_table, the softmax); DDV
+``attention=True`` adds the QActs INSIDE the attention kernels, where P2-ViT quantizes hardest: per ViT / DeiT block
+``attn.qact_attn1`` (the int8 score codes) and ``attn.log_int_softmax`` (the output of QIntSoftmax: probabilities 0 and 2^-k, k = 0 ... 15),
+in module order between attn.qact1 and attn.qact2; per Swin block ``attn.qact_attn1``, ``attn.qact2`` and ``attn.log_int_softmax`` between
+attn.qact1 and attn.qact3.  On a fused model it is still the ONE engine call: the attention launch runs its tapped instantiation, which stores
+the score codes and the exponents k of one block into a scratch (``FrozenPlan.ddv_attn_bytes``) that is reduced right behind the launch - the
+codes as exact integer sums, the exponents as exact sums of 2^(30 - ka - kb) (``P2V_COS_LOG2K``) - and reused by the next block.  Any other
+state hooks the same-named modules (there ``log_int_softmax`` is the module's output, a plain softmax in a float model).  Swin's
+``attn.qact_table`` quantizes a parameter, not an activation: it is no stage.
+
+Not covered: DDV
 on sliced streams; the FULL stages of an ``input_quant=False`` model on the engine (the reference's own ``add_hooks`` fails there: no
 qact_input); and forward hooks of your own on QAct / QIntLayerNorm modules of a fused model - they never fire, because the engine
 bypasses the module graph (hooks on QLinear / QConv2d are served, see ``cka``).
 
 ``python -m diff_vit_amd.ddv --model deit_small --bits 8 --n 50`` (or ``--model swin_tiny``; ``--bits mixed`` is refused for Swin) prints
 the float-vs-quantized similarity per stage on the synthetic data of ``harness`` and writes ``ddv_result/ddv.pkl``; ``--stages full``
-prints every hook point of the reference's list.  ``--inputs blackbox
+prints every hook point of the reference's list, ``--attention`` also the stages inside the attention kernels.  ``--inputs blackbox
 --mut-iters 1000`` takes the perturbed twins from ``profiling.gen_profiling_inputs_in_blackbox`` on (float model, quantized model) instead
 of PGD (the default, ``--inputs pgd``)."""
 import argparse
@@ -54,29 +63,32 @@ import torch.nn as nn
 from . import ops  # noqa: F401  (registers torch.ops.p2vit.*)
 
 
-def stage_names(depth, with_linear=True, full=False):
+def stage_names(depth, with_linear=True, full=False, attention=False):
     """the DDV stages in module order, the one list ``FrozenPlan.forward_ddv`` and the module-graph path share.  ``full``: plus the stages
-    behind the reference's remaining hook points (``P2V_DDV_STAGES_FULL``; qact_pos, which no input reaches, is not a stage)."""
+    behind the reference's remaining hook points (``P2V_DDV_STAGES_FULL``; qact_pos, which no input reaches, is not a stage).
+    ``attention``: plus the two QActs inside the attention kernel (``P2V_DDV_STAGES_ATTN``), 2 per block."""
     names = (['qact_input', 'patch_embed.qact', 'qact_embed'] if full else []) + ['qact1']
     for i in range(depth):
         p = 'blocks.%d.' % i
-        names += ([p + 'norm1'] if full else []) + ([p + 'attn.qkv'] if with_linear else []) + [p + 'attn.qact1', p + 'attn.qact2']
+        names += ([p + 'norm1'] if full else []) + ([p + 'attn.qkv'] if with_linear else []) + [p + 'attn.qact1']
+        names += ([p + 'attn.qact_attn1', p + 'attn.log_int_softmax'] if attention else []) + [p + 'attn.qact2']
         names += ([p + 'attn.proj'] if with_linear else []) + ([p + 'attn.qact3'] if full else []) + [p + 'qact2']
         names += ([p + 'norm2'] if full else []) + ([p + 'mlp.fc1'] if with_linear else []) + [p + 'mlp.qact1']
         names += ([p + 'mlp.fc2'] if with_linear else []) + ([p + 'mlp.qact2'] if full else []) + [p + 'qact4']
     return names + (['norm'] if full else []) + ['qact2'] + (['head'] if with_linear else []) + ['act_out']
 
 
-def swin_stage_names(depths, with_linear=True):
+def swin_stage_names(depths, with_linear=True, attention=False):
     """the DDV stages of a Swin model in execution order (a linear layer in front of the QAct that follows it), the one list
     ``SwinPlan.forward_ddv`` and the module-graph path share: 9 per block, 2 per merge, 5 fixed; ``with_linear`` adds 4 per block, 1 per
-    merge and 2."""
+    merge and 2; ``attention`` the three QActs inside the window kernel, 3 per block."""
+    inner = ['attn.qact_attn1', 'attn.qact2', 'attn.log_int_softmax'] if attention else []
     lin = bool(with_linear)
     names = (['patch_embed.proj'] if lin else []) + ['patch_embed.qact_before_norm', 'patch_embed.qact']
     for li, depth in enumerate(depths):
         for bi in range(depth):
             p = 'layers.%d.blocks.%d.' % (li, bi)
-            names += [p + 'qact1'] + ([p + 'attn.qkv'] if lin else []) + [p + 'attn.qact1', p + 'attn.qact3']
+            names += [p + 'qact1'] + ([p + 'attn.qkv'] if lin else []) + [p + 'attn.qact1'] + [p + k for k in inner] + [p + 'attn.qact3']
             names += ([p + 'attn.proj'] if lin else []) + [p + 'attn.qact4', p + 'qact2', p + 'qact3']
             names += ([p + 'mlp.fc1'] if lin else []) + [p + 'mlp.qact1'] + ([p + 'mlp.fc2'] if lin else []) + [p + 'mlp.qact2', p + 'qact4']
         if li < len(depths) - 1:
@@ -202,7 +214,7 @@ def _swin_hooked_outputs(model, x, names):
     return [got[nm].reshape(x.shape[0], -1) for nm in names]
 
 
-def _compute_ddv_swin(model, x, xa, bit_config, with_linear):
+def _compute_ddv_swin(model, x, xa, bit_config, with_linear, attention=False):
     if isinstance(bit_config, (list, tuple)):
         raise NotImplementedError('compute_ddv: a Swin model has one weight width and no per-layer bit_config list '
                                   '(swin_quant.py:813-817); pass 8, 4 or None')
@@ -214,18 +226,20 @@ def _compute_ddv_swin(model, x, xa, bit_config, with_linear):
             raise ValueError('%r is not in list' % (bit_config,))
         if model._plan is None or model._plan.bits != int(bit_config):
             model.freeze(dev, bits=int(bit_config))
-        _, names, sums = model._plan.forward_ddv(torch.cat((x, xa), 0), with_linear)
+        _, names, sums = model._plan.forward_ddv(torch.cat((x, xa), 0), with_linear, attention=attention)
         return names, sums
-    names = swin_stage_names(model.arch['depths'], with_linear)
+    names = swin_stage_names(model.arch['depths'], with_linear, attention)
     a, b = _swin_hooked_outputs(model, x, names), _swin_hooked_outputs(model, xa, names)
     if dev.type == 'cuda':
         return names, torch.ops.p2vit.pair_cosine(a, b, [None] * len(a))
     return names, pair_cosine_cpu(a, b)
 
 
-def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True, stages='engine'):
+def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=True, stages='engine', attention=False):
     """modeldiff_p2.compute_ddv:84-116 for ``model`` under ``bit_config``: dict stage name -> fp64 tensor [n] (on the model's device).
-    ``stages='full'``: every hook point of the reference's list (module docstring); the ``qact_pos`` entry has length 1."""
+    ``stages='full'``: every hook point of the reference's list (module docstring); the ``qact_pos`` entry has length 1.
+    ``attention``: also the QActs inside the attention kernels (module docstring); False returns exactly the dict without them."""
+    attention = bool(attention)
     from .swin import SwinTransformer
     from .vit import VisionTransformer
     if stages not in ('engine', 'full'):
@@ -234,11 +248,11 @@ def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=T
     if not isinstance(model, (SwinTransformer, VisionTransformer)):
         raise NotImplementedError('compute_ddv covers the ViT / DeiT and the Swin models')
     if isinstance(model, SwinTransformer) and isinstance(bit_config, (list, tuple)):
-        _compute_ddv_swin(model, normal_inputs, adv_inputs, bit_config, with_linear)       # raises
+        _compute_ddv_swin(model, normal_inputs, adv_inputs, bit_config, with_linear, attention)       # raises
     if tuple(normal_inputs.shape) != tuple(adv_inputs.shape) or normal_inputs.dim() != 4 or normal_inputs.shape[0] < 1:
         raise AssertionError('compute_ddv: clean and perturbed inputs must be two [n, C, H, W] batches of one shape')
     if isinstance(model, SwinTransformer):
-        names, sums = _compute_ddv_swin(model, normal_inputs, adv_inputs, bit_config, with_linear)
+        names, sums = _compute_ddv_swin(model, normal_inputs, adv_inputs, bit_config, with_linear, attention)
         d = ddv_from_sums(sums)
         return {nm: d[k] for k, nm in enumerate(names)}
     dev = _device_of(model)
@@ -250,12 +264,13 @@ def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=T
             raise ValueError('None is not in list')              # bit_pool.index(None), vit_fquant.py:282
         if model._plan is None:
             model.freeze(dev)
-        _, names, sums = model._plan.forward_ddv(torch.cat((x, xa), 0), [int(b) for b in bit_config], with_linear, stages=stages)
+        _, names, sums = model._plan.forward_ddv(torch.cat((x, xa), 0), [int(b) for b in bit_config], with_linear, stages=stages,
+                                                 **({'attention': True} if attention else {}))
         pos = _qact_pos_ddv(model._plan.qact_pos_all_zero, dev) if full else None
     else:
         if full and not getattr(model, 'input_quant', True):
             raise AttributeError("compute_ddv(stages='full'): the model has no qact_input (input_quant=False), as in the reference's add_hooks")
-        names = stage_names(model.depth, with_linear, full)
+        names = stage_names(model.depth, with_linear, full, attention)
         hooked = _with_qact_pos(names) if full else names
         a = _hooked_outputs(model, x, bit_config, hooked, fused_state)
         b = _hooked_outputs(model, xa, bit_config, hooked, fused_state)
@@ -364,6 +379,8 @@ def main(argv=None):
     p.add_argument('--steps', default=50, type=int, help='PGD steps')
     p.add_argument('--stages', default='engine', choices=['engine', 'full'],
                    help='full: every hook point of the reference\'s add_hooks (ViT / DeiT; a Swin list is already its full one)')
+    p.add_argument('--attention', action='store_true',
+                   help='also the QActs inside the attention kernels: qact_attn1 and the log2 softmax (Swin: and attn.qact2)')
     p.add_argument('--inputs', default='pgd', choices=['pgd', 'blackbox'],
                    help='the perturbed twins: PGD on the float model, or ModelDiff\'s black-box search on (float, quantized)')
     p.add_argument('--mut-iters', default=1000, type=int, help='iterations of the black-box search (--inputs blackbox)')
@@ -400,8 +417,8 @@ def main(argv=None):
     else:
         torch.manual_seed(args.seed)
         adv = gen_adv_inputs(fp, x, num_steps=args.steps)
-    d_fp = compute_ddv(fp, x, adv, None, stages=args.stages)
-    d_q = compute_ddv(q, x, adv, bits, stages=args.stages)
+    d_fp = compute_ddv(fp, x, adv, None, stages=args.stages, attention=args.attention)
+    d_q = compute_ddv(q, x, adv, bits, stages=args.stages, attention=args.attention)
     sim, ref = similarity(d_fp, d_q), reference_similarity(d_fp, d_q)
     for k in d_fp:
         print('%-24s cosine %+.6f   sign agreement %.2f%%' % (k, sim[k], ref[k]))

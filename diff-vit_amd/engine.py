@@ -83,7 +83,9 @@ class CkaLayer(C.Structure):
 
 
 COS_I8, COS_F32 = 0, 1
+COS_LOG2K = 3                                 # P2V_COS_LOG2K: bytes k of the log2 softmax, the probabilities 2^-k (0 from 16 on)
 DDV_STAGES_ENGINE, DDV_STAGES_FULL = 0, 1     # P2V_DDV_STAGES_*: the stage_set of p2v_forward_ddv_ex
+DDV_STAGES_ATTN = 2                           # or-ed onto either for p2v_forward_ddv_ex2: the QActs inside the attention kernel
 SCORE_MAX_K = 8                                  # P2V_SCORE_MAX_K: values of k per totals slot
 
 
@@ -164,6 +166,13 @@ def lib():
         L.p2v_int_layernorm_tap.argtypes = [_p, _ll, _i, _i, C.POINTER(Ln), _p, _ll, _p, _p]
         L.p2v_gemm_resid_tap.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Linear), C.POINTER(Epilogue), _p, _i, _p, _p]
         L.p2v_gemm_embed_tap.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Linear), C.POINTER(Epilogue), _p, _i, _p, _p, _p]
+    if hasattr(L, 'p2v_forward_ddv_ex2'):         # DDV stages inside attention and the pitched taps of the attention operators, additive
+        L.p2v_ddv_stage_count_ex2.argtypes = [_p, _i, _i]
+        L.p2v_ddv_attn_scratch_bytes.argtypes = [_p, _i]
+        L.p2v_ddv_attn_scratch_bytes.restype = C.c_size_t
+        L.p2v_forward_ddv_ex2.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _i, _p, C.c_size_t, _p, C.c_size_t, _p, _p]
+        L.p2v_lis_attention_taps.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Attn), _p, _p, _p, _i, _p]
+        L.p2v_window_attention_taps.argtypes = [_p, _i, _i, _i, _i, C.POINTER(WinAttn), _p, _p, _p, _p, _i, _p]
     if hasattr(L, 'p2v_cos_stage_descs'):         # recorded DDV stages (P2V_OP_COS / P2V_OP_COS_COMBINE), additive
         L.p2v_cos_stage_desc_bytes.restype = C.c_size_t
         L.p2v_cos_stage_descs.argtypes = [C.POINTER(CosLayer), _i, _i, _p]

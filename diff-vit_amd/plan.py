@@ -419,31 +419,41 @@ class FrozenPlan:
             bufs[0] = bufs[0].view(B, g, g, self.D).permute(0, 3, 1, 2)
         return out, bufs
 
-    def ddv_stage_names(self, with_linear=False, stages='engine'):
+    def ddv_stage_names(self, with_linear=False, stages='engine', attention=False):
         """names of the ``forward_ddv`` stages in module order (``ddv.stage_names``: the oracle's tap names, plus the QLinear outputs)."""
         from .ddv import stage_names
         if stages not in ('engine', 'full'):
             raise ValueError("forward_ddv: stages must be 'engine' or 'full', not %r" % (stages,))
-        return stage_names(self.depth, with_linear, stages == 'full')
+        return stage_names(self.depth, with_linear, stages == 'full', attention)
+
+    def ddv_attn_bytes(self, n):
+        """bytes of the scratch ``forward_ddv(attention=True)`` needs for n pairs: the score-code and the exponent plane of ONE block's
+        attention over the 2n images, rows pitched to whole 16-byte groups (2 * 2n * heads * tokens * round_up(tokens, 16))."""
+        return int(E.lib().p2v_ddv_attn_scratch_bytes(self._handle, n))
 
     def ddv_tap_bytes(self, n):
         """bytes of the one fp32 buffer ``forward_ddv(with_linear=True)`` needs for n pairs: the largest single tap of 2n images."""
         return int(E.lib().p2v_ddv_tap_scratch_bytes(self._handle, n))
 
-    def forward_ddv(self, images_2n, bit_config, with_linear=False, stages='engine'):
+    def forward_ddv(self, images_2n, bit_config, with_linear=False, stages='engine', attention=False):
         """p2v_forward_ddv: ``images_2n`` holds n clean images followed by their n perturbed twins.  Returns (logits [2n, classes],
         stage names, sums): sums is fp64 [stages, n, 3] = (sum a.b, sum a.a, sum b.b) of every stage's activation on image i and on
         image n + i, reduced from the int8 codes between the launches of the ONE forward (``ddv.ddv_from_sums`` turns them into a
         DDV).  The only fp32 activation memory is one tap of 2n images (``ddv_tap_bytes``), and only with ``with_linear``.
         ``stages='full'`` (``P2V_DDV_STAGES_FULL``): also the stages behind the reference's remaining hook points - the stem's codes, the
-        LayerNorm values, the mid codes of proj / fc2 - in the same one call; the tap buffer is then needed either way."""
+        LayerNorm values, the mid codes of proj / fc2 - in the same one call; the tap buffer is then needed either way.
+        ``attention`` (``P2V_DDV_STAGES_ATTN``, with either set): per block also ``attn.qact_attn1`` (the score codes) and
+        ``attn.log_int_softmax`` (the 4-bit log2 probabilities), both exact, from the tapped attention launch through one scratch of
+        ``ddv_attn_bytes(n)`` that the next block reuses."""
         images, cfg = self._check(images_2n, bit_config)
         B = images.shape[0]
         if B % 2:
             raise AssertionError('forward_ddv takes n clean images followed by their n perturbed twins: %d images' % B)
         n = B // 2
         L = E.lib()
-        names = self.ddv_stage_names(with_linear, stages)
+        names = self.ddv_stage_names(with_linear, stages, attention)
+        if attention:
+            return self._forward_ddv_attention(images, cfg, len(bit_config), n, names, with_linear, stages)
         full = stages == 'full'
         stage_set = E.DDV_STAGES_FULL if full else E.DDV_STAGES_ENGINE
         if full and not self.input_quant:
@@ -467,6 +477,32 @@ class FrozenPlan:
             else:
                 E.check(L.p2v_forward_ddv(self._handle, E.ptr(images), n, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(),
                                           int(with_linear), E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(sums),
+                                          E.stream_ptr(self.device)))
+        return out, names, sums
+
+    def _forward_ddv_attention(self, images, cfg, n_cfg, n, names, with_linear, stages):
+        """``forward_ddv(attention=True)``: the one p2v_forward_ddv_ex2 call with the attention scratch"""
+        L = E.lib()
+        full = stages == 'full'
+        if not hasattr(L, 'p2v_forward_ddv_ex2'):
+            raise RuntimeError('forward_ddv(attention=True): libp2vit_hip.so lacks p2v_forward_ddv_ex2: rebuild')
+        if full and not self.input_quant:
+            raise NotImplementedError("forward_ddv(stages='full'): no qact_input stage on an input_quant=False plan")
+        stage_set = (E.DDV_STAGES_FULL if full else E.DDV_STAGES_ENGINE) | E.DDV_STAGES_ATTN
+        assert len(names) == L.p2v_ddv_stage_count_ex2(self._handle, int(with_linear), stage_set)
+        B = images.shape[0]
+        with torch.cuda.device(self.device):
+            nbytes = L.p2v_ddv_workspace_bytes(self._handle, n)
+            if self._ws is None or self._ws.numel() < nbytes:
+                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                self._ws_batch = max(self._ws_batch, B)
+            ws = self._ws
+            out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
+            sums = torch.empty(len(names), n, 3, dtype=torch.float64, device=self.device)
+            tap = torch.empty(self.ddv_tap_bytes(n), dtype=torch.uint8, device=self.device) if (with_linear or full) else None
+            att = torch.empty(self.ddv_attn_bytes(n), dtype=torch.uint8, device=self.device)
+            E.check(L.p2v_forward_ddv_ex2(self._handle, E.ptr(images), n, cfg, n_cfg, E.ptr(out), E.ptr(ws), ws.numel(), int(with_linear), stage_set,
+                                          E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(att), att.numel(), E.ptr(sums),
                                           E.stream_ptr(self.device)))
         return out, names, sums
 

@@ -210,7 +210,7 @@ class SwinPlan:
         return e
 
     # ---- forward -------------------------------------------------------------------------------------------------------
-    def _record(self, B, fused=True, ddv_n=0, with_linear=False, lin_taps=False):
+    def _record(self, B, fused=True, ddv_n=0, with_linear=False, lin_taps=False, attention=False):
         """the launch sequence of one forward at batch B as a ``p2v_op`` array with its own activation buffers (built once
         per batch size and stream slot, replayed by ``p2v_run_ops``).  ``fused``: norm1 + qkv and norm2 + fc1 of stages up to 384
         channels run as ONE launch each (``P2V_OP_LN_GEMM``: the LayerNorm output stays in LDS); the tap replay records the
@@ -218,7 +218,10 @@ class SwinPlan:
         ``ddv_n`` > 0 (B = 2 * ddv_n, unfused): behind the launch that completes a DDV stage a ``P2V_OP_COS`` record reduces samples
         [0, n) of the live buffer against samples [n, 2n); proj / fc2 also store their mid codes (attn.qact4 / mlp.qact2); ``with_linear``
         adds the fp32 layer outputs through ONE scratch buffer; a ``P2V_OP_COS_COMBINE`` closes the sequence.
-        ``lin_taps`` (unfused): the fp32 output of every QConv2d / QLinear into a buffer of its own (``forward_linear_taps``)."""
+        ``lin_taps`` (unfused): the fp32 output of every QConv2d / QLinear into a buffer of its own (``forward_linear_taps``).
+        ``attention`` (with ``ddv_n``): the window launches run tapped (the planes of ``p2v_window_attention_taps``, named in the WINATTN
+        record) into three planes per stage that its blocks share - qact_attn1, qact2 (int8 codes) and the softmax exponents
+        (``P2V_COS_LOG2K``) - each reduced right behind the launch."""
         a = self.arch
         P, g = a['patch_size'], self.g
         dev = self.device
@@ -236,7 +239,7 @@ class SwinPlan:
             """DDV stage ``name``: per image rows x cols elements of ``t_`` (row stride ``stride`` elements: padding behind ``cols`` is never read)"""
             if not n:
                 return
-            esz = 1 if dtype == E.COS_I8 else 4
+            esz = 4 if dtype == E.COS_F32 else 1
             lay = E.CosLayer(E.ptr(t_), C.c_void_p(t_.data_ptr() + n * rows * stride * esz), scale, rows * stride, stride, rows, cols, dtype)
             o = E.Op()
             o.kind, o.inp = E.OP_COS, E.ptr(t_)
@@ -346,6 +349,10 @@ class SwinPlan:
             fc1_n, hid_k = stg['blocks'][0]['fc1']['N'], stg['blocks'][0]['fc2']['K']
             hid = buf(rows, hid_k, zero=hid_k != fc1_n)
             mid = buf(rows, Cc) if n else None
+            wb = stg['blocks'][0]
+            Nw, nW = wb['ws'] * wb['ws'], wb['wa'].n_windows
+            pitch = (Nw + 15) // 16 * 16
+            planes = [buf(B * nW * wb['heads'] * Nw, pitch) for _ in range(3)] if (n and attention) else None
             for bi, b in enumerate(stg['blocks']):
                 p = 'layers.%d.blocks.%d.' % (li, bi)
                 t_qkv, t_fc1 = ftap(p + 'attn.qkv', rows, b['qkv']['N']), None
@@ -367,7 +374,13 @@ class SwinPlan:
                 o.i0, o.i1, o.i2, o.i3 = B, T, b['heads'], 32
                 o.wa = b['wa']
                 o.wa.out_stride = att.shape[1]
+                if planes is not None:       # the tapped launch (op table of include/p2vit.h: members the record did not use before)
+                    o.lin.w_codes, o.lin.w_frag, o.ep.tap_out, o.ldo = E.ptr(planes[0]), E.ptr(planes[1]), E.ptr(planes[2]), pitch
                 ops.append(o)
+                if planes is not None:
+                    stage(p + 'attn.qact_attn1', planes[0], nW * b['heads'] * Nw, Nw, pitch)
+                    stage(p + 'attn.qact2', planes[1], nW * b['heads'] * Nw, Nw, pitch)
+                    stage(p + 'attn.log_int_softmax', planes[2], nW * b['heads'] * Nw, Nw, pitch, E.COS_LOG2K)
                 stage(p + 'attn.qact3', att, T, Cc, att.shape[1])       # (the out_stride padding of att is never written: cols = Cc)
                 gemm_f32(p + 'attn.proj', att, b['proj'], T)
                 gemm(E.EPI_RESID, att, b['proj'], epi_res(b['proj_epi'], x, mid), x2)
@@ -495,18 +508,21 @@ class SwinPlan:
             E.check(E.lib().p2v_run_ops(r['ops'], r['n'], E.stream_ptr(self.device)))
             return r, out
 
-    def forward_ddv(self, images_2n, with_linear=True):
+    def forward_ddv(self, images_2n, with_linear=True, attention=False):
         """The DDV of the quantized model inside the forward: ``images_2n`` = n clean images followed by their n perturbed twins.
         Returns (logits [2n, classes], byte-equal to ``forward``; stage names = ``ddv.swin_stage_names(depths, with_linear)``; sums fp64
         [stages, n, 3] = sum a.b, sum a.a, sum b.b per stage and pair).  One recorded sequence, one ``p2v_run_ops`` call on the current
         stream: every stage is reduced from the live buffer right behind the launch that completes it (the LayerNorm outputs exist in HBM
         because the unfused sequence is recorded; attn.qact4 / mlp.qact2 come from the mid-code output of the RESID epilogue), one combine
-        launch closes it.  The QActs inside the window kernel (qact_attn1, qact2, qact_table, the softmax) are not stages."""
+        launch closes it.  ``attention``: also the QActs inside the window kernel - attn.qact_attn1, attn.qact2 (codes) and
+        attn.log_int_softmax (the 4-bit log2 probabilities), exact sums from the tapped window launch; stage names =
+        ``ddv.swin_stage_names(depths, with_linear, attention=True)``.  qact_table does not depend on the input and is not a stage."""
         images_2n = self._check_images(images_2n)
         if images_2n.shape[0] < 2 or images_2n.shape[0] % 2:
             raise AssertionError('forward_ddv takes n clean images followed by their n perturbed twins, got %d images' % images_2n.shape[0])
         n = images_2n.shape[0] // 2
-        r, _ = self._replay_extra(images_2n, ('ddv', n, bool(with_linear)), ddv_n=n, with_linear=bool(with_linear))
+        key = ('ddv', n, bool(with_linear)) + (('attn',) if attention else ())
+        r, _ = self._replay_extra(images_2n, key, ddv_n=n, with_linear=bool(with_linear), attention=bool(attention))
         return r['logits'][:, :self.head['N']].clone(), list(r['names']), r['sums'].clone()
 
     def forward_linear_taps(self, images):

@@ -34,7 +34,8 @@
  *           of the last block leaves stale are not read);
  *       (2) a forward writes nothing outside [workspace, workspace + p2v_workspace_bytes) - p2v_ddv_workspace_bytes for p2v_forward_ddv / _ex -
  *           and outside its dense outputs (logits [batch][classes], each tap at its stated extent, sums, tap_scratch up to
- *           p2v_ddv_tap_scratch_bytes).  Inside the workspace the alignment gaps between the seven buffers and the trailing 256 bytes are
+ *           p2v_ddv_tap_scratch_bytes, attn_scratch of p2v_forward_ddv_ex2 up to p2v_ddv_attn_scratch_bytes - and of its rows only the
+ *           columns [0, tokens)).  Inside the workspace the alignment gaps between the seven buffers and the trailing 256 bytes are
  *           never written.  Each launch of a stop_after >= 0 run, where the last block computes every row, writes exactly the
  *           rows x cols extent of its target buffer(s) (p2v_workspace_view).  The class-row launches of a stop_after = -1 run write less
  *           ("cls_rows": `batch` compact rows of ln / hid, the class rows of x / att); for them the statement is the weaker one that
@@ -463,6 +464,18 @@ int p2v_lis_attention(const int8_t* qkv, int batch, int tokens, int heads, int h
 int p2v_lis_attention_rows(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int query_rows,
                            int8_t* out, void* stream);
 
+/* Additive (found by its symbol): p2v_lis_attention with the two QActs inside the kernel as PITCHED planes, each optional (NULL):
+ *   score_codes   the qact_attn1 codes of every real (query, key) pair, int8
+ *   probs_k       the log2 softmax exponents (16 = zero), the values of p2v_lis_attention's probs_k
+ * both dev int8 [batch][heads][tokens][pitch], 16-byte aligned, pitch >= tokens and a multiple of 16 (rows and images start 16-byte aligned,
+ * what p2v_pair_cosine asks for).  Written: columns [0, tokens) of every row; the columns [tokens, pitch) keep the caller's bytes.  The
+ * codes are taken from the registers that feed the softmax (the resident kernel: row maximum minus the table offset of the slot), no score
+ * is computed twice.  `out` is byte-identical to p2v_lis_attention's.  Same checks as p2v_lis_attention; a tapped launch beyond the resident
+ * kernel's token count runs the streaming kernel (p2v_attention_kernel(head_dim, tokens, 1)).  P2V_E_ARG: pitch < tokens, pitch % 16, a
+ * misaligned plane - only when a plane is given; with both NULL the call is p2v_lis_attention(..., probs_k = NULL). */
+int p2v_lis_attention_taps(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int8_t* out,
+                           int8_t* score_codes, int8_t* probs_k, int pitch, void* stream);
+
 /* Swin window attention core (WindowAttention.forward between qact1 and qact3, swin_quant.py:186-217; window partition /
  * cyclic shift / reverse of SwinTransformerBlock.forward, swin_quant.py:366-391, folded into the addressing):
  *   (q*scale) @ k^T -> qact_attn1 -> + qact_table(relative_position_bias_table)[index] -> qact2 -> (+ -100 mask) ->
@@ -494,6 +507,15 @@ typedef struct p2v_winattn {
 int p2v_window_attention(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim,
                          const p2v_winattn* wa, int8_t* out, int8_t* probs_k, void* stream);
 
+/* Additive (found by its symbol): p2v_window_attention with the three QActs inside the kernel as PITCHED planes, each optional (NULL):
+ *   attn1_codes   qact_attn1 codes            qact2_codes   qact2 codes (behind the bias-table add, in front of the -100 mask)
+ *   probs_k       log2 softmax exponents (16 = zero), the values of p2v_window_attention's probs_k
+ * dev int8 [batch][n_windows][heads][N][pitch], N = ws * ws, 16-byte aligned, pitch >= N and a multiple of 16.  Written: columns [0, N) of
+ * every row, nothing else.  `out` is byte-identical to p2v_window_attention's; same checks, both kernels (windows up to 8 x 8 and 9 x 9 ...
+ * 12 x 12).  P2V_E_ARG for a bad pitch or a misaligned plane when a plane is given. */
+int p2v_window_attention_taps(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                              int8_t* out, int8_t* attn1_codes, int8_t* qact2_codes, int8_t* probs_k, int pitch, void* stream);
+
 /* PatchMerging.forward gather (swin_quant.py:446-459): x int8 [batch][H*W][C] -> out int8 [batch][(H/2)*(W/2)][4*C] in the
  * reference's channel order x0 (even row, even col), x1 (odd row, even col), x2 (even row, odd col), x3 (odd, odd). */
 int p2v_patch_merge_gather(const int8_t* x, int batch, int H, int W, int C, int8_t* out, void* stream);
@@ -523,7 +545,11 @@ int p2v_avgpool_quant(const int8_t* x, int batch, int tokens, int C, float s_in,
  *   P2V_OP_COS_COMBINE  closes the stages of a sequence: in the device table, i1 its stages (>= 1), i0 n, lin.w_codes the partial slots,
  *                     out sums fp64 [stages][n][3].  One launch
  *   P2V_OP_GEMM_F32   in (A), out fp32 [M][ldo] = fmaf(acc, colscale, bias), columns [0, N) only: M, K, N, lda, ldo (N: dense, or a multiple
- *                     of 4 beyond it); lin; in and out 16-byte aligned.  (The public p2v_gemm_i8 refuses this epilogue.) */
+ *                     of 4 beyond it); lin; in and out 16-byte aligned.  (The public p2v_gemm_i8 refuses this epilogue.)
+ *   P2V_OP_WINATTN    optionally names the planes of p2v_window_attention_taps in members the kind did not read before (all NULL / 0 in
+ *                     an earlier record: the untapped launch): lin.w_codes the qact_attn1 plane, lin.w_frag the qact2 plane, ep.tap_out the
+ *                     exponent plane (all three written as int8_t*), ldo the pitch
+ *   P2V_OP_COS        i1 may be P2V_COS_LOG2K (the exponent plane; lin.colscale must be NULL) */
 enum { P2V_OP_PATCHIFY = 0, P2V_OP_GEMM = 1, P2V_OP_LAYERNORM = 2, P2V_OP_WINATTN = 3, P2V_OP_MERGE = 4, P2V_OP_AVGPOOL = 5, P2V_OP_LN_GEMM = 6,
        P2V_OP_COS = 7, P2V_OP_COS_COMBINE = 8, P2V_OP_GEMM_F32 = 9 };
 typedef struct p2v_op {
@@ -610,7 +636,14 @@ int p2v_hsic_accumulate(const float* g1, int l1, const float* g2, int l2, int n,
  * row r at + r * row_stride (both in ELEMENTS); int8 codes or fp32 values.  `scale` (int8 only): per-channel fp32 [cols], the value of an
  * element is scale[c] * code - the PTF scales of the residual stream; NULL: one scale for the tensor, which a cosine does not see.
  * Pointers and strides (in bytes) must be multiples of 16: P2V_E_ARG otherwise. */
-enum { P2V_COS_I8 = 0, P2V_COS_F32 = 1 };
+/* (additive) P2V_COS_LOG2K: int8 bytes k that stand for the probabilities of the 4-bit log2 softmax, 2^-k for 0 <= k <= 15 and 0 from 16 on
+ * (read as unsigned bytes).  The sums are exact integers: every value is 2^(15-k) units of 2^-15, a product at most 2^30, accumulated in
+ * int64 through the same tree and splits as P2V_COS_I8, converted once and scaled by 2^-30.  That is exact in fp64 while the integer stays
+ * below 2^53: a softmax row's probabilities sum to about 1 (each is at most 1.5 times its exact quotient and at most 1), so sum p^2 <= sum p
+ * <= ~1.5 per row and a sample of `rows` rows gives at most ~1.5 * rows * 2^30 - below 2^53 for rows < 2^22, which every plan geometry meets
+ * (ViT: rows = heads * tokens <= 64 * 4096 = 2^18; Swin: rows = heads * tokens of the image).  For arbitrary bytes the bound is rows * cols <= 2^23; beyond it the one
+ * conversion rounds (rows * cols < 2^33 is refused).  scale must be NULL (P2V_E_ARG otherwise). */
+enum { P2V_COS_I8 = 0, P2V_COS_F32 = 1, P2V_COS_LOG2K = 3 };      /* (2 is not an element type: it stays refused, as before) */
 typedef struct p2v_cos_layer {
   const void* a;       /* dev, n samples */
   const void* b;       /* dev, n samples */
@@ -764,6 +797,25 @@ int p2v_profile_candidates(const float* inputs, int n, long long image_elems, in
 int p2v_profile_step(void* state, size_t state_bytes, int n, int classes, const float* cand1, const float* cand2, const float* staging,
                      float* inputs, long long image_elems, int idx, long long pos, double* trace_row, void* stream);
 int p2v_profile_diversity(const float* logits, long long ld, int n, int classes, double* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- DDV stages inside attention (additive: no structure, existing entry point or P2V_ABI_VERSION changes; found by their symbols) ------
+ * P2V_DDV_STAGES_ATTN, or-ed onto P2V_DDV_STAGES_ENGINE or P2V_DDV_STAGES_FULL in the three functions below (the _ex functions keep refusing
+ * it), adds per block, in module order between attn.qact1 and attn.qact2,
+ *   blocks.i.attn.qact_attn1         the int8 score codes of every (query, key) pair           exact integer sums (P2V_COS_I8)
+ *   blocks.i.attn.log_int_softmax    the output of QIntSoftmax, probabilities 0 and 2^-k        exact (P2V_COS_LOG2K)
+ * = 2 * depth more stages.  The attention launch of a block runs its tapped form (p2v_lis_attention_taps) into attn_scratch - the two planes
+ * of the 2n images of ONE block, [2][2n][heads][tokens][pitch] with pitch = round_up(tokens, 16): p2v_ddv_attn_scratch_bytes(plan, n) =
+ * 2 * 2n * heads * tokens * pitch bytes - which is reduced right behind the launch and reused by the next block, like tap_scratch.  Only the
+ * columns [0, tokens) of a row are written and read: the result does not depend on what the scratch held, nothing outside its dense extent is
+ * written.  Without the flag p2v_forward_ddv_ex2 is p2v_forward_ddv_ex, launch for launch (attn_scratch is ignored); with it the logits and
+ * the sums of every other stage are byte-identical.  Refused before any launch: the flag with a NULL or misaligned (16 bytes) attn_scratch
+ * (P2V_E_ARG) or a short one (P2V_E_WORKSPACE); everything p2v_forward_ddv_ex refuses. */
+enum { P2V_DDV_STAGES_ATTN = 2 };
+int p2v_ddv_stage_count_ex2(const p2v_plan* plan, int with_linear, int stage_set);
+size_t p2v_ddv_attn_scratch_bytes(const p2v_plan* plan, int n);       /* 0: null plan, n outside 1 .. 2^29 */
+int p2v_forward_ddv_ex2(p2v_plan* plan, const float* images, int n, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                        size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, int8_t* attn_scratch,
+                        size_t attn_scratch_bytes, double* sums, void* stream);
 
 const char* p2v_last_error(void);
 int p2v_abi_version(void);

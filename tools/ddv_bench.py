@@ -23,7 +23,11 @@ per model.
        ddv_linear_ms              forward_ddv(with_linear=True): + every linear output through ONE fp32 scratch buffer
        taps_torch_ms              the alternative it replaces: forward(taps=...) (segmented replay, every tap cloned) +
                                   torch.ops.p2vit.pair_cosine on the cloned taps
-       resid_tap                  the last stage's fc2 (RESID) launch alone, without and with the mid-code output, median of 10 x 20 launches"""
+       resid_tap                  the last stage's fc2 (RESID) launch alone, without and with the mid-code output, median of 10 x 20 launches
+
+    python tools/ddv_bench.py --attention [--models deit_small] [--swin swin_tiny] [--n 50] [--reps 10]
+       the cost of the stages inside attention: forward_ddv(with_linear=False) without and with attention=True, ALTERNATING in one
+       process (three rounds of median-of-reps each), the stage counts and the bytes of the attention scratch"""
 import argparse
 import json
 import os
@@ -160,6 +164,48 @@ def run_swin(name, n, reps):
                           'plain_us': round(t_plain * 1e3, 2), 'tapped_us': round(t_tap * 1e3, 2)}}
 
 
+def run_attention(name, n, reps, swin):
+    """forward_ddv without / with the stages inside attention, alternating; ViT / DeiT from the golden calibration, Swin calibrated on two images"""
+    if swin:
+        import contextlib
+        with contextlib.redirect_stdout(sys.stderr):
+            model = dva.harness.str2model(name)(cfg=dva.Config(True, True, 'minmax'))
+        model.load_state_dict(dva.synth.swin_state_dict(model.state_dict(), 0))
+        model = model.cuda().eval()
+        img = model.arch['img_size']
+        with torch.no_grad():
+            dva.harness.calibrate_model(model, dva.synth.images(0, 2, img).cuda())
+        plan = model.freeze(torch.device('cuda:0'), bits=8)
+        x = dva.synth.images(1, 2 * n, img).cuda()
+        fwd = lambda: plan.forward(x, n_streams=1)
+        off, on = (lambda: plan.forward_ddv(x, False)), (lambda: plan.forward_ddv(x, False, attention=True))
+        depths = model.arch['depths']
+        stages = (len(dva.ddv.swin_stage_names(depths, False)), len(dva.ddv.swin_stage_names(depths, False, True)))
+        scratch = 0
+        for st_ in plan.stages:      # three planes per stage, shared by its blocks
+            b = st_['blocks'][0]
+            N = b['ws'] * b['ws']
+            scratch += 3 * 2 * n * b['wa'].n_windows * b['heads'] * N * ((N + 15) // 16 * 16)
+    else:
+        g = np.load(os.path.join(ROOT, 'tests', 'golden', name + '.npz'))
+        arch = dva.synth.ARCHS[name]
+        calib = O.unflatten_calib({k[len('calib/'):]: torch.from_numpy(g[k]) for k in g.files if k.startswith('calib/')})
+        plan = dva.FrozenPlan(arch, dva.synth.vit_state_dict(arch, int(g['seed'])), calib, device=torch.device('cuda:0'))
+        bits = [8] * (4 * arch['depth'] + 2)
+        x = dva.synth.images(1, 2 * n, 224).cuda()
+        fwd = lambda: plan.forward(x, bits)
+        off, on = (lambda: plan.forward_ddv(x, bits, False)), (lambda: plan.forward_ddv(x, bits, False, attention=True))
+        stages = (len(dva.ddv.stage_names(arch['depth'], False)), len(dva.ddv.stage_names(arch['depth'], False, False, True)))
+        scratch = plan.ddv_attn_bytes(n)
+    t_fwd = timed(fwd, reps)
+    rounds = [(timed(off, reps), timed(on, reps)) for _ in range(3)]
+    t_off, t_on = float(np.median([r[0] for r in rounds])), float(np.median([r[1] for r in rounds]))
+    return {'model': name, 'n': n, 'images': 2 * n, 'forward_ms': round(t_fwd, 3), 'stages': {'without': stages[0], 'with_attention': stages[1]},
+            'rounds_ms': [[round(a_, 3), round(b_, 3)] for a_, b_ in rounds], 'ddv_int8_ms': round(t_off, 3), 'ddv_int8_attention_ms': round(t_on, 3),
+            'attention_over_plain': round(t_on / t_off, 3), 'us_per_added_stage': round((t_on - t_off) * 1e3 / (stages[1] - stages[0]), 2),
+            'attention_scratch_MB': round(scratch / 1e6, 1)}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--n', type=int, default=50)
@@ -167,7 +213,14 @@ def main():
     p.add_argument('--models', default='deit_small,vit_base')
     p.add_argument('--stages', default='engine', choices=['engine', 'full'], help='full: also time forward_ddv(stages="full") (ViT / DeiT)')
     p.add_argument('--swin', default=None, help='a Swin factory name of harness.str2model (swin_base): the Swin lines instead')
+    p.add_argument('--attention', action='store_true', help='the cost of the stages inside attention (see the module docstring)')
     a = p.parse_args()
+    if a.attention:
+        for m in ([] if a.models == 'deit_small,vit_base' and a.swin else a.models.split(',')):
+            print(json.dumps(run_attention(m, a.n, a.reps, False)), flush=True)
+        if a.swin:
+            print(json.dumps(run_attention(a.swin, a.n, a.reps, True)), flush=True)
+        return
     if a.swin:
         print(json.dumps(run_swin(a.swin, a.n, a.reps)), flush=True)
         return
