@@ -1015,6 +1015,27 @@ int p2v_ln_prefold(p2v_ln* ln, int C, float* buf, size_t buf_bytes) {
   return P2V_OK;
 }
 
+size_t p2v_freeze_bytes(int N, int K, int layout) {
+  if (N < 1 || K < 1 || K > (1 << 30) || layout < P2V_W_ROWS_I8 || layout > P2V_W_FRAG_P4) return 0;
+  const size_t codes = ((size_t)N + 127) / 128 * 128 * (size_t)round_up(K, GBK_PAD);
+  return layout == P2V_W_TILES_P4 || layout == P2V_W_FRAG_P4 ? codes / 2 : codes;
+}
+
+int p2v_freeze_weights(const float* w, long long ldw, int N, int K, const float* scale, int n_scale, int bits, int layout, void* out,
+                       size_t out_bytes, void* stream) {
+  if (!w || !scale || !out) return fail(P2V_E_ARG, "p2v_freeze_weights: null argument");
+  if ((uintptr_t)w % 4 || (uintptr_t)scale % 4 || (uintptr_t)out % 16) return fail(P2V_E_ARG, "p2v_freeze_weights: w / scale must be 4-byte, out 16-byte aligned");
+  if (N < 1 || K < 1 || K > (1 << 30) || ldw < K) return fail(P2V_E_SHAPE, "p2v_freeze_weights: N=%d K=%d ldw=%lld", N, K, ldw);
+  if (n_scale != 1 && n_scale != N) return fail(P2V_E_SHAPE, "p2v_freeze_weights: %d scales for %d rows (1 or N)", n_scale, N);
+  if (layout < P2V_W_ROWS_I8 || layout > P2V_W_FRAG_P4) return fail(P2V_E_SHAPE, "p2v_freeze_weights: unknown layout %d", layout);
+  if (bits != 4 && bits != 8) return fail(P2V_E_BITS, "p2v_freeze_weights: %d-bit codes (4 or 8)", bits);
+  if (bits == 8 && (layout == P2V_W_TILES_P4 || layout == P2V_W_FRAG_P4)) return fail(P2V_E_BITS, "p2v_freeze_weights: the packed layouts hold 4-bit codes");
+  const size_t need = p2v_freeze_bytes(N, K, layout);
+  if (out_bytes < need) return fail(P2V_E_WORKSPACE, "p2v_freeze_weights: out %zu < %zu bytes", out_bytes, need);
+  if (need >= ((size_t)1 << 41)) return fail(P2V_E_SHAPE, "p2v_freeze_weights: %zu output bytes pass the grid of one launch", need);
+  return launch_rc(p2v_launch_freeze_weights(w, ldw, N, K, scale, n_scale, bits, layout, out, (hipStream_t)stream), "freeze_weights");
+}
+
 size_t p2v_resid_prefold_bytes(int N) { return N > 0 ? resid_tab_floats(N) * sizeof(float) : 0; }
 
 int p2v_resid_prefold(const p2v_linear* lin, const p2v_epilogue* epi, int N, float* tab, size_t tab_bytes, int* usable, void* stream) {

@@ -190,3 +190,7 @@ int p2v_launch_profile_candidates(const float* inputs, long long elems, int idx,
 int p2v_launch_profile_step(void* state, int n, int classes, const float* cand1, const float* cand2, const float* staging, float* inputs,
                             long long elems, int idx, long long pos, double* trace, hipStream_t st);
 int p2v_launch_profile_diversity(const float* logits, long long ld, int n, int classes, double* ws, double* out, hipStream_t st);
+
+// weight freeze (p2vit_freeze.hip): one streaming launch, every argument checked by p2v_freeze_weights
+int p2v_launch_freeze_weights(const float* w, long long ldw, int N, int K, const float* scale, int n_scale, int bits, int layout, void* out,
+                              hipStream_t st);

@@ -87,6 +87,7 @@ COS_LOG2K = 3                                 # P2V_COS_LOG2K: bytes k of the lo
 DDV_STAGES_ENGINE, DDV_STAGES_FULL = 0, 1     # P2V_DDV_STAGES_*: the stage_set of p2v_forward_ddv_ex
 DDV_STAGES_ATTN = 2                           # or-ed onto either for p2v_forward_ddv_ex2: the QActs inside the attention kernel
 SCORE_MAX_K = 8                                  # P2V_SCORE_MAX_K: values of k per totals slot
+W_ROWS_I8, W_FRAG_I8, W_TILES_P4, W_FRAG_P4 = range(4)      # P2V_W_*: the layouts of p2v_freeze_weights
 
 
 class CosLayer(C.Structure):
@@ -189,6 +190,10 @@ def lib():
         L.p2v_profile_candidates.argtypes = [_p, _i, _ll, _i, _ll, _f, _p, _p]
         L.p2v_profile_step.argtypes = [_p, C.c_size_t, _i, _i, _p, _p, _p, _p, _ll, _i, _ll, _p, _p]
         L.p2v_profile_diversity.argtypes = [_p, _ll, _i, _i, _p, _p, C.c_size_t, _p]
+    if hasattr(L, 'p2v_freeze_weights'):          # the weight freeze is additive, found by its symbols
+        L.p2v_freeze_bytes.argtypes = [_i, _i, _i]
+        L.p2v_freeze_bytes.restype = C.c_size_t
+        L.p2v_freeze_weights.argtypes = [_p, _ll, _i, _i, _p, _i, _i, _i, _p, C.c_size_t, _p]
     L.p2v_forward_profile.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_int32), _i]
     L.p2v_forward_profile_begin.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(_p)]
@@ -307,6 +312,30 @@ def pack_int4_tiles(wp):
     src = torch.arange(4).reshape(1, 4) ^ ((rows >> 3) & 3).reshape(128, 1)                      # position c' holds chunk c' ^ f(row)
     b = torch.gather(b, 3, src.reshape(1, 128, 1, 4, 1).expand(b.shape[0], 128, b.shape[2], 4, 8))
     return b.permute(0, 2, 1, 3, 4).reshape(n_pad // 128, k_pad // 64, 128, 32).contiguous()
+
+
+def freeze_weights(w, scale, bits, layout):
+    """``p2v_freeze_weights`` on the current stream: fp32 weights ``w`` [N, K] (any row stride) and their scales (1 or N values), both
+    on the GPU -> the codes of width ``bits`` in ``layout`` (W_ROWS_I8 / W_FRAG_I8 / W_TILES_P4 / W_FRAG_P4) as a device tensor
+    shaped like the host function of that layout makes it (the padded rows / :func:`fragment_order` / :func:`pack_int4_tiles` /
+    :func:`fragment_order_packed4`).  One launch, no synchronisation."""
+    import torch
+    if w.dim() != 2 or w.dtype != torch.float32 or scale.dtype != torch.float32 or not w.is_cuda or scale.device != w.device:
+        raise AssertionError('freeze_weights takes fp32 weights [N, K] and fp32 scales on one GPU')
+    if w.stride(1) != 1:
+        w = w.contiguous()
+    scale = scale.reshape(-1).contiguous()
+    N, K = w.shape
+    n_pad, k_pad = (N + 127) // 128 * 128, (K + 63) // 64 * 64
+    shape, dtype = {W_ROWS_I8: ((n_pad, k_pad), torch.int8), W_FRAG_I8: ((n_pad // 128, 4, k_pad // 32, 2, 32, 16), torch.int8),
+                    W_TILES_P4: ((n_pad // 128, k_pad // 64, 128, 32), torch.uint8),
+                    W_FRAG_P4: ((n_pad // 128, 4, k_pad // 32, 2, 32, 8), torch.uint8)}.get(layout, ((16,), torch.int8))
+    L = lib()
+    with torch.cuda.device(w.device):
+        out = torch.empty(shape, dtype=dtype, device=w.device)
+        check(L.p2v_freeze_weights(ptr(w), w.stride(0), N, K, ptr(scale), scale.numel(), int(bits), int(layout), ptr(out), out.numel(),
+                                   stream_ptr(w.device)))
+    return out
 
 
 def ptr(t):

@@ -83,13 +83,15 @@ def _is_swin(model):
 
 def _forward(model, data, bit_config=None, stats=None):
     """``model(data, bit_config, plot)`` -> (output, FLOPs, distance).  The reference's Swin returns the logits alone and takes
-    no bit_config (swin_quant.py:813-817): a uniform bit_config selects its weight width, FLOPs/distance stay empty.
+    no bit_config (swin_quant.py:813-817); here a list of ``bit_config_length()`` entries gives every layer its width (a one-entry
+    list keeps meaning "uniform"), FLOPs = ``layer_macs()`` and distance = the model's ``global_distance`` (filled by a calibration
+    forward), both in bit-list order.
     ``stats`` = (mean, std): ``data`` is a uint8 NHWC batch for ``forward_uint8``."""
     if _is_swin(model):
-        bits = int(bit_config[0]) if bit_config else 8
+        bits = 8 if not bit_config else (int(bit_config[0]) if len(bit_config) == 1 else [int(b) for b in bit_config])
         if stats is not None:
-            return model.forward_uint8(data, bits, stats[0], stats[1], 'NHWC'), [], []
-        return model(data, bits=bits), [], []
+            return model.forward_uint8(data, bits, stats[0], stats[1], 'NHWC'), model.layer_macs(), model.global_distance
+        return model(data, bits=bits), model.layer_macs(), model.global_distance
     if stats is not None:
         return model.forward_uint8(data, bit_config, stats[0], stats[1], 'NHWC')
     return model(data, bit_config, False)
@@ -389,7 +391,7 @@ def main(argv=None):
             print('Calibrating with Gaussian noise...')
             calib_data = synth.images(args.seed + 1, args.calib_batchsize, arch['img_size']).to(device)
         _, FLOPs, global_distance = calibrate_model(model, calib_data, where=args.calib_on)
-        if args.mixed and not _is_swin(model):
+        if args.mixed:
             # test_quant.py:253-408 on the fast path: every candidate bit_config is one validate() over the HIP engine (the frozen
             # plan holds both weight widths per layer, so switching configurations costs nothing)
             from .search import mixed_precision_search
@@ -401,9 +403,10 @@ def main(argv=None):
             score_many = None
             if args.device_metrics:
                 score_many = lambda cfgs: [r[1] for r in validate_many(quiet, loader, model, device, cfgs)]
+            # Swin: the candidates tie {qkv, proj} and {fc1, fc2} of a block and keep the convolution at 8 bits (search_ties)
             ranked, pop = mixed_precision_search(score, FLOPs, global_distance, seed=args.seed, pop_size=args.search_pop,
                                                  evo_iter=args.search_iter, max_configs=args.search_max_configs, slack=args.search_slack,
-                                                 score_many=score_many)
+                                                 score_many=score_many, ties=model.search_ties() if _is_swin(model) else None)
             print('best mixed-precision configuration: Prec@1 %.3f' % pop[0][1])
             print(pop[0][0])
             return validate(args, loader, model, criterion, device, pop[0][0], device_metrics=args.device_metrics) + (pop[0][0],)

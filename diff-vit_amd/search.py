@@ -21,14 +21,28 @@ def model_size(FLOPs, bit_config):
     return sum(FLOPs[i] * bit_config[i] for i in range(len(FLOPs)))
 
 
-def pareto_candidates(FLOPs, n_layers_gd, rng, bit_choice=(4, 8), max_configs=50, slack=1.1):
-    """test_quant.py:262-284"""
+def pareto_candidates(FLOPs, n_layers_gd, rng, bit_choice=(4, 8), max_configs=50, slack=1.1, ties=None):
+    """test_quant.py:262-284.  ``ties`` None: the reference's walk (the conv at the widest choice, the layers behind it tied in pairs, the
+    head alone).  Otherwise a list of index groups: each group draws ONE bit, the groups in ascending order of their first index, and an
+    index in no group stays at 8 (Swin: ``SwinTransformer.search_ties``)."""
     bit_choice = list(bit_choice)
     constraint = slack * sum(FLOPs[i] * 4 for i in range(len(FLOPs)))
     bit_list = []
+    if ties is not None:
+        ties = sorted((sorted(g) for g in ties), key=lambda g: g[:1])
+        seen = [i for g in ties for i in g]
+        if not all(ties) or len(set(seen)) != len(seen) or min(seen, default=0) < 0 or max(seen, default=0) >= len(FLOPs):
+            raise ValueError('ties must be disjoint, non-empty groups of layer indices below %d' % len(FLOPs))
     for _ in range(2 ** min(n_layers_gd, 24)):
-        cfg = [rng.choice(bit_choice) for _ in range(len(FLOPs) // 2 - 1)]
-        new = [max(bit_choice)] + [b for b in cfg for _ in range(2)] + [rng.choice(bit_choice)]
+        if ties is None:
+            cfg = [rng.choice(bit_choice) for _ in range(len(FLOPs) // 2 - 1)]
+            new = [max(bit_choice)] + [b for b in cfg for _ in range(2)] + [rng.choice(bit_choice)]
+        else:
+            new = [8] * len(FLOPs)
+            for g in ties:
+                b = rng.choice(bit_choice)
+                for i in g:
+                    new[i] = b
         if not model_size(FLOPs, new) > constraint and new not in bit_list:
             bit_list.append(new)
         if len(bit_list) > max_configs:
@@ -125,9 +139,9 @@ def evolutionary_search(score_fn, omega_list, FLOPs, constraint, rng, bit_choice
     return parent
 
 
-def mixed_precision_search(score_fn, FLOPs, global_distance, mean_hessian=None, seed=0, log=print, score_many=None, **kw):
+def mixed_precision_search(score_fn, FLOPs, global_distance, mean_hessian=None, seed=0, log=print, score_many=None, ties=None, **kw):
     """the whole block test_quant.py:253-408; returns (pareto-ranked list, final population).  ``score_many``: see
-    ``evolutionary_search``; the top-5 validation is one call of it as well."""
+    ``evolutionary_search``; the top-5 validation is one call of it as well.  ``ties``: see ``pareto_candidates``."""
     assert len(FLOPs) - 1 == len(global_distance)
     if mean_hessian is None:
         mean_hessian = [1.0] * len(global_distance)
@@ -135,7 +149,7 @@ def mixed_precision_search(score_fn, FLOPs, global_distance, mean_hessian=None, 
     rng = random.Random(seed)
     log('Pareto Frontier.......')
     pk = {k: v for k, v in kw.items() if k in ('max_configs', 'slack')}
-    bit_list, constraint = pareto_candidates(FLOPs, len(global_distance), rng, **pk)
+    bit_list, constraint = pareto_candidates(FLOPs, len(global_distance), rng, ties=ties, **pk)
     ranked = omega_rank(bit_list, global_distance, mean_hessian)
     log('Hessien-Based Validating...')
     for i in range(min(5, len(ranked))):

@@ -21,6 +21,18 @@ __all__ = ['SwinTransformer', 'swin_micro_patch4_window7_56', 'swin_tiny_patch4_
            'swin_base_patch4_window7_224']
 
 
+def check_bit_list(cfg, n):
+    """the ViT surface's convention for a per-layer width list: ValueError for a wrong length or an entry outside {4, 8, -1};
+    an entry of -1 (the reference's per-layer fp fallback) raises NotImplementedError - the Swin engine has none."""
+    if len(cfg) != n:
+        raise ValueError('bit_config has %d entries, the model %d QConv2d / QLinear layers' % (len(cfg), n))
+    for b in cfg:
+        if b not in (4, 8, -1):
+            raise ValueError('%r is not in list: bit_config entries are 4 or 8' % (b,))
+    if -1 in cfg:
+        raise NotImplementedError('bit_config entry -1 (a layer in fp32): the Swin engine has no per-layer fp fallback')
+
+
 def window_partition(x, ws):
     B, H, W, C = x.shape
     return x.view(B, H // ws, ws, W // ws, ws, C).permute(0, 1, 3, 2, 4, 5).contiguous().view(-1, ws, ws, C)
@@ -74,10 +86,11 @@ class WindowAttention(nn.Module):
         self.qact4 = _qact(cfg, quant, calibrate)
         self.proj = _qlinear(cfg, dim, dim, quant, calibrate)
         nn.init.trunc_normal_(self.relative_position_bias_table, std=.02)
+        self.global_distance = []        # (SwinTransformer shares ONE list with every module that owns a QLinear)
 
     def forward(self, x, mask=None):
         B_, N, C = x.shape
-        x = self.qact1(self.qkv(x))
+        x = self.qact1(self.qkv(x, self.global_distance))
         qkv = x.reshape(B_, N, 3, self.num_heads, C // self.num_heads).permute(2, 0, 3, 1, 4)
         q, k, v = qkv[0], qkv[1], qkv[2]
         attn = self.qact_attn1((q * self.scale) @ k.transpose(-2, -1))
@@ -89,7 +102,7 @@ class WindowAttention(nn.Module):
             attn = (attn.view(B_ // nW, nW, self.num_heads, N, N) + mask.unsqueeze(1).unsqueeze(0)).view(-1, self.num_heads, N, N)
         attn = self.log_int_softmax(attn, self.qact2.quantizer.scale)
         x = (attn @ v).transpose(1, 2).reshape(B_, N, C)
-        return self.qact4(self.proj(self.qact3(x)))
+        return self.qact4(self.proj(self.qact3(x), self.global_distance))
 
 
 class Mlp(nn.Module):
@@ -100,9 +113,11 @@ class Mlp(nn.Module):
         self.qact1 = _qact(cfg, quant, calibrate)
         self.fc2 = _qlinear(cfg, hidden_features, in_features, quant, calibrate)
         self.qact2 = _qact(cfg, quant, calibrate)
+        self.global_distance = []
 
     def forward(self, x):
-        return self.qact2(self.fc2(self.qact1(self.act(self.fc1(x)))))
+        gd = self.global_distance
+        return self.qact2(self.fc2(self.qact1(self.act(self.fc1(x, gd))), gd))
 
 
 class SwinTransformerBlock(nn.Module):
@@ -160,6 +175,7 @@ class PatchMerging(nn.Module):
         self.qact1 = _qact(cfg, quant, calibrate)
         self.reduction = _qlinear(cfg, 4 * dim, 2 * dim, quant, calibrate, bias=False)
         self.qact2 = _qact(cfg, quant, calibrate, ln=True)
+        self.global_distance = []
 
     def forward(self, x, last_quantizer=None):
         H, W = self.input_resolution
@@ -174,7 +190,7 @@ class PatchMerging(nn.Module):
         # channels by C scales - one more reason its Swin cannot run as shipped (SURVEY 8c caveat 3).  The intent (FQ-ViT's own
         # PatchMerging) is built; the integer LayerNorm with in_scale_expand = 4 is pinned by the real class (tests/golden/kat_ops.npz).
         x = self.qact1(self.norm(x, last_quantizer, self.qact1.quantizer, None, 4))
-        return self.qact2(self.reduction(x))
+        return self.qact2(self.reduction(x, self.global_distance))
 
 
 class BasicLayer(nn.Module):
@@ -249,6 +265,11 @@ class SwinTransformer(nn.Module):
         self.act_out = _qact(cfg, quant, calibrate)
         self.apply(self._init_weights)
         self._plan = None
+        # the weight-distance entry of every QLinear of a calibration forward, in bit-list order (the convolution has none, as in ViT)
+        self.global_distance = []
+        for m in self.modules():
+            if isinstance(m, (WindowAttention, Mlp, PatchMerging)):
+                m.global_distance = self.global_distance
 
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):
@@ -282,6 +303,7 @@ class SwinTransformer(nn.Module):
         for m in self._q_modules():
             m.calibrate = True
         self._plan = None
+        del self.global_distance[:]          # (in place: the modules hold this very list)
 
     def model_open_last_calibrate(self):
         for m in self._q_modules():
@@ -309,15 +331,70 @@ class SwinTransformer(nn.Module):
                 c[name] = {k: v.detach().float().cpu().reshape(-1) for k, v in m.quantizer.dic_scale.items()}
         return c
 
-    def freeze(self, device=None, bits=8):
+    def freeze(self, device=None, bits=8, pack4=True):
         from .swin_plan import SwinPlan
         if not self.input_quant:
             raise NotImplementedError('the HIP engine fuses qact_input into the patch gather: input_quant=True models only')
         if not (self.cfg.INT_NORM and self.cfg.INT_SOFTMAX):
             raise NotImplementedError('the HIP engine implements the ptf=True, lis=True configuration')
         dev = device or self.head.weight.device
-        self._plan = SwinPlan(self.arch, dict(self.state_dict()), self.export_calib(), device=dev, in_chans=self.in_chans, bits=bits)
+        self._plan = SwinPlan(self.arch, dict(self.state_dict()), self.export_calib(), device=dev, in_chans=self.in_chans, bits=bits, pack4=pack4)
         return self._plan
+
+    # ---- per-layer widths -----------------------------------------------------------------------------------------------
+    def bit_config_names(self):
+        """the layers a ``bits`` list addresses, in its order: ``patch_embed.proj``; per block ``attn.qkv, attn.proj, mlp.fc1, mlp.fc2``;
+        behind a stage's blocks its ``downsample.reduction``; ``head`` (= ``linear_modules()`` = ``SwinPlan.linear_tap_names()``)"""
+        return [n for n, _ in self.linear_modules()]
+
+    def bit_config_length(self):
+        return 1 + 4 * sum(self.arch['depths']) + (self.num_layers - 1) + 1
+
+    def layer_macs(self):
+        """analytic multiply-accumulates of one image per layer, in bit-list order"""
+        a = self.arch
+        g = a['img_size'] // a['patch_size']
+        macs = [g * g * self.in_chans * a['patch_size'] ** 2 * a['embed_dim']]
+        H = g
+        for li, depth in enumerate(a['depths']):
+            Cc, T = a['embed_dim'] * 2 ** li, H * H
+            hid = int(Cc * a['mlp_ratio'])
+            macs += [T * Cc * 3 * Cc, T * Cc * Cc, T * Cc * hid, T * hid * Cc] * depth
+            if li < self.num_layers - 1:
+                H //= 2
+                macs.append(H * H * 4 * Cc * 2 * Cc)
+        return macs + [self.num_features * self.num_classes]
+
+    def search_ties(self):
+        """index groups of the mixed-precision search (``search.pareto_candidates(ties=...)``): ``{qkv, proj}`` and ``{fc1, fc2}`` of
+        every block share a width, each reduction and the head draw alone, and index 0 (the convolution) is in no group: it stays at 8"""
+        ties = []
+        for i, n in enumerate(self.bit_config_names()):
+            if n.endswith('attn.qkv') or n.endswith('mlp.fc1'):
+                ties.append([i, i + 1])
+            elif n.endswith('reduction') or n == 'head':
+                ties.append([i])
+        return ties
+
+    def _bits_arg(self, bits):
+        """``bits`` of forward / forward_uint8 -> (default width of a plan frozen for it, validated list or None)"""
+        if isinstance(bits, (list, tuple)):
+            cfg = [int(b) for b in bits]
+            check_bit_list(cfg, self.bit_config_length())
+            return (self._plan.bits if self._plan is not None else 8), cfg
+        return bits, None
+
+    def _plan_for(self, x, bits):
+        """the frozen plan, serving ``bits`` (an int or a list) without a rebuild: it holds both widths of every layer.  An int moves
+        the plan's default width, which the tapped and model-diff paths run."""
+        width, cfg = self._bits_arg(bits)
+        if self._plan is None:
+            self.freeze(x.device if x.is_cuda else None, bits=width)
+        if cfg is None and self._plan.bits != width:
+            if width not in (4, 8):
+                raise KeyError('int%s' % (width,))
+            self._plan.bits = width
+        return cfg
 
     # ---- forward -----------------------------------------------------------------------------------------------------
     def forward_features(self, x):
@@ -332,15 +409,19 @@ class SwinTransformer(nn.Module):
         return torch.flatten(x, 1)
 
     def forward(self, x, bits=8):
+        """``bits``: 8 | 4 for the whole model, or a list of ``bit_config_length()`` widths in the order of ``bit_config_names()``"""
         if self.quant and all(m.quant and not m.calibrate for m in self._q_modules()):   # a per-module .quant = False sends the reference down its float branch
             # ---- THE HOT PATH: HIP kernels through the C ABI ------------------------------------------------------------------
-            if self._plan is None or self._plan.bits != bits:
-                self.freeze(x.device if x.is_cuda else None, bits=bits)
+            cfg = self._plan_for(x, bits)
             linear = self.linear_modules()
             if any(m._forward_hooks for _, m in linear):
+                if cfg is not None:
+                    raise NotImplementedError('forward hooks on the layers of a Swin model run one weight width: pass bits=8 or 4')
                 return self._forward_hooked(x, linear)
-            return self._plan.forward(x)
-        return self.act_out(self.head(self.forward_features(x)))
+            return self._plan.forward(x, bit_config=cfg)
+        if isinstance(bits, (list, tuple)):
+            self._bits_arg(bits)
+        return self.act_out(self.head(self.forward_features(x), self.global_distance))
 
     def linear_modules(self):
         """(name, module) of the QConv2d / QLinear modules in ``named_modules`` order: the order of ``SwinPlan.forward_linear_taps``"""
@@ -374,13 +455,12 @@ class SwinTransformer(nn.Module):
             raise ValueError('mean / std have %d / %d entries, the model %d input channels' % (len(mean), len(std), self.in_chans))
         lut = uint8_lut(mean, std, self.in_chans)
         if self.quant and all(m.quant and not m.calibrate for m in self._q_modules()):
-            if self._plan is None or self._plan.bits != bits:
-                self.freeze(images.device if images.is_cuda else None, bits=bits)
+            cfg = self._plan_for(images, bits)
             cache = self._plan.__dict__.setdefault('_u8_luts', {})       # device tables: they go with the plan (input scale)
             key = lut.numpy().tobytes()
             if key not in cache:
                 cache[key] = self._plan.input_lut(lut)
-            return self._plan.forward_uint8(images, cache[key], layout)
+            return self._plan.forward_uint8(images, cache[key], layout, bit_config=cfg)
         return self.forward(expand_uint8(images, lut, layout), bits)
 
 

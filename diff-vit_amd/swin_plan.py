@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import engine as E
-from .swin import relative_position_index, shifted_window_regions  # noqa: F401
+from .swin import check_bit_list, relative_position_index, shifted_window_regions  # noqa: F401
 
 
 def _pad128(n):
@@ -32,8 +32,16 @@ def _window_index(H, W, ws, shift):
 
 
 class SwinPlan:
-    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, bits=8):
-        self.arch, self.device, self.in_chans, self.bits = dict(arch), torch.device(device), in_chans, bits
+    """``bits``: the plan's default weight width (what every entry point runs without a list; the model-diff paths know only this one).
+    The plan holds the fp32 weights on the GPU and freezes the codes of a (layer, width, layout) with ``p2v_freeze_weights`` when a
+    forward first asks for them, so ``forward(..., bit_config=[...])`` takes one width per layer - in the order of ``linear_tap_names()`` -
+    without rebuilding anything.  ``pack4``: 4-bit layers of the fused forward stream packed codes (two per byte); False keeps them
+    one per byte (A/B comparison).  The tapped / model-diff sequences always read int8-stored codes."""
+
+    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, bits=8, pack4=True):
+        if bits not in (4, 8):
+            raise KeyError('int%s' % (bits,))          # (the weight scale a width has none of: what the lookup below raised)
+        self.arch, self.device, self.in_chans, self.bits, self.pack4 = dict(arch), torch.device(device), in_chans, bits, bool(pack4)
         if self.device.type != 'cuda':
             raise RuntimeError('SwinPlan needs a GPU device: the quantized forward has no CPU path')
         if self.device.index is None:
@@ -43,8 +51,15 @@ class SwinPlan:
         self.W = {k: v.detach().float().cpu() for k, v in state_dict.items() if v.dtype == torch.float32}
         self.c = calib
         self._recorded = {}
+        self._layers, self._all_frozen = [], False
+        self.resid_prefolded = []
         with torch.cuda.device(self.device):      # uploads and GELU-table builds on the plan's device, whatever the caller's current one
             self._build()
+            self._names = self.linear_tap_names()
+            assert [d['name'] for d in sorted(self._layers, key=lambda d: self._names.index(d['name']))] == self._names
+            for d in self._layers:
+                d['idx'] = self._names.index(d['name'])
+            self._layers.sort(key=lambda d: d['idx'])
 
     # ---- helpers -------------------------------------------------------------------------------------------------------
     def _dev(self, t, dtype=torch.float32):
@@ -69,27 +84,94 @@ class SwinPlan:
         return s
 
     def _linear(self, name, s_x, bias=True, k_pad=None, frag=False):
-        """int8-stored weight codes [n_pad][k_pad], colscale = s_x * s_w, bias; ``frag``: also the MFMA-fragment-order copy the fused
-        LayerNorm+GEMM kernel streams (qkv / fc1 of stages up to 384 channels)."""
-        bt = 'int%d' % self.bits
+        """one QConv2d / QLinear: the fp32 weights [N][K] and the bias on the GPU.  Codes, column scales and RESID tables are made per
+        width on first use (``_lin``).  ``frag``: the fused LayerNorm+GEMM kernel may stream this layer (qkv / fc1 of stages up to 384
+        channels), which reads the MFMA-fragment-order copy."""
         w = self.W[name + '.weight']
         w2 = w.reshape(w.shape[0], -1)
         N, K = w2.shape
-        s_w = self.c[name][bt].reshape(-1)
-        lo, hi = (-128, 127) if self.bits == 8 else (-8, 7)
-        codes = torch.clamp(torch.round(w2 / s_w.reshape(-1, 1)), lo, hi)
-        kp = k_pad or (K + 63) // 64 * 64          # the GEMM walks 64-deep k-tiles: extra weight columns are zero
-        wp = torch.zeros(_pad128(N), kp, dtype=torch.int8)
-        wp[:N, :K] = codes.to(torch.int8)
-        cs = torch.zeros(_pad128(N))
-        cs[:N] = (torch.tensor(float(s_x)) * s_w.expand(N)).float()
+        kp = (K + 63) // 64 * 64                   # the GEMM walks 64-deep k-tiles: extra weight columns are zero
+        assert k_pad in (None, kp)
         b = torch.zeros(_pad128(N))
         if bias:
             b[:N] = self.W[name + '.bias']
-        d = dict(w=self._dev(wp, torch.int8), cs=self._dev(cs), b=self._dev(b), N=N, K=kp)
-        d['wf'] = self._dev(E.fragment_order(wp), torch.int8) if frag else None
-        d['lin'] = E.Linear(E.ptr(d['w']), E.ptr(d['cs']), E.ptr(d['b']), E.ptr(d['wf']) if frag else None, 0)
+        d = dict(name=name, N=N, K=kp, frag=bool(frag), s_x=float(s_x), w32=self._dev(w2), b=self._dev(b), width={}, forms={}, epi=None)
+        self._layers.append(d)
         return d
+
+    def _width(self, d, bits):
+        """(weight scales, colscale = s_x * s_w) of layer ``d`` at ``bits``, on the GPU"""
+        if bits not in d['width']:
+            s_w = self.c[d['name']]['int%d' % bits].reshape(-1).float()
+            cs = torch.zeros(_pad128(d['N']))
+            cs[:d['N']] = (torch.tensor(d['s_x']) * s_w.expand(d['N'])).float()
+            d['width'][bits] = (self._dev(s_w), self._dev(cs))
+        return d['width'][bits]
+
+    def _packed(self, bits):
+        return self.pack4 and bits == 4
+
+    def _lin(self, d, bits, packed=False, frag=False):
+        """the ``p2v_linear`` of layer ``d`` at ``bits``: int8-stored codes, or (``packed``) the packed int4 tiles; ``frag``: with the
+        fragment-order copy.  Frozen on the current stream on first use, kept afterwards."""
+        f = d['forms'].get((bits, packed))
+        if f is not None and (f['wf'] is not None or not frag):
+            return f['lin']
+        with torch.cuda.device(self.device):
+            s_w, cs = self._width(d, bits)
+            if f is None:
+                w = E.freeze_weights(d['w32'], s_w, bits, E.W_TILES_P4 if packed else E.W_ROWS_I8)
+                f = d['forms'][(bits, packed)] = dict(w=w, wf=None, tab=None, lin=E.Linear(E.ptr(w), E.ptr(cs), E.ptr(d['b']), None, 1 if packed else 0))
+            if frag and f['wf'] is None:
+                f['wf'] = E.freeze_weights(d['w32'], s_w, bits, E.W_FRAG_P4 if packed else E.W_FRAG_I8)
+                f['lin'].w_frag = E.ptr(f['wf'])
+        return f['lin']
+
+    def _resid_tab(self, d, bits, packed=False):
+        """``p2v_epilogue.resid_tab`` of the RESID layer ``d`` at ``bits`` (None where the library does not prove the table exact): it
+        folds the layer's column scales and bias, so there is one per weights / epilogue pair"""
+        lin = self._lin(d, bits, packed)
+        f = d['forms'][(bits, packed)]
+        if f['tab'] is None:
+            with torch.cuda.device(self.device):
+                e, n, L = d['epi'], d['N'], E.lib()
+                nbytes = L.p2v_resid_prefold_bytes(n)
+                tab = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+                usable = C.c_int(0)
+                torch.cuda.synchronize(self.device)                       # the vectors were uploaded on torch's stream
+                E.check(L.p2v_resid_prefold(C.byref(lin), C.byref(e), n, E.ptr(tab), nbytes, C.byref(usable), None))
+                f['tab'] = (tab if usable.value else False,)
+                self.resid_prefolded.append(bool(usable.value))
+        t = f['tab'][0]
+        return C.cast(E.ptr(t), C.c_void_p) if t is not False else None
+
+    def _ensure(self, d, bits, packed):
+        self._lin(d, bits, packed, frag=d['frag'])
+        if d['epi'] is not None:
+            self._resid_tab(d, bits, packed)
+
+    def freeze_all(self):
+        """freeze every (layer, width) a fused forward can ask for - 8-bit codes, 4-bit codes (packed with ``pack4``), the fragment-order
+        copies and the RESID tables - so that no later ``bit_config`` allocates or synchronises"""
+        for d in self._layers:
+            for bits in (8, 4):
+                self._ensure(d, bits, self._packed(bits))
+        torch.cuda.synchronize(self.device)
+        self._all_frozen = True
+        return self
+
+    def bit_config(self, bit_config=None):
+        """the validated per-layer widths as a tuple of ``len(linear_tap_names())`` ints (None: the plan's default width everywhere).
+        ValueError for a wrong length or an entry outside {4, 8, -1}; NotImplementedError for -1 (Swin has no per-layer fp fallback)."""
+        n = len(self._names)
+        if bit_config is None:
+            return (self.bits,) * n
+        try:
+            cfg = tuple(int(b) for b in bit_config)
+        except TypeError:
+            raise ValueError('bit_config must be a list of %d entries of 4 or 8, got %r' % (n, bit_config))
+        check_bit_list(cfg, n)
+        return cfg
 
     def _ln(self, prefix, s_in_vec, s_out, C_):
         """QIntLayerNorm 'int' constants: mask = round(in_scale / min), inv_out = 1 / out_scale; the following QAct has the LN's
@@ -190,27 +272,17 @@ class SwinPlan:
         self.head = self._linear('head', self.s_pool)
         self.s_out = self._pot('act_out')
 
-    def _resid_epi(self, s_mid, s_res, s_next, n, lin=None):
-        """constants of a RESID epilogue; with the layer's weights (``lin``) also the pre-folded table of ``p2v_resid_prefold`` - used
-        only when the library proves it gives the reference's codes for these constants (all 65 536 numerators of every channel)."""
+    def _resid_epi(self, s_mid, s_res, s_next, n, lin):
+        """constants of the RESID epilogue behind layer ``lin``; the pre-folded table of ``p2v_resid_prefold`` is made per width
+        (``_resid_tab``)"""
         e = E.Epilogue()
         t = [self._vec(s_mid, n), self._vec(s_res, n), self._vec(s_next, n)]
         e.s_mid, e.s_res, e.s_next = [C.cast(E.ptr(x), C.c_void_p) for x in t]
-        if lin is not None:
-            L = E.lib()
-            nbytes = L.p2v_resid_prefold_bytes(n)
-            tab = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
-            usable = C.c_int(0)
-            torch.cuda.synchronize(self.device)                       # the vectors above were uploaded on torch's stream
-            E.check(L.p2v_resid_prefold(C.byref(lin['lin']), C.byref(e), n, E.ptr(tab), nbytes, C.byref(usable), None))
-            if usable.value:
-                self._keep.append(tab)
-                e.resid_tab = C.cast(E.ptr(tab), C.c_void_p)
-            self.resid_prefolded = getattr(self, 'resid_prefolded', []) + [bool(usable.value)]
+        lin['epi'] = e
         return e
 
     # ---- forward -------------------------------------------------------------------------------------------------------
-    def _record(self, B, fused=True, ddv_n=0, with_linear=False, lin_taps=False, attention=False):
+    def _record(self, B, fused=True, ddv_n=0, with_linear=False, lin_taps=False, attention=False, cfg=None):
         """the launch sequence of one forward at batch B as a ``p2v_op`` array with its own activation buffers (built once
         per batch size and stream slot, replayed by ``p2v_run_ops``).  ``fused``: norm1 + qkv and norm2 + fc1 of stages up to 384
         channels run as ONE launch each (``P2V_OP_LN_GEMM``: the LayerNorm output stays in LDS); the tap replay records the
@@ -221,8 +293,20 @@ class SwinPlan:
         ``lin_taps`` (unfused): the fp32 output of every QConv2d / QLinear into a buffer of its own (``forward_linear_taps``).
         ``attention`` (with ``ddv_n``): the window launches run tapped (the planes of ``p2v_window_attention_taps``, named in the WINATTN
         record) into three planes per stage that its blocks share - qact_attn1, qact2 (int8 codes) and the softmax exponents
-        (``P2V_COS_LOG2K``) - each reduced right behind the launch."""
+        (``P2V_COS_LOG2K``) - each reduced right behind the launch.
+        ``cfg`` (fused only): the width of every layer (``bit_config()``); 4-bit layers read packed codes with ``pack4``.  ``_switch``
+        moves the recording to another list.  Every other sequence runs the plan's default width on int8-stored codes (the RESID mid-code
+        tap and the records of ``p2v_gemm_i8`` behind it take those)."""
         a = self.arch
+        if not fused or cfg is None:
+            cfg = (self.bits,) * len(self._names)
+        lin_ops = []
+
+        def L_(d, frag=False):
+            """(p2v_linear, RESID table or None) of layer ``d`` in this sequence"""
+            bits = cfg[d['idx']]
+            packed = fused and self._packed(bits)
+            return self._lin(d, bits, packed, frag), (self._resid_tab(d, bits, packed) if d['epi'] is not None else None)
         P, g = a['patch_size'], self.g
         dev = self.device
         ops, taps, keep = [], [], []
@@ -275,7 +359,7 @@ class SwinPlan:
             o = E.Op()
             o.kind, o.inp, o.out = E.OP_GEMM_F32, E.ptr(x), E.ptr(t_)
             o.M, o.K, o.N, o.lda, o.ldo = x.shape[0], x.shape[1], N, x.shape[1], ld
-            o.lin = lin['lin']
+            o.lin = L_(lin)[0]
             ops.append(o)
             if n:
                 stage(name, t_, rows, N, ld, E.COS_F32)
@@ -292,7 +376,10 @@ class SwinPlan:
             o = E.Op()
             o.kind, o.epi, o.inp, o.out = E.OP_GEMM, kind, E.ptr(x), E.ptr(out)
             o.M, o.K, o.N, o.lda, o.ldo = x.shape[0], x.shape[1], lin['N'], x.shape[1], out.shape[1]
-            o.lin, o.ep = lin['lin'], epi
+            o.lin, o.ep = L_(lin)[0], epi
+            if kind == E.EPI_RESID:
+                o.ep.resid_tab = L_(lin)[1]
+            lin_ops.append((len(ops), lin))
             ops.append(o)
             return out
 
@@ -300,7 +387,8 @@ class SwinPlan:
             o = E.Op()
             o.kind, o.epi, o.inp, o.out = E.OP_LN_GEMM, kind, E.ptr(x), E.ptr(out)
             o.M, o.K, o.N, o.lda, o.ldo = x.shape[0], Cc, lin['N'], x.shape[1], lin['N']
-            o.lin, o.ep, o.ln = lin['lin'], epi, ln
+            o.lin, o.ep, o.ln = L_(lin, frag=True)[0], epi, ln
+            lin_ops.append((len(ops), lin))
             ops.append(o)
             return out
 
@@ -319,7 +407,7 @@ class SwinPlan:
 
         def epi_res(src, residual, mid=None):
             e = E.Epilogue()
-            e.s_mid, e.s_res, e.s_next, e.residual, e.resid_tab = src.s_mid, src.s_res, src.s_next, E.ptr(residual), src.resid_tab
+            e.s_mid, e.s_res, e.s_next, e.residual = src.s_mid, src.s_res, src.s_next, E.ptr(residual)      # (resid_tab: per width, set by gemm)
             e.tap_out = E.ptr(mid)              # RESID records: the int8 mid-code destination (include/p2vit.h, op table)
             return e
 
@@ -358,7 +446,7 @@ class SwinPlan:
                 t_qkv, t_fc1 = ftap(p + 'attn.qkv', rows, b['qkv']['N']), None
                 e_fc1 = epi_req(b['inv_s_fc1'])
                 e_fc1.gelu = E.gelu_table(b['inv_s_fc1'], self.device)       # exact GELU -> qact1 threshold table (cached per scale)
-                fuse = (fused and b['qkv']['wf'] is not None and hid_k == fc1_n and E.lib().p2v_ln_gemm_fusable(E.EPI_REQUANT, Cc, b['qkv']['N'], 0) == 1
+                fuse = (fused and b['qkv']['frag'] and hid_k == fc1_n and E.lib().p2v_ln_gemm_fusable(E.EPI_REQUANT, Cc, b['qkv']['N'], 0) == 1
                         and E.lib().p2v_ln_gemm_fusable(E.EPI_GELU, Cc, b['fc1']['N'], e_fc1.gelu.cells if e_fc1.gelu.table else 0) == 1)
                 if fuse:
                     ln_gemm(E.EPI_REQUANT, x, b['ln1'], Cc, b['qkv'], epi_req(b['inv_s_qkv']), qkv)
@@ -432,9 +520,10 @@ class SwinPlan:
         o = E.Op()
         o.kind, o.epi, o.inp = E.OP_GEMM, E.EPI_HEAD, E.ptr(pooled)
         o.M, o.K, o.N, o.lda, o.ldo = B, self.C_last, self.head['N'], self.C_last, self.head['N']
-        o.lin, o.ep = self.head['lin'], e
+        o.lin, o.ep = L_(self.head)[0], e
+        lin_ops.append((len(ops), self.head))
         ops.append(o)
-        rec = dict(taps=taps, keep=keep, head=len(ops) - 1, lin_out=lin_out)
+        rec = dict(taps=taps, keep=keep, head=len(ops) - 1, lin_out=lin_out, cfg=tuple(cfg), lin_ops=lin_ops)
         if n:
             # the stages reference a STATIC logits buffer (their records hold its address); forward_ddv returns a copy
             ldl = (self.head['N'] + 3) // 4 * 4
@@ -465,16 +554,49 @@ class SwinPlan:
         rec['n'] = len(ops)
         return rec
 
-    def _replay(self, images, slot, taps=None, profile=False):
-        with torch.cuda.device(self.device):       # the recorded pointers and the launch stream belong to the plan's GPU
-            return self._replay_on_device(images, slot, taps, profile)
+    def _prepare(self, cfg):
+        """freeze, on the caller's stream and thread, whatever a fused forward under ``cfg`` reads and the plan does not hold yet"""
+        if not self._all_frozen:
+            for d in self._layers:
+                self._ensure(d, cfg[d['idx']], self._packed(cfg[d['idx']]))
 
-    def _replay_on_device(self, images, slot, taps, profile):
-        B = images.shape[0]
-        key = (B, slot, taps is None)
+    def _switch(self, r, cfg):
+        """move the fused recording ``r`` to the widths ``cfg``: the ``lin`` and ``ep.resid_tab`` members of its GEMM / LN_GEMM records in
+        the host op table, which ``p2v_run_ops`` reads when it is called.  Buffers, shapes and record kinds do not depend on a width."""
+        old = r['cfg']
+        for i, d in r['lin_ops']:
+            bits = cfg[d['idx']]
+            if bits != old[d['idx']]:
+                o = r['ops'][i]
+                packed = self._packed(bits)
+                o.lin = self._lin(d, bits, packed, frag=o.kind == E.OP_LN_GEMM)
+                if d['epi'] is not None:
+                    o.ep.resid_tab = self._resid_tab(d, bits, packed)
+        r['cfg'] = cfg
+
+    def _fused_record(self, B, slot, cfg):
+        """the one fused recording of (batch, slot), at the widths ``cfg``"""
+        key = (B, slot, True)
         if key not in self._recorded:
-            self._recorded[key] = self._record(B, fused=taps is None)
+            self._recorded[key] = self._record(B, fused=True, cfg=cfg)
         r = self._recorded[key]
+        if r['cfg'] != cfg:
+            self._switch(r, cfg)
+        return r
+
+    def _replay(self, images, slot, taps=None, profile=False, cfg=None):
+        with torch.cuda.device(self.device):       # the recorded pointers and the launch stream belong to the plan's GPU
+            return self._replay_on_device(images, slot, taps, profile, cfg or self.bit_config())
+
+    def _replay_on_device(self, images, slot, taps, profile, cfg):
+        B = images.shape[0]
+        if taps is None:
+            r = self._fused_record(B, slot, cfg)
+        else:
+            key = (B, slot, False, self.bits)
+            if key not in self._recorded:
+                self._recorded[key] = self._record(B, fused=False)
+            r = self._recorded[key]
         out = torch.empty(B, self.head['N'], dtype=torch.float32, device=self.device)
         r['ops'][0].inp = E.ptr(images)
         r['ops'][r['n'] - 1].out = E.ptr(out)
@@ -497,6 +619,7 @@ class SwinPlan:
     def _replay_extra(self, images, key, **kw):
         """replay the recorded sequence ``key`` (made with ``_record(B, fused=False, **kw)`` on first use) in one ``p2v_run_ops`` call"""
         with torch.cuda.device(self.device):
+            key = key + (self.bits,)
             if key not in self._recorded:
                 self._recorded[key] = self._record(images.shape[0], fused=False, **kw)
             r = self._recorded[key]
@@ -558,14 +681,11 @@ class SwinPlan:
         from .data import uint8_lut_i8
         return uint8_lut_i8(lut_f32.detach().float().cpu(), 1.0 / self.s_in).contiguous().to(self.device)
 
-    def _replay_u8(self, images, lut, layout, slot):
+    def _replay_u8(self, images, lut, layout, slot, cfg=None):
         """the recorded sequence with its first launch replaced: p2v_u8_patchify writes the same patch matrix into the recorded buffer"""
         with torch.cuda.device(self.device):
             B = images.shape[0]
-            key = (B, slot, True)
-            if key not in self._recorded:
-                self._recorded[key] = self._record(B, fused=True)
-            r = self._recorded[key]
+            r = self._fused_record(B, slot, cfg or self.bit_config())
             out = torch.empty(B, self.head['N'], dtype=torch.float32, device=self.device)
             p = r['ops'][0]
             L, st = E.lib(), E.stream_ptr(self.device)
@@ -574,9 +694,11 @@ class SwinPlan:
             E.check(L.p2v_run_ops(C.cast(C.byref(r['ops'], C.sizeof(E.Op)), C.POINTER(E.Op)), r['n'] - 1, st))
             return out
 
-    def forward_uint8(self, images, lut, layout='NHWC', n_streams=3, slices=None):
+    def forward_uint8(self, images, lut, layout='NHWC', n_streams=3, slices=None, bit_config=None):
         """``forward`` on uint8 images ([B, S, S, C] for 'NHWC', [B, C, S, S] for 'NCHW') read through ``lut`` (``input_lut``), single or
-        sliced like ``forward``: the logits equal ``forward`` on the images data.normalize_uint8 makes of them."""
+        sliced like ``forward``: the logits equal ``forward`` on the images data.normalize_uint8 makes of them.  ``bit_config``: as in
+        ``forward``."""
+        cfg = self.bit_config(bit_config)
         a, S, Cin = self.arch, self.arch['img_size'], self.in_chans
         if layout not in E.LAYOUTS:
             raise AssertionError("layout must be 'NHWC' or 'NCHW', got %r" % (layout,))
@@ -590,17 +712,27 @@ class SwinPlan:
         if not isinstance(lut, torch.Tensor) or lut.dtype != torch.int8 or tuple(lut.shape) != (Cin, 256) or lut.device != self.device or not lut.is_contiguous():
             raise AssertionError('lut must be a contiguous int8 [%d, 256] tensor on %s (SwinPlan.input_lut)' % (Cin, self.device))
         images = images.contiguous()
-        return self._sliced(images, n_streams, slices, lambda x, slot: self._replay_u8(x, lut, layout, slot))
+        with torch.cuda.device(self.device):
+            self._prepare(cfg)
+        return self._sliced(images, n_streams, slices, lambda x, slot: self._replay_u8(x, lut, layout, slot, cfg))
 
-    def forward(self, images, taps=None, n_streams=3, slices=None):
+    def forward(self, images, taps=None, n_streams=3, slices=None, bit_config=None):
         """images fp32 [B, in_chans, S, S] on the plan's device -> logits fp32 [B, classes] (act_out grid).  One C call replays
         the recorded launch sequence; a large batch runs as ``n_streams`` contiguous slices on their own HIP streams (images are
         independent), like the ViT plan (three: Swin-B at 256 images 25.1 k img/s against 24.6 k on two, same call, profiles/r04_slices.txt).
-        ``slices``: explicit slice sizes; slices beyond ``n_streams`` run on the caller's stream."""
+        ``slices``: explicit slice sizes; slices beyond ``n_streams`` run on the caller's stream.
+        ``bit_config``: one width (4 or 8) per QConv2d / QLinear in the order of ``linear_tap_names()``; None = the plan's default width
+        everywhere.  Another list costs no rebuild and no device memory: the one recording of a (batch, slot) is moved to it (``_switch``),
+        and codes the plan does not hold yet are frozen on the caller's stream first (``freeze_all`` does that ahead of time)."""
+        cfg = self.bit_config(bit_config)
         images = self._check_images(images)
         if taps is not None:
+            if bit_config is not None:
+                raise NotImplementedError('the tapped forward runs the plan\'s one default width: no bit_config list')
             return self._replay(images, 0, taps)
-        return self._sliced(images, n_streams, slices, self._replay)
+        with torch.cuda.device(self.device):
+            self._prepare(cfg)
+        return self._sliced(images, n_streams, slices, lambda x, slot: self._replay(x, slot, cfg=cfg))
 
     def _sliced(self, images, n_streams, slices, replay):
         """the batch slicing of ``forward``; ``replay(images, slot)`` runs one slice on the current stream"""

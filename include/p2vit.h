@@ -817,6 +817,27 @@ int p2v_forward_ddv_ex2(p2v_plan* plan, const float* images, int n, const int8_t
                         size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, int8_t* attn_scratch,
                         size_t attn_scratch_bytes, double* sums, void* stream);
 
+/* ---- Weight freeze on the device (additive: no structure, existing entry point or P2V_ABI_VERSION changes; found by their symbols) ------
+ * p2v_freeze_weights turns the fp32 weights of one layer (dev [N][ldw], ldw >= K, only 4-byte aligned) into the codes of one bit width in
+ * one of the layouts a p2v_linear holds:
+ *   code[n][k] = clamp(rne(w[n][k] / scale[n_scale == 1 ? 0 : n]), lo, hi)      [-128, 127] at 8 bits, [-8, 7] at 4 bits
+ * with an IEEE division and a round to nearest even - torch.round(w / s), for scales that are powers of two and for scales that are not -
+ * zero padded to n_pad = round_up(N, 128) rows of k_pad = round_up(K, 64) codes (every code with n >= N or k >= K is 0; nothing there is read).
+ *   P2V_W_ROWS_I8    int8 [n_pad][k_pad], row major: p2v_linear.w_codes with packed4 == 0 (bits 8, or 4-bit codes one per byte)
+ *   P2V_W_FRAG_I8    the same codes in MFMA-fragment order: p2v_linear.w_frag with packed4 == 0
+ *   P2V_W_TILES_P4   the packed int4 tile images, chunk swizzle included: p2v_linear.w_codes with packed4 == 1 (bits 4 only)
+ *   P2V_W_FRAG_P4    the packed fragment order: p2v_linear.w_frag with packed4 == 1 (bits 4 only)
+ * p2v_freeze_bytes = n_pad * k_pad, half of it for the two packed layouts; 0 for N or K < 1 (or K > 2^30) or an unknown layout.  The call
+ * writes exactly these bytes of `out` (dev, 16-byte aligned) and nothing beyond them; it allocates nothing, does not synchronise and is ONE
+ * launch on `stream`: one thread per 16 codes of a row, stored as one 16- or 8-byte vector.
+ * Refused before any HIP call: P2V_E_ARG for a null pointer (or a misaligned one: w / scale 4 bytes, out 16 bytes); P2V_E_SHAPE for N or
+ * K < 1, ldw < K, n_scale not in {1, N}, an unknown layout; P2V_E_BITS for bits not in {4, 8} and for a packed layout with bits = 8;
+ * P2V_E_WORKSPACE for out_bytes < p2v_freeze_bytes. */
+enum { P2V_W_ROWS_I8 = 0, P2V_W_FRAG_I8 = 1, P2V_W_TILES_P4 = 2, P2V_W_FRAG_P4 = 3 };
+size_t p2v_freeze_bytes(int N, int K, int layout);
+int p2v_freeze_weights(const float* w, long long ldw, int N, int K, const float* scale, int n_scale, int bits, int layout, void* out,
+                       size_t out_bytes, void* stream);
+
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
 
