@@ -319,17 +319,19 @@ __global__ __launch_bounds__(256, 3) void k_window_attention(std::conditional_t<
 // ---------------------------------------------------------------------------------------------------
 int g_attn_waves = 8;     // P2V_ATTN_WAVES
 int p2v_launch_window_attention_wide(const WinAttnArgs& a, hipStream_t st);      // p2vit_winattn_wide.hip: windows of 9 x 9 ... 12 x 12
+// a thunk per instantiation: the untapped kernels take the base struct
+template <int NT, bool TAP>
+static void launch_window_t(const WinAttnArgs& a, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((k_window_attention<NT, TAP>), grid, dim3(256), 0, st, a);
+}
 int p2v_launch_window_attention(const WinAttnArgs& a, hipStream_t st) {
   if (a.wa.ws > 8) return p2v_launch_window_attention_wide(a, st);
   const int hgroups = (a.H + 3) / 4;
   const dim3 grid((unsigned)(a.B * a.wa.n_windows * hgroups));
-  if (a.wa.ws == 7) {
-    if (a.tapped()) hipLaunchKernelGGL((k_window_attention<49, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_window_attention<49, false>), grid, dim3(256), 0, st, a);
-  } else {
-    if (a.tapped()) hipLaunchKernelGGL((k_window_attention<0, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_window_attention<0, false>), grid, dim3(256), 0, st, a);
-  }
+  // [generic (any ws up to 8)][untapped]
+  static void (*const table[2][2])(const WinAttnArgs&, dim3, hipStream_t) = {{launch_window_t<49, true>, launch_window_t<49, false>},
+                                                                             {launch_window_t<0, true>, launch_window_t<0, false>}};
+  table[a.wa.ws == 7 ? 0 : 1][a.tapped() ? 0 : 1](a, grid, st);
   CHECK_LAUNCH();
   return 0;
 }
@@ -361,7 +363,7 @@ int p2v_launch_attention(const AttnArgs& a, int head_dim, hipStream_t st) {
     case P2V_KERNEL_STREAMING: return p2v_launch_attention_stream(a, head_dim, st);
     default: return -1;
   }
-  if (head_dim == 64) { P2V_ATTN_CASES(64, 19, true) }
-  if (head_dim == 32) { P2V_ATTN_CASES(32, 19, false) }
+  if (head_dim == 64) return launch_attn_hd<64, 19, true>(a, nkb, st);
+  if (head_dim == 32) return launch_attn_hd<32, 19, false>(a, nkb, st);
   return p2v_launch_attention_wide(a, head_dim, nkb, st);
 }

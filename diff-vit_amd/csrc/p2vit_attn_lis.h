@@ -2,6 +2,7 @@
 // instantiate it (p2vit_attn.hip: head_dim 32 / 64; p2vit_attn_wide.hip: 48 / 80 / 96 / 128), so that they compile side by side.
 #pragma once
 #include "p2vit_device.h"
+#include "p2vit_launch.h"
 
 extern int g_attn_waves;     // P2V_ATTN_WAVES
 
@@ -354,58 +355,48 @@ __global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 :
   }
 }
 
-// ISH_OK: the integer score requant is instantiated for this head_dim (64, where qk_scale is a power of two); otherwise every launch takes the
-// fp32 chain, which is exact for any multiplier
-template <int HD, int NKB, bool ISH_OK = true>
-static int launch_attn_t(const AttnArgs& a_, hipStream_t st) {
-  constexpr int KROWS = NKB * 32;   // NKB here = 32-key pairs
-  constexpr size_t smem = (size_t)KROWS * HD + (size_t)HD * (KROWS + 4) * 2 + 258 * 8 + 258 * 8;
-  AttnArgs a = a_;
-  {   // score multiplier 2^-p with p >= 1: the integer round-half-even path (|score| <= 64 * 128 * 128 < 2^21, p <= 24)
-    int ex;
-    const float m = a.at.qk_scale * (a.at.s_qkv_sq * a.at.inv_s_attn);
-    a.pshift = (m > 0.f && frexpf(m, &ex) == 0.5f && ex <= 0 && ex >= -23) ? 1 - ex : 0;
+// one resident instantiation: K and V^T of more than ~300 keys are beyond the default dynamic LDS limit
+template <int HD, int NKP, bool TAP, bool ISH>
+static int launch_attn_t(const AttnArgs& a, hipStream_t st) {
+  constexpr size_t smem = (size_t)NKP * 32 * HD + (size_t)HD * (NKP * 32 + 4) * 2 + 258 * 8 + 258 * 8;
+  if (smem > 64 * 1024) {
+    static P2vLdsGrant grant = {};
+    const hipError_t e = grant.ensure(reinterpret_cast<const void*>(&k_lis_attention<HD, NKP, TAP, ISH>), (int)smem);
+    if (e != hipSuccess) return (int)e;
   }
-#ifdef P2V_DIAG
-  a.stamps = g_gemm_stamps;
-#endif
-  const dim3 grid(a.B * a.H), block(64 * g_attn_waves);
-#define P2V_ATTN_LAUNCH(TAP_, ISH_)                                                                                          \
-  do {                                                                                                                       \
-    if (smem > 64 * 1024) {          /* K and V^T of more than ~300 keys: beyond the default dynamic LDS limit */            \
-      static bool granted[16] = {false};                                                                                     \
-      int dev = 0;                                                                                                           \
-      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;                                                \
-      if (dev < 0 || !granted[dev]) {                                                                                        \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lis_attention<HD, NKB, TAP_, ISH_>),             \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                           \
-        if (e != hipSuccess) return (int)e;                                                                                  \
-        if (dev >= 0) granted[dev] = true;                                                                                   \
-      }                                                                                                                      \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((k_lis_attention<HD, NKB, TAP_, ISH_>), grid, block, smem, st, a);                                    \
-  } while (0)
-  if constexpr (!ISH_OK) a.pshift = 0;
-  if (a.tapped()) {
-    if constexpr (ISH_OK) { if (a.pshift) { P2V_ATTN_LAUNCH(true, true); CHECK_LAUNCH(); return 0; } }
-    P2V_ATTN_LAUNCH(true, false);
-  } else {
-    if constexpr (ISH_OK) { if (a.pshift) { P2V_ATTN_LAUNCH(false, true); CHECK_LAUNCH(); return 0; } }
-    P2V_ATTN_LAUNCH(false, false);
-  }
-#undef P2V_ATTN_LAUNCH
+  hipLaunchKernelGGL((k_lis_attention<HD, NKP, TAP, ISH>), dim3(a.B * a.H), dim3(64 * g_attn_waves), smem, st, a);
   CHECK_LAUNCH();
   return 0;
 }
 
-// every ceil(tokens / 32) up to MAXP is instantiated: the padding of a launch is always less than one 32-key pair
-#define P2V_ATTN_CASE(HD_, P_, MAXP_, ISH_) case P_: if constexpr (P_ <= MAXP_) return launch_attn_t<HD_, P_, ISH_>(a, st); else return -1;
-#define P2V_ATTN_CASES(HD_, MAXP_, ISH_)                                                                                              \
-  switch (nkb) {                                                                                                                      \
-    P2V_ATTN_CASE(HD_, 1, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 2, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 3, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 4, MAXP_, ISH_)     \
-    P2V_ATTN_CASE(HD_, 5, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 6, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 7, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 8, MAXP_, ISH_)     \
-    P2V_ATTN_CASE(HD_, 9, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 10, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 11, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 12, MAXP_, ISH_)  \
-    P2V_ATTN_CASE(HD_, 13, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 14, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 15, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 16, MAXP_, ISH_) \
-    P2V_ATTN_CASE(HD_, 17, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 18, MAXP_, ISH_) P2V_ATTN_CASE(HD_, 19, MAXP_, ISH_)                                   \
-    default: return -1;                                                                                                               \
+// The resident launchers of one head_dim, in the order the code object holds their kernels (p2vit_launch.h): flat index
+// (nkp * 2 + (untapped)) * 2 + (fp32 score chain), nkp = ceil(tokens / 32).  Every nkp up to MAXP is instantiated: the padding of a launch is
+// always less than one 32-key pair.  ISH_OK: the integer score requant is instantiated for this head_dim (64, where qk_scale is a power of
+// two); otherwise every launch takes the fp32 chain, which is exact for any multiplier
+typedef int (*AttnLauncher)(const AttnArgs&, hipStream_t);
+constexpr int attn_index(int nkp, bool tap, bool ish) { return (nkp * 2 + (tap ? 0 : 1)) * 2 + (ish ? 0 : 1); }
+template <int HD, bool ISH_OK>
+struct AttnAt {
+  template <int I> static constexpr AttnLauncher at() {
+    constexpr int NKP = I >> 2;
+    static_assert(attn_index(NKP, !(I >> 1 & 1), !(I & 1)) == I, "decoded as the launcher encodes");
+    if constexpr (NKP >= 1 && (ISH_OK || (I & 1))) return launch_attn_t<HD, NKP, !(I >> 1 & 1), !(I & 1)>;
+    else return nullptr;
   }
+};
+
+template <int HD, int MAXP, bool ISH_OK>
+static int launch_attn_hd(const AttnArgs& a_, int nkp, hipStream_t st) {
+  static constexpr auto table = p2v_table<AttnLauncher, AttnAt<HD, ISH_OK>, (MAXP + 1) * 4>();
+  if (nkp < 1 || nkp > MAXP) return -1;
+  AttnArgs a = a_;
+  {   // score multiplier 2^-p with p >= 1: the integer round-half-even path (|score| <= 64 * 128 * 128 < 2^21, p <= 24)
+    int ex;
+    const float m = a.at.qk_scale * (a.at.s_qkv_sq * a.at.inv_s_attn);
+    a.pshift = (ISH_OK && m > 0.f && frexpf(m, &ex) == 0.5f && ex <= 0 && ex >= -23) ? 1 - ex : 0;
+  }
+#ifdef P2V_DIAG
+  a.stamps = g_gemm_stamps;
+#endif
+  return table[attn_index(nkp, a.tapped(), a.pshift != 0)](a, st);
+}

@@ -244,36 +244,28 @@ template <int NG>
 static int launch_packed_t(const AttnArgs& a, hipStream_t st) {
   constexpr size_t smem = (size_t)NG * 64 * 128 + 2 * 258 * 8;
   static_assert(smem <= 160 * 1024, "LDS of a CU");
-  // beyond the default dynamic LDS limit: asked for once per device.  Unsynchronised like the resident launcher's flags: two enqueueing threads
-  // that race here both set the same attribute to the same value
-  static bool granted[16] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
-  if (dev < 0 || !granted[dev]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lis_attention_packed<NG>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    if (dev >= 0) granted[dev] = true;
-  }
+  static P2vLdsGrant grant = {};                   // always beyond the default dynamic LDS limit
+  const hipError_t e = grant.ensure(reinterpret_cast<const void*>(&k_lis_attention_packed<NG>), (int)smem);
+  if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL((k_lis_attention_packed<NG>), dim3((unsigned)(a.B * a.H)), dim3(64 * g_attn_waves), smem, st, a);
   CHECK_LAUNCH();
   return 0;
 }
 
+// the launchers by ceil(tokens / 64): 10 .. 19 are instantiated
+typedef int (*PackedLauncher)(const AttnArgs&, hipStream_t);
+struct PackedAt {
+  template <int I> static constexpr PackedLauncher at() {
+    if constexpr (I >= 10) return launch_packed_t<I>;
+    else return nullptr;
+  }
+};
+static const auto packed_table = p2v_table<PackedLauncher, PackedAt, 20>();
+
 // head_dim 64, no tap, tokens beyond the resident kernel's up to P2V_MAX_TOKENS_PACKED: one instantiation per ceil(tokens / 64)
 int p2v_launch_attention_packed(const AttnArgs& a, hipStream_t st) {
   if (a.probs_k || a.B * a.H <= 0 || a.N > P2V_MAX_TOKENS_PACKED) return -1;
-  switch ((a.N + 63) / 64) {
-    case 10: return launch_packed_t<10>(a, st);
-    case 11: return launch_packed_t<11>(a, st);
-    case 12: return launch_packed_t<12>(a, st);
-    case 13: return launch_packed_t<13>(a, st);
-    case 14: return launch_packed_t<14>(a, st);
-    case 15: return launch_packed_t<15>(a, st);
-    case 16: return launch_packed_t<16>(a, st);
-    case 17: return launch_packed_t<17>(a, st);
-    case 18: return launch_packed_t<18>(a, st);
-    case 19: return launch_packed_t<19>(a, st);
-    default: return -1;
-  }
+  const int ng = (a.N + 63) / 64;
+  const PackedLauncher launch = (ng >= 0 && ng < (int)packed_table.size()) ? packed_table[ng] : nullptr;
+  return launch ? launch(a, st) : -1;
 }

@@ -164,33 +164,37 @@ __global__ __launch_bounds__(64) void k_lis_attention_stream(std::conditional_t<
   }
 }
 
-template <int HD>
+template <int HD, bool TAP>
 static int launch_stream_t(const AttnArgs& a, hipStream_t st) {
   const int nkb = (a.N + 15) / 16, nkp = (nkb + 1) / 2;
   const size_t smem = 2 * 258 * 8 + (size_t)HD * AS_VSTRIDE * 2 + (size_t)2 * nkp * 64 * 4;
   const dim3 grid((unsigned)(a.B * a.H), (unsigned)nkb), block(64);
-  auto launch = [&](auto kernel) -> int {
-    if (smem > 64 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(kernel, grid, block, smem, st, a);
-    CHECK_LAUNCH();
-    return 0;
-  };
-  return a.tapped() ? launch(&k_lis_attention_stream<HD, true>) : launch(&k_lis_attention_stream<HD, false>);
+  if (smem > 64 * 1024) {
+    static P2vLdsGrant grant = {};
+    const hipError_t e = grant.ensure(reinterpret_cast<const void*>(&k_lis_attention_stream<HD, TAP>), (int)smem);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL((k_lis_attention_stream<HD, TAP>), grid, block, smem, st, a);
+  CHECK_LAUNCH();
+  return 0;
 }
+
+// the launchers, in the order the code object holds their kernels (p2vit_launch.h): flat index (head_dim / 16) * 2 + (untapped); null = head_dim not instantiated
+typedef int (*StreamLauncher)(const AttnArgs&, hipStream_t);
+constexpr int stream_index(int head_dim, bool tap) { return head_dim / 16 * 2 + (tap ? 0 : 1); }
+struct StreamAt {
+  template <int I> static constexpr StreamLauncher at() {
+    constexpr int HD = (I >> 1) * 16;
+    static_assert(stream_index(HD, !(I & 1)) == I, "decoded as the launcher encodes");
+    if constexpr (HD == 32 || HD == 48 || HD == 64 || HD == 80 || HD == 96 || HD == 128) return launch_stream_t<HD, !(I & 1)>;
+    else return nullptr;
+  }
+};
+static const auto stream_table = p2v_table<StreamLauncher, StreamAt, 18>();
 
 // tokens beyond p2v_max_tokens(head_dim), up to P2V_MAX_TOKENS_STREAMED
 int p2v_launch_attention_stream(const AttnArgs& a, int head_dim, hipStream_t st) {
   if (a.N > P2V_MAX_TOKENS_STREAMED || a.B * a.H <= 0) return -1;
-  switch (head_dim) {
-    case 32: return launch_stream_t<32>(a, st);
-    case 48: return launch_stream_t<48>(a, st);
-    case 64: return launch_stream_t<64>(a, st);
-    case 80: return launch_stream_t<80>(a, st);
-    case 96: return launch_stream_t<96>(a, st);
-    case 128: return launch_stream_t<128>(a, st);
-    default: return -1;
-  }
+  const StreamLauncher launch = (head_dim >= 0 && head_dim <= 128 && head_dim % 16 == 0) ? stream_table[stream_index(head_dim, a.tapped())] : nullptr;
+  return launch ? launch(a, st) : -1;
 }

@@ -4,9 +4,9 @@
 #include "p2vit_attn_lis.h"
 
 int p2v_launch_attention_wide(const AttnArgs& a, int head_dim, int nkb, hipStream_t st) {
-  if (head_dim == 48) { P2V_ATTN_CASES(48, 19, false) }
-  if (head_dim == 80) { P2V_ATTN_CASES(80, 19, false) }
-  if (head_dim == 96) { P2V_ATTN_CASES(96, 17, false) }
-  if (head_dim == 128) { P2V_ATTN_CASES(128, 12, false) }
+  if (head_dim == 48) return launch_attn_hd<48, 19, false>(a, nkb, st);
+  if (head_dim == 80) return launch_attn_hd<80, 19, false>(a, nkb, st);
+  if (head_dim == 96) return launch_attn_hd<96, 17, false>(a, nkb, st);
+  if (head_dim == 128) return launch_attn_hd<128, 12, false>(a, nkb, st);
   return -1;
 }

@@ -1,5 +1,6 @@
 // p2vit_gemm.hip -- tiled int8 MFMA GEMMs (stem / head, fp32-image patch embedding, the LDS-DMA layer GEMM) and their launcher.
 #include "p2vit_epilogue.h"
+#include "p2vit_launch.h"
 
 #ifdef P2V_DIAG
 unsigned long long* g_gemm_stamps = nullptr;
@@ -539,19 +540,52 @@ static int device_cus() {
   }
   return cus[dev];
 }
-// dynamic LDS (the GELU table) of a tiled-GEMM instantiation beyond what it has been granted so far on this device
-template <typename K>
-static bool grant_dynamic_lds(K kernel, int slot, int bytes) {
-  static int granted[16][8] = {{0}};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
-  if (dev >= 0 && bytes <= granted[dev][slot]) return true;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
+// The instantiations of the two GEMM kernels, in the order the code object holds them (p2vit_launch.h).
+// shape: 0 = 256-row tiles, packed int4 weights; 1 = 256 rows, int8; 2 = 128 rows, int4; 3 = 128 rows, int8.
+// k_gemm_dma: the two epilogues with a side buffer lead, for every shape (slot * 4 + shape); then, shape by shape, the other four (8 + shape * 4 + slot)
+typedef void (*GemmKernel)(GemmArgs);
+constexpr int kTiledLead[2] = {P2V_EPI_GELU_TAB, P2V_EPI_RESID_TAP};
+constexpr int kTiledRest[4] = {P2V_EPI_REQUANT, P2V_EPI_GELU, P2V_EPI_RESID_PRE, P2V_EPI_RESID};
+constexpr int tiled_gemm_index(int e, int shape) {      // -1: not an epilogue of the tiled kernel
+  if (p2v_slot(kTiledLead, e) >= 0) return p2v_slot(kTiledLead, e) * 4 + shape;
+  return p2v_slot(kTiledRest, e) < 0 ? -1 : 8 + shape * 4 + p2v_slot(kTiledRest, e);
+}
+struct TiledGemmAt {
+  template <int I> static constexpr GemmKernel at() {
+    constexpr int E = I < 8 ? kTiledLead[I / 4] : kTiledRest[I % 4], SHAPE = I < 8 ? I % 4 : I / 4 - 2;
+    static_assert(tiled_gemm_index(E, SHAPE) == I, "decoded as the launcher encodes");
+    return k_gemm_dma<E, !(SHAPE & 1), (SHAPE < 2 ? 4 : 2)>;
   }
-  if (dev >= 0) granted[dev][slot] = bytes;
-  return true;
+};
+static const auto tiled_gemm_table = p2v_table<GemmKernel, TiledGemmAt, 24>();
+// the GELU table rides in dynamic LDS: a grant record per GELU_TAB instantiation, held by a thunk that names its own kernel; indexed by shape
+template <int I>
+static hipError_t grant_gelu_tab_t(int bytes) {
+  static P2vLdsGrant grant = {};
+  return grant.ensure(reinterpret_cast<const void*>(TiledGemmAt::at<tiled_gemm_index(P2V_EPI_GELU_TAB, I)>()), bytes);
+}
+static hipError_t (*const gelu_tab_grant_table[4])(int) = {grant_gelu_tab_t<0>, grant_gelu_tab_t<1>, grant_gelu_tab_t<2>, grant_gelu_tab_t<3>};
+// k_gemm_i8: slot * 2 + (int8 weights)
+constexpr int kWideEpi[4] = {P2V_EPI_F32, P2V_EPI_EMBED_TAP, P2V_EPI_EMBED, P2V_EPI_HEAD};
+constexpr int wide_gemm_index(int e, bool w4) { return p2v_slot(kWideEpi, e) * 2 + (w4 ? 0 : 1); }
+struct WideGemmAt {
+  template <int I> static constexpr GemmKernel at() {
+    static_assert(wide_gemm_index(kWideEpi[I / 2], !(I & 1)) == I, "decoded as the launcher encodes");
+    return k_gemm_i8<kWideEpi[I / 2], !(I & 1)>;
+  }
+};
+static const auto wide_gemm_table = p2v_table<GemmKernel, WideGemmAt, 8>();
+
+// which k_gemm_dma epilogue a layer GEMM runs; -1: not one of the tiled kernel's
+static int tiled_gemm_epilogue(int epi, const GemmArgs& g, unsigned tab_bytes) {
+  switch (epi) {
+    case P2V_EPI_REQUANT: return P2V_EPI_REQUANT;
+    case P2V_EPI_GELU: return tab_bytes ? P2V_EPI_GELU_TAB : P2V_EPI_GELU;
+    case P2V_EPI_RESID:
+      if (g.out_codes) return P2V_EPI_RESID_TAP;      // the mid-code tap: the generic RESID chain whatever resid_tab says (same codes); tiled kernel only
+      return (g.ep.resid_tab && g_resid_pre) ? P2V_EPI_RESID_PRE : P2V_EPI_RESID;
+    default: return -1;
+  }
 }
 
 int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
@@ -571,73 +605,35 @@ int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
     const bool big = (g_gemm_tile == 256 || (g_gemm_tile == 0 && !g.w4 && tiles256 >= 2LL * device_cus()));
     const int tiles_m = big ? (g.M + 255) / 256 : (g.M + GBM - 1) / GBM;
     dim3 grid4(g.tiles_n * tiles_m), block4(big ? 512 : 256);
+    const int shape = (big ? 0 : 2) + (g.w4 ? 0 : 1);
     unsigned tab_bytes = (epi == P2V_EPI_GELU && g.ep.gelu.table) ? (unsigned)g.ep.gelu.cells * 8u : 0u;
     // static LDS of the GELU_TAB instantiations (ring + column constants) plus the table can pass the 64 KB a kernel gets by default
     // (1/scale = 256: 2111 cells = 16.5 KB): ask for the larger dynamic block once per process and device, or use the arithmetic epilogue
     if (tab_bytes) {
       const int stat = (big ? 3 * (256 + GBN) * GBK : 3 * DMA_STAGE_BYTES) + 2 * GBN * (int)sizeof(float);
       if (stat + (int)tab_bytes > 64 * 1024) {
-        bool ok;
-        if (big) ok = g.w4 ? grant_dynamic_lds(&k_gemm_dma<P2V_EPI_GELU_TAB, true, 4>, 0, (int)tab_bytes)
-                           : grant_dynamic_lds(&k_gemm_dma<P2V_EPI_GELU_TAB, false, 4>, 1, (int)tab_bytes);
-        else if (g.w4) ok = grant_dynamic_lds(&k_gemm_dma<P2V_EPI_GELU_TAB, true, 2>, 2, (int)tab_bytes);
-        else ok = grant_dynamic_lds(&k_gemm_dma<P2V_EPI_GELU_TAB, false, 2>, 4, (int)tab_bytes);
-        if (!ok) tab_bytes = 0;                   // arithmetic P2V_EPI_GELU kernel: same codes, no table
+        if (gelu_tab_grant_table[shape]((int)tab_bytes) != hipSuccess) {
+          (void)hipGetLastError();
+          tab_bytes = 0;                          // arithmetic P2V_EPI_GELU kernel: same codes, no table
+        }
       }
     }
-#define P2V_LAUNCH_TILED(KERNEL)                                                                                          \
-    switch (epi) {                                                                                                        \
-      case P2V_EPI_REQUANT: hipLaunchKernelGGL(KERNEL(P2V_EPI_REQUANT), grid4, block4, 0, st, g); break;                  \
-      case P2V_EPI_GELU:                                                                                                  \
-        if (tab_bytes) hipLaunchKernelGGL(KERNEL(P2V_EPI_GELU_TAB), grid4, block4, tab_bytes, st, g);                     \
-        else hipLaunchKernelGGL(KERNEL(P2V_EPI_GELU), grid4, block4, 0, st, g);                                           \
-        break;                                                                                                            \
-      case P2V_EPI_RESID:                                                                                                 \
-        if (g.ep.resid_tab && g_resid_pre) hipLaunchKernelGGL(KERNEL(P2V_EPI_RESID_PRE), grid4, block4, 0, st, g);        \
-        else hipLaunchKernelGGL(KERNEL(P2V_EPI_RESID), grid4, block4, 0, st, g);                                          \
-        break;                                                                                                            \
-      default: return -1;                                                                                                 \
-    }
-#define P2V_K_DMA3(E) (k_gemm_dma<E, false, 2>)
-#define P2V_K_DMA3P(E) (k_gemm_dma<E, true, 2>)
-#define P2V_K_DMA3L(E) (k_gemm_dma<E, false, 4>)
-#define P2V_K_DMA3PL(E) (k_gemm_dma<E, true, 4>)
-    if (epi == P2V_EPI_RESID && g.out_codes) {
-      // the mid-code tap: the generic RESID chain whatever resid_tab says (same codes); tiled kernel only
-      if ((long long)g.M * g.ldo >= (1LL << 32)) return -1;
-      if (big) {
-        if (g.w4) hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, true, 4>), grid4, block4, 0, st, g);
-        else hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, false, 4>), grid4, block4, 0, st, g);
-      } else if (g.w4) hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, true, 2>), grid4, block4, 0, st, g);
-      else hipLaunchKernelGGL((k_gemm_dma<P2V_EPI_RESID_TAP, false, 2>), grid4, block4, 0, st, g);
-    } else {
-    if (big) {
-      if (g.w4) { P2V_LAUNCH_TILED(P2V_K_DMA3PL) }
-      else { P2V_LAUNCH_TILED(P2V_K_DMA3L) }
-    } else if (g.w4) { P2V_LAUNCH_TILED(P2V_K_DMA3P) }          // packed int4 weights: the LDS-DMA kernel only
-    else { P2V_LAUNCH_TILED(P2V_K_DMA3) }
-    }
-#undef P2V_LAUNCH_TILED
+    const int e = tiled_gemm_epilogue(epi, g, tab_bytes);
+    if (e < 0) return -1;
+    if (e == P2V_EPI_RESID_TAP && (long long)g.M * g.ldo >= (1LL << 32)) return -1;
+    hipLaunchKernelGGL(tiled_gemm_table[tiled_gemm_index(e, shape)], grid4, block4, tab_bytes, st, g);
     CHECK_LAUNCH();
     return 0;
   }
   // EMBED / HEAD: one launch each per forward; F32: a tap of p2v_forward_linear_taps; 8-wave shape (64x32 wave tiles, <= 128 VGPRs)
   const int tiles_m = (g.M + GBM - 1) / GBM;
   dim3 grid(g.tiles_n * tiles_m), block(512);
-  if (epi == P2V_EPI_F32) {
-    if (g.w4) hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_F32, true>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_F32, false>), grid, block, 0, st, g);
-  } else if (epi == P2V_EPI_EMBED && g.out_codes) {      // the stem's mid-code taps: both planes or neither
+  int e = epi;
+  if (epi == P2V_EPI_EMBED && g.out_codes) {      // the stem's mid-code taps: both planes or neither
     if (!g.out_codes2) return -1;
-    if (g.w4) hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED_TAP, true>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED_TAP, false>), grid, block, 0, st, g);
-  } else if (epi == P2V_EPI_EMBED) {
-    if (g.w4) hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED, true>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_EMBED, false>), grid, block, 0, st, g);
-  } else {
-    if (g.w4) hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_HEAD, true>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_i8<P2V_EPI_HEAD, false>), grid, block, 0, st, g);
+    e = P2V_EPI_EMBED_TAP;
   }
+  hipLaunchKernelGGL(wide_gemm_table[wide_gemm_index(e, g.w4 != 0)], grid, block, 0, st, g);
   CHECK_LAUNCH();
   return 0;
 }

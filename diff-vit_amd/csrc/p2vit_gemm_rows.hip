@@ -1,5 +1,6 @@
 // p2vit_gemm_rows.hip -- int8 MFMA GEMM for a FEW activation rows (the class-token rows of the last ViT block: M = images of a slice).
 #include "p2vit_epilogue.h"
+#include "p2vit_launch.h"
 
 // ---------------------------------------------------------------------------------------------------
 // K1r: the layer GEMM when M is small.  The tiled kernel (k_gemm_dma) gets its parallelism from M: at M = 68 it is one or two
@@ -125,6 +126,25 @@ __global__ __launch_bounds__(512) void k_gemm_rows(GemmArgs g) {
 extern int g_resid_pre;
 int g_gemm_rows = 0;      // P2V_GEMM_ROWS: 0 = the row kernel where the forward asks for it (class rows of the last block), 1 = wherever it applies, 2 = never
 
+// the instantiations of k_gemm_rows, in the order the code object holds them (p2vit_launch.h): (int8 weights) * 5 + slot
+typedef void (*GemmRowsKernel)(GemmArgs);
+constexpr int kRowsEpi[5] = {P2V_EPI_REQUANT, P2V_EPI_GELU_TAB, P2V_EPI_GELU, P2V_EPI_RESID_PRE, P2V_EPI_RESID};
+constexpr int gemm_rows_index(int e, bool w4) { return (w4 ? 0 : 5) + p2v_slot(kRowsEpi, e); }
+struct GemmRowsAt {
+  template <int I> static constexpr GemmRowsKernel at() {
+    static_assert(gemm_rows_index(kRowsEpi[I % 5], I < 5) == I, "decoded as the launcher encodes");
+    return k_gemm_rows<kRowsEpi[I % 5], (I < 5)>;
+  }
+};
+static const auto gemm_rows_table = p2v_table<GemmRowsKernel, GemmRowsAt, 10>();
+
+// which epilogue of the row kernel a REQUANT / GELU / RESID layer runs
+static int gemm_rows_epilogue(int epi, const GemmArgs& g, unsigned tab_bytes) {
+  if (epi == P2V_EPI_REQUANT) return P2V_EPI_REQUANT;
+  if (epi == P2V_EPI_GELU) return tab_bytes ? P2V_EPI_GELU_TAB : P2V_EPI_GELU;
+  return (g.ep.resid_tab && g_resid_pre) ? P2V_EPI_RESID_PRE : P2V_EPI_RESID;
+}
+
 // -3: not a shape / epilogue of the row kernel (the caller runs the tiled kernel)
 int p2v_launch_gemm_rows(int epi, const GemmArgs& g0, hipStream_t st) {
   if (epi != P2V_EPI_REQUANT && epi != P2V_EPI_GELU && epi != P2V_EPI_RESID) return -3;
@@ -139,21 +159,7 @@ int p2v_launch_gemm_rows(int epi, const GemmArgs& g0, hipStream_t st) {
   // kernel gets by default takes the arithmetic epilogue: same codes
   unsigned tab_bytes = (epi == P2V_EPI_GELU && g.ep.gelu.table) ? (unsigned)g.ep.gelu.cells * 8u : 0u;
   if (GR_SLOTS * GR_SLOT_BYTES + 2 * GBN * (int)sizeof(float) + (int)tab_bytes > 64 * 1024) tab_bytes = 0;
-#define P2V_LAUNCH_ROWS(W4_)                                                                                                \
-  switch (epi) {                                                                                                            \
-    case P2V_EPI_REQUANT: hipLaunchKernelGGL((k_gemm_rows<P2V_EPI_REQUANT, W4_>), grid, block, 0, st, g); break;            \
-    case P2V_EPI_GELU:                                                                                                      \
-      if (tab_bytes) hipLaunchKernelGGL((k_gemm_rows<P2V_EPI_GELU_TAB, W4_>), grid, block, tab_bytes, st, g);               \
-      else hipLaunchKernelGGL((k_gemm_rows<P2V_EPI_GELU, W4_>), grid, block, 0, st, g);                                     \
-      break;                                                                                                                \
-    default:                                                                                                                \
-      if (g.ep.resid_tab && g_resid_pre) hipLaunchKernelGGL((k_gemm_rows<P2V_EPI_RESID_PRE, W4_>), grid, block, 0, st, g);  \
-      else hipLaunchKernelGGL((k_gemm_rows<P2V_EPI_RESID, W4_>), grid, block, 0, st, g);                                    \
-      break;                                                                                                                \
-  }
-  if (g.w4) { P2V_LAUNCH_ROWS(true) }
-  else { P2V_LAUNCH_ROWS(false) }
-#undef P2V_LAUNCH_ROWS
+  hipLaunchKernelGGL(gemm_rows_table[gemm_rows_index(gemm_rows_epilogue(epi, g, tab_bytes), g.w4 != 0)], grid, block, tab_bytes, st, g);
   CHECK_LAUNCH();
   return 0;
 }

@@ -1,5 +1,6 @@
 // p2vit_ln.hip -- integer LayerNorm (stand-alone) and the fused LayerNorm + GEMM kernels, with their launchers.
 #include "p2vit_ln_row.h"
+#include "p2vit_launch.h"
 
 // ---------------------------------------------------------------------------------------------------
 // K2: integer LayerNorm (QIntLayerNorm mode 'int', layers.py:255-289) + /channel_scale + qact0 clamp
@@ -681,31 +682,36 @@ bool p2v_ln_gemm_supported(int epi, int C, int N, int table_cells) {
   return ln_gemm_lds(C, N, ((C + GBK - 1) / GBK + 1) / 2, table_cells).total <= 80 * 1024;     // two workgroups per CU
 }
 template <int EPI, int KT, int VER, bool W4>
-static int launch_ln_gemm_t2(const LnArgs& a, const GemmArgs& g, int cells, hipStream_t st) {
+static int launch_ln_gemm_t(const LnArgs& a, const GemmArgs& g, int cells, hipStream_t st) {
+  // VER 1: the 4-wave kernel; 2 / 3: k_ln_gemm2 with one / two wave groups
+  constexpr auto kernel = [] {
+    if constexpr (VER == 1) return &k_ln_gemm<EPI, KT, W4>;
+    else return &k_ln_gemm2<EPI, KT, VER - 1, W4>;
+  }();
   const int smem = ln_gemm_lds(a.C, g.N, (KT + 1) / 2, cells).total;
-  static int granted[16] = {0};                 // per device: the dynamic LDS size this instantiation has been allowed so far
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;
-  const void* fn;
-  if constexpr (VER == 3) fn = reinterpret_cast<const void*>(&k_ln_gemm2<EPI, KT, 2, W4>);
-  else if constexpr (VER == 2) fn = reinterpret_cast<const void*>(&k_ln_gemm2<EPI, KT, 1, W4>);
-  else fn = reinterpret_cast<const void*>(&k_ln_gemm<EPI, KT, W4>);
-  if (dev < 0 || smem > granted[dev]) {         // (a racing second thread only repeats the call)
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return (int)e;
-    if (dev >= 0) granted[dev] = smem;
-  }
+  static P2vLdsGrant grant = {};
+  const hipError_t e = grant.ensure(reinterpret_cast<const void*>(kernel), smem);
+  if (e != hipSuccess) return (int)e;
   const dim3 grid((unsigned)((g.M + LG_BM - 1) / LG_BM));
-  if constexpr (VER == 3) hipLaunchKernelGGL((k_ln_gemm2<EPI, KT, 2, W4>), grid, dim3(512), (unsigned)smem, st, a, g);
-  else if constexpr (VER == 2) hipLaunchKernelGGL((k_ln_gemm2<EPI, KT, 1, W4>), grid, dim3(256), (unsigned)smem, st, a, g);
-  else hipLaunchKernelGGL((k_ln_gemm<EPI, KT, W4>), grid, dim3(256), (unsigned)smem, st, a, g);
+  hipLaunchKernelGGL(kernel, grid, dim3(VER == 3 ? 512 : 256), (unsigned)smem, st, a, g);
   CHECK_LAUNCH();
   return 0;
 }
-template <int EPI, int KT, int VER>
-static int launch_ln_gemm_t(const LnArgs& a, const GemmArgs& g, int cells, hipStream_t st) {
-  return g.w4 ? launch_ln_gemm_t2<EPI, KT, VER, true>(a, g, cells, st) : launch_ln_gemm_t2<EPI, KT, VER, false>(a, g, cells, st);
-}
+// the fused launchers, in the order the code object holds their kernels (p2vit_launch.h): flat index
+// (((3 - version) * 3 + slot) * 6 + kt - 1) * 2 + (int8 weights); null = not instantiated (versions 2 and 3 serve REQUANT and the table GELU only)
+typedef int (*LnGemmLauncher)(const LnArgs&, const GemmArgs&, int, hipStream_t);
+constexpr int kLnGemmEpi[3] = {P2V_EPI_REQUANT, P2V_EPI_GELU_TAB, P2V_EPI_GELU};
+constexpr int ln_gemm_index(int e, int ver, int kt, bool w4) { return (((3 - ver) * 3 + p2v_slot(kLnGemmEpi, e)) * 6 + kt - 1) * 2 + (w4 ? 0 : 1); }
+struct LnGemmAt {
+  template <int I> static constexpr LnGemmLauncher at() {
+    constexpr int E = kLnGemmEpi[I / 12 % 3], VER = 3 - I / 36;
+    static_assert(ln_gemm_index(E, VER, I / 2 % 6 + 1, !(I & 1)) == I, "decoded as the launcher encodes");
+    if constexpr (E != P2V_EPI_GELU || VER == 1) return launch_ln_gemm_t<E, I / 2 % 6 + 1, VER, !(I & 1)>;
+    else return nullptr;
+  }
+};
+static const auto ln_gemm_table = p2v_table<LnGemmLauncher, LnGemmAt, 108>();
+
 int g_ln_gemm_ver = 2;    // P2V_LN_GEMM_V=1: the 4-wave kernel of round 2 for every launch (A/B runs; same results)
 // g0.W must point to the FRAGMENT-ORDER copy of the weights (p2v_linear.w_frag; packed two codes per byte when g0.w4)
 int p2v_launch_ln_gemm(int epi, const LnArgs& a_, const GemmArgs& g0, hipStream_t st) {
@@ -721,29 +727,28 @@ int p2v_launch_ln_gemm(int epi, const LnArgs& a_, const GemmArgs& g0, hipStream_
   g.stamps = g_gemm_stamps;
 #endif
   const int kt = (a.C + GBK - 1) / GBK;
-#define P2V_LG(EPI_, VER_)                                                        \
-  switch (kt) {                                                                   \
-    case 1: return launch_ln_gemm_t<EPI_, 1, VER_>(a, g, cells, st);              \
-    case 2: return launch_ln_gemm_t<EPI_, 2, VER_>(a, g, cells, st);              \
-    case 3: return launch_ln_gemm_t<EPI_, 3, VER_>(a, g, cells, st);              \
-    case 4: return launch_ln_gemm_t<EPI_, 4, VER_>(a, g, cells, st);              \
-    case 5: return launch_ln_gemm_t<EPI_, 5, VER_>(a, g, cells, st);              \
-    default: return launch_ln_gemm_t<EPI_, 6, VER_>(a, g, cells, st);             \
-  }
+  const int e = epi == P2V_EPI_REQUANT ? P2V_EPI_REQUANT : (cells ? P2V_EPI_GELU_TAB : P2V_EPI_GELU);
   // the dense 8-wave kernel: REQUANT and table GELU without activation taps; everything else runs the 4-wave kernel
-  if (g_ln_gemm_ver == 3 && !g.ep.tap_out) {
-    if (epi == P2V_EPI_REQUANT) { P2V_LG(P2V_EPI_REQUANT, 3) }
-    if (cells) { P2V_LG(P2V_EPI_GELU_TAB, 3) }
-  }
-  if (g_ln_gemm_ver == 2 && !g.ep.tap_out) {
-    if (epi == P2V_EPI_REQUANT) { P2V_LG(P2V_EPI_REQUANT, 2) }
-    if (cells) { P2V_LG(P2V_EPI_GELU_TAB, 2) }
-  }
-  if (epi == P2V_EPI_REQUANT) { P2V_LG(P2V_EPI_REQUANT, 1) }
-  if (cells) { P2V_LG(P2V_EPI_GELU_TAB, 1) }
-  P2V_LG(P2V_EPI_GELU, 1)
-#undef P2V_LG
+  const int ver = ((g_ln_gemm_ver == 3 || g_ln_gemm_ver == 2) && !g.ep.tap_out && e != P2V_EPI_GELU) ? g_ln_gemm_ver : 1;
+  const LnGemmLauncher launch = ln_gemm_table[ln_gemm_index(e, ver, kt >= 1 && kt <= 5 ? kt : 6, g.w4 != 0)];
+  return launch ? launch(a, g, cells, st) : -3;
 }
+
+// the instantiations of k_int_layernorm, in the order the code object holds them (p2vit_launch.h): flat index
+// (((untapped) * 2 + (row per half wave)) * 9 + nch) * 2 + (constants folded by the kernel).  A row per wave (64 lanes) holds 2..8 groups of
+// 256 channels, a row per half wave 1..3 groups of 128; null = not instantiated
+typedef void (*LnKernel)(LnArgs);
+constexpr int ln_index(bool tap, bool half, int nch, bool pre) { return (((tap ? 0 : 2) + (half ? 1 : 0)) * 9 + nch) * 2 + (pre ? 0 : 1); }
+struct LnAt {
+  template <int I> static constexpr LnKernel at() {
+    constexpr bool HALF = (I / 18 & 1) != 0;
+    constexpr int NCH = I / 2 % 9;
+    static_assert(ln_index(I < 36, HALF, NCH, !(I & 1)) == I, "decoded as the launcher encodes");
+    if constexpr (HALF ? (NCH >= 1 && NCH <= 3) : (NCH >= 2 && NCH <= 8)) return k_int_layernorm<NCH, HALF ? 32 : 64, !(I & 1), (I < 36)>;
+    else return nullptr;
+  }
+};
+static const auto ln_table = p2v_table<LnKernel, LnAt, 72>();
 
 int g_ln_rows = 4;        // P2V_LN_ROWS: consecutive rows per half wave
 int p2v_launch_layernorm(const LnArgs& a_, hipStream_t st) {
@@ -759,38 +764,10 @@ int p2v_launch_layernorm(const LnArgs& a_, hipStream_t st) {
   const int nch = wide ? (a.C + 255) / 256 : (a.C + 127) / 128;
   const int rows_per_block = (wide ? 4 : 8) * LN_ROWS;
   dim3 grid((unsigned)((a.rows + rows_per_block - 1) / rows_per_block)), block(256);
-  if (a.tap_out) {      // the value tap (p2v_int_layernorm_tap, the FULL stage set of p2v_forward_ddv_ex): same grid, same codes
-#define P2V_LN_TAP(N_, L_) case N_: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<N_, L_, true, true>), grid, block, 0, st, a); \
-                                    else hipLaunchKernelGGL((k_int_layernorm<N_, L_, false, true>), grid, block, 0, st, a); break;
-    if (wide) {
-      switch (nch) { P2V_LN_TAP(2, 64) P2V_LN_TAP(3, 64) P2V_LN_TAP(4, 64) P2V_LN_TAP(5, 64) P2V_LN_TAP(6, 64) P2V_LN_TAP(7, 64) P2V_LN_TAP(8, 64) default: return -1; }
-    } else {
-      switch (nch) { P2V_LN_TAP(1, 32) P2V_LN_TAP(2, 32) P2V_LN_TAP(3, 32) default: return -1; }
-    }
-#undef P2V_LN_TAP
-    CHECK_LAUNCH();
-    return 0;
-  }
-  if (wide) {
-    switch (nch) {
-      case 2: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<2, 64, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<2, 64, false>), grid, block, 0, st, a); break;
-      case 3: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<3, 64, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<3, 64, false>), grid, block, 0, st, a); break;
-      case 4: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<4, 64, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<4, 64, false>), grid, block, 0, st, a); break;
-      case 5: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<5, 64, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<5, 64, false>), grid, block, 0, st, a); break;
-      case 6: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<6, 64, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<6, 64, false>), grid, block, 0, st, a); break;
-      case 7: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<7, 64, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<7, 64, false>), grid, block, 0, st, a); break;
-      case 8: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<8, 64, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<8, 64, false>), grid, block, 0, st, a); break;
-      default: return -1;
-    }
-  } else {
-    switch (nch) {
-      case 1: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<1, 32, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<1, 32, false>), grid, block, 0, st, a); break;
-      case 2: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<2, 32, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<2, 32, false>), grid, block, 0, st, a); break;
-      case 3: if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm<3, 32, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((k_int_layernorm<3, 32, false>), grid, block, 0, st, a); break;
-      default: return -1;
-    }
-  }
+  // tap_out: the value tap (p2v_int_layernorm_tap, the FULL stage set of p2v_forward_ddv_ex): same grid, same codes
+  const LnKernel kernel = (nch >= 0 && nch <= 8) ? ln_table[ln_index(a.tap_out != nullptr, !wide, nch, a.pre.gm != nullptr)] : nullptr;
+  if (!kernel) return -1;
+  hipLaunchKernelGGL(kernel, grid, block, 0, st, a);
   CHECK_LAUNCH();
   return 0;
 }
-

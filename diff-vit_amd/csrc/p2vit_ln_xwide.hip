@@ -140,13 +140,10 @@ int p2v_launch_layernorm_xwide(const LnArgs& a_, hipStream_t st) {
   const long long per = (a.rows + 511) / 512;
   a.rows_per_half = (int)(per > 8 ? per : 8);
   dim3 grid((unsigned)((a.rows + a.rows_per_half - 1) / a.rows_per_half)), block(LX_LANES);
-  if (a.C <= 3072) {
-    if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm_xwide<3, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_int_layernorm_xwide<3, false>), grid, block, 0, st, a);
-  } else {
-    if (a.pre.gm) hipLaunchKernelGGL((k_int_layernorm_xwide<4, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_int_layernorm_xwide<4, false>), grid, block, 0, st, a);
-  }
+  // [groups of 1024 channels - 3][constants folded by the kernel]
+  static void (*const table[2][2])(LnArgs) = {{k_int_layernorm_xwide<3, true>, k_int_layernorm_xwide<3, false>},
+                                              {k_int_layernorm_xwide<4, true>, k_int_layernorm_xwide<4, false>}};
+  hipLaunchKernelGGL(table[a.C <= 3072 ? 0 : 1][a.pre.gm ? 0 : 1], grid, block, 0, st, a);
   CHECK_LAUNCH();
   return 0;
 }

@@ -282,15 +282,12 @@ int p2v_launch_u8_patchify(const uint8_t* img, int B, int C, int H, int W, int P
   const unsigned blocks = (unsigned)B * gh * nseg;
   const size_t lds = (size_t)C * 256 + (size_t)P * Q * P * C;
   const bool vec = k_pad % 16 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-#define U8P(PT, L, V) hipLaunchKernelGGL((k_u8_patchify<PT, L, V>), dim3(blocks), dim3(256), lds, st, img, C, H, W, P, lut, out, k_pad, Q)
-#define U8P_L(PT, V) do { if (nhwc) U8P(PT, 1, V); else U8P(PT, 0, V); } while (0)
-  if (!vec) U8P_L(0, 0);
-  else if (P == 16) U8P_L(16, 1);
-  else if (P == 8) U8P_L(8, 1);
-  else if (P == 4) U8P_L(4, 1);
-  else U8P_L(0, 1);
-#undef U8P_L
-#undef U8P
+  // [dword stores, then the 16-byte stores with P = 16 / 8 / 4 / any at compile time][NCHW]
+  static void (*const table[5][2])(const uint8_t*, int, int, int, int, const int8_t*, int8_t*, int, int) = {
+      {k_u8_patchify<0, 1, 0>, k_u8_patchify<0, 0, 0>},   {k_u8_patchify<16, 1, 1>, k_u8_patchify<16, 0, 1>}, {k_u8_patchify<8, 1, 1>, k_u8_patchify<8, 0, 1>},
+      {k_u8_patchify<4, 1, 1>, k_u8_patchify<4, 0, 1>},   {k_u8_patchify<0, 1, 1>, k_u8_patchify<0, 0, 1>}};
+  const int form = !vec ? 0 : (P == 16 ? 1 : (P == 8 ? 2 : (P == 4 ? 3 : 4)));
+  hipLaunchKernelGGL(table[form][nhwc ? 0 : 1], dim3(blocks), dim3(256), lds, st, img, C, H, W, P, lut, out, k_pad, Q);
   CHECK_LAUNCH();
   return 0;
 }

@@ -344,40 +344,28 @@ __global__ __launch_bounds__(256, 2) void k_window_attention_wide(std::condition
   }
 }
 
-template <int WS>
+template <int WS, bool TAP>
 static int launch_winattn_wide_t(const WinAttnArgs& a, hipStream_t st) {
   constexpr size_t smem = WinWide<WS>::SMEM;
   const int hgroups = (a.H + 3) / 4;
   const dim3 grid((unsigned)(a.B * a.wa.n_windows * hgroups));
-#define P2V_WW_LAUNCH(TAP_)                                                                                                  \
-  do {                                                                                                                       \
-    if (smem > 64 * 1024) {          /* 12 x 12: beyond the default dynamic LDS limit */                                     \
-      static bool granted[16] = {false};                                                                                     \
-      int dev = 0;                                                                                                           \
-      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = -1;                                                \
-      if (dev < 0 || !granted[dev]) {                                                                                        \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_window_attention_wide<WS, TAP_>),                \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                           \
-        if (e != hipSuccess) return (int)e;                                                                                  \
-        if (dev >= 0) granted[dev] = true;                                                                                   \
-      }                                                                                                                      \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((k_window_attention_wide<WS, TAP_>), grid, dim3(256), smem, st, a);                                   \
-  } while (0)
-  if (a.tapped()) P2V_WW_LAUNCH(true);
-  else P2V_WW_LAUNCH(false);
-#undef P2V_WW_LAUNCH
+  if (smem > 64 * 1024) {          // 12 x 12: beyond the default dynamic LDS limit
+    static P2vLdsGrant grant = {};
+    const hipError_t e = grant.ensure(reinterpret_cast<const void*>(&k_window_attention_wide<WS, TAP>), (int)smem);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL((k_window_attention_wide<WS, TAP>), grid, dim3(256), smem, st, a);
   CHECK_LAUNCH();
   return 0;
 }
 
 // windows of 9 x 9 ... 12 x 12 (p2v_launch_window_attention routes them here); -1: no instantiation
 int p2v_launch_window_attention_wide(const WinAttnArgs& a, hipStream_t st) {
-  switch (a.wa.ws) {
-    case 9: return launch_winattn_wide_t<9>(a, st);
-    case 10: return launch_winattn_wide_t<10>(a, st);
-    case 11: return launch_winattn_wide_t<11>(a, st);
-    case 12: return launch_winattn_wide_t<12>(a, st);
-    default: return -1;
-  }
+  // [ws - 9][untapped]
+  static int (*const table[4][2])(const WinAttnArgs&, hipStream_t) = {{launch_winattn_wide_t<9, true>, launch_winattn_wide_t<9, false>},
+                                                                      {launch_winattn_wide_t<10, true>, launch_winattn_wide_t<10, false>},
+                                                                      {launch_winattn_wide_t<11, true>, launch_winattn_wide_t<11, false>},
+                                                                      {launch_winattn_wide_t<12, true>, launch_winattn_wide_t<12, false>}};
+  if (a.wa.ws < 9 || a.wa.ws > 12) return -1;
+  return table[a.wa.ws - 9][a.tapped() ? 0 : 1](a, st);
 }

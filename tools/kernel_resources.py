@@ -1,8 +1,12 @@
 """VGPRs / scratch / static LDS of every kernel in a built library, read from the code-object notes (llvm-readelf --notes on the unbundled
-gfx950 code objects; no GPU needed).  The library holds one offload bundle per translation unit.
+gfx950 code objects, llvm-readobj --notes where the ROCm install has no llvm-readelf; no GPU needed).  The library holds one offload bundle
+per translation unit.
 usage: python tools/kernel_resources.py [lib.so] [substring ...]          table (substring `scratch`: only kernels with a private segment)
-       python tools/kernel_resources.py [lib.so] --isa <substring> [out]   disassembly of the first matching kernel + instruction-class counts"""
-import collections, os, re, struct, subprocess, sys, tempfile
+       python tools/kernel_resources.py [lib.so] --isa <substring> [out]   disassembly of the first matching kernel + instruction-class counts
+       python tools/kernel_resources.py [lib.so] --digest                  one line per kernel, sorted by mangled name: resources, code size,
+                                                                           SHA-256 of the code bytes and of the 64-byte descriptor (two builds
+                                                                           hold the same device code when their listings are equal)"""
+import collections, hashlib, os, re, struct, subprocess, sys, tempfile
 
 LLVM = '/opt/rocm/lib/llvm/bin/'
 
@@ -24,12 +28,16 @@ def code_objects(lib):
         i += 24
 
 
-def rows_of(co):
+def notes_of(co):
+    tool = 'llvm-readelf' if os.path.exists(LLVM + 'llvm-readelf') else 'llvm-readobj'      # the same metadata text from either
     with tempfile.NamedTemporaryFile(suffix='.co') as f:
         f.write(co); f.flush()
-        notes = subprocess.run([LLVM + 'llvm-readelf', '--notes', f.name], capture_output=True, text=True).stdout
+        return subprocess.run([LLVM + tool, '--notes', f.name], capture_output=True, text=True, check=True).stdout
+
+
+def rows_of(co):
     rows = []
-    for b in notes.split('- .agpr_count')[1:]:
+    for b in notes_of(co).split('- .agpr_count')[1:]:
         g = lambda k: re.search(r'\.%s:\s+(\S+)' % k, b).group(1)
         rows.append((g('name'), int(g('vgpr_count')), int(g('private_segment_fixed_size')), int(g('group_segment_fixed_size'))))
     return rows
@@ -60,12 +68,49 @@ def isa(cos, pat, out_path):
     print('no kernel matches', pat)
 
 
+def symbols_of(co):
+    """name -> (bytes of the symbol) for every sized symbol of an ELF64 code object, through the section that holds its address"""
+    shoff, = struct.unpack_from('<Q', co, 0x28)
+    shentsize, shnum = struct.unpack_from('<HH', co, 0x3A)
+    secs = [struct.unpack_from('<IIQQQQIIQQ', co, shoff + i * shentsize) for i in range(shnum)]
+    tabs = [x for x in secs if x[1] == 2] or [x for x in secs if x[1] == 11]                # SHT_SYMTAB, else SHT_DYNSYM
+    out = {}
+    for tab in tabs:
+        strtab = secs[tab[6]]
+        for o in range(tab[4], tab[4] + tab[5], 24):
+            name, _, _, shndx, value, size = struct.unpack_from('<IBBHQQ', co, o)
+            if not size or not 0 < shndx < shnum or secs[shndx][1] == 8:                    # SHT_NOBITS holds no bytes
+                continue
+            a = strtab[4] + name
+            pos = value - secs[shndx][3] + secs[shndx][4]
+            out[co[a:co.index(b'\0', a)].decode()] = co[pos:pos + size]
+    return out
+
+
+def digest(cos):
+    lines = []
+    for co in cos:
+        syms = symbols_of(co)
+        for b in notes_of(co).split('- .agpr_count:')[1:]:
+            b = '    .agpr_count:' + b
+            g = lambda k: re.search(r'^    \.%s:\s+(\S+)' % k, b, re.M).group(1)                 # kernel-level keys (arguments are nested deeper)
+            name = g('name')
+            code, kd = syms[name], syms[g('symbol')]
+            assert len(kd) == 64, (name, len(kd))
+            lines.append('%s vgpr %s sgpr %s agpr %s private %s group %s kernarg %s code %d %s kd %s' % (
+                name, g('vgpr_count'), g('sgpr_count'), g('agpr_count'), g('private_segment_fixed_size'), g('group_segment_fixed_size'),
+                g('kernarg_segment_size'), len(code), hashlib.sha256(code).hexdigest(), hashlib.sha256(kd).hexdigest()))
+    print('\n'.join(sorted(lines)))
+
+
 def main():
     args = sys.argv[1:]
     lib = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'diff-vit_amd', 'csrc', 'libp2vit_hip.so')
     if args and args[0].endswith('.so'):
         lib = args.pop(0)
     cos = code_objects(lib)
+    if args and args[0] == '--digest':
+        return digest(cos)
     if args and args[0] == '--isa':
         return isa(cos, args[1], args[2] if len(args) > 2 else None)
     print('vgpr scratch lds  kernel')
@@ -77,4 +122,5 @@ def main():
                 print('%4d %7d %6d  %s' % (r[1], r[2], r[3], d))
 
 
-main()
+if __name__ == '__main__':
+    main()
