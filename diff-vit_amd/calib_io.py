@@ -65,14 +65,26 @@ def save_plan(path, model):
     import json
     import numpy as np
     kind = 'swin' if 'depths' in model.arch else 'vit'
+    cfg = getattr(model, 'cfg', None)
     out = {'meta': np.array(json.dumps({'kind': kind, 'arch': model.arch, 'in_chans': model.in_chans, 'format': 1,
-                                        'input_quant': bool(getattr(model, 'input_quant', True))}))}
+                                        'input_quant': bool(getattr(model, 'input_quant', True)),
+                                        'int_norm': bool(getattr(cfg, 'INT_NORM', True)), 'int_softmax': bool(getattr(cfg, 'INT_SOFTMAX', True)),
+                                        'ln_eps': float(getattr(getattr(model, 'norm', None), 'eps', 1e-6))}))}
     for k, v in flatten(model.export_calib()).items():
         out['calib/' + k] = v.detach().float().cpu().numpy()
     for k, v in model.state_dict().items():
         if v.dtype == torch.float32:
             out['weight/' + k] = v.detach().cpu().numpy()
     np.savez_compressed(path, **out)
+
+
+def plan_flags(path):
+    """(int_norm, int_softmax) of a plan file: Config(ptf, lis) of the model it was saved from; files written before the keys existed hold
+    the (True, True) configuration."""
+    import json
+    import numpy as np
+    meta = json.loads(str(np.load(path, allow_pickle=False)['meta']))
+    return bool(meta.get('int_norm', True)), bool(meta.get('int_softmax', True))
 
 
 def load_plan(path, device='cuda', bits=8):
@@ -93,4 +105,6 @@ def load_plan(path, device='cuda', bits=8):
         return SwinPlan(arch, sd, calib, device=device, in_chans=meta['in_chans'], bits=bits)
     from .plan import FrozenPlan
     # input_quant False = the reference's vit_large factory (vit_fquant.py:925); files written before the key existed are input_quant models
-    return FrozenPlan(arch, sd, calib, device=device, in_chans=meta['in_chans'], input_quant=bool(meta.get('input_quant', True)))
+    return FrozenPlan(arch, sd, calib, device=device, in_chans=meta['in_chans'], input_quant=bool(meta.get('input_quant', True)),
+                      int_norm=bool(meta.get('int_norm', True)), int_softmax=bool(meta.get('int_softmax', True)),
+                      ln_eps=float(meta.get('ln_eps', 1e-6)))

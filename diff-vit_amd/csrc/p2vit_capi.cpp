@@ -102,6 +102,11 @@ struct p2v_plan {
   std::vector<const float*> resid_tab;
   std::vector<float*> resid_buf;
   int device = -1;                  // the device that owns the folded constants (= the device of the caller's arrays)
+  // Config(ptf=False) / Config(lis=False): float LayerNorm and table softmax (p2v_plan_set_float_ops / _float_block / _float_head)
+  bool float_norm = false, float_softmax = false, fhead_set = false;
+  std::vector<p2v_float_block> fblocks;
+  std::vector<char> fblock_set;
+  p2v_float_ln final_fln = {};
   ~p2v_plan() {
     int prev = -1;
     const bool sw = device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device && hipSetDevice(device) == hipSuccess;
@@ -236,6 +241,8 @@ int p2v_plan_create(const p2v_model_desc* desc, p2v_plan** out) {
   p->resid_buf.assign(d.depth, nullptr);
   p->embed_set = p->head_set = false;
   p->cls_codes = nullptr;
+  p->fblocks.resize(d.depth);
+  p->fblock_set.assign(d.depth, 0);
   *out = p;
   return P2V_OK;
 }
@@ -662,8 +669,20 @@ struct Fwd {
   // QIntLayerNorm of `rows` rows of x -> QLinear -> `out`: one fused launch where the kernel covers the shape and the layer has fragment-order
   // weights (the LayerNorm codes then stay in LDS; parity runs read the workspace, so for them the kernel writes them too), else the
   // LayerNorm into LN and the GEMM from there
-  int ln_linear(int k_fused, int k_gemm, int epi, long long stride, int rows, const p2v_ln& norm, const p2v_linear& lin, const p2v_epilogue& e, int N,
-                int8_t* out, bool few) {
+  // float LayerNorm of `rows` rows of x (pitch `stride`) into `out` (pitch D); vals: the fp32 tap or null
+  int float_layernorm(const p2v_float_ln& f, long long stride, long long rows, int8_t* out, float* vals) {
+    const FloatLnArgs a{X, stride, rows, D, (double)f.s_in, (double)f.eps, f.gamma, f.beta, f.g, out, D, vals};
+    return step(P2V_K_LAYERNORM, [&] { return launch_rc(p2v_launch_float_layernorm(a, st), "float_layernorm"); });
+  }
+  // fnorm: the plan's float LayerNorm in this place, or null (QIntLayerNorm mode 'int')
+  int ln_linear(int k_fused, int k_gemm, int epi, long long stride, int rows, const p2v_ln& norm, const p2v_float_ln* fnorm, const p2v_linear& lin,
+                const p2v_epilogue& e, int N, int8_t* out, bool few) {
+    if (fnorm) {                    // always the unfused pair: the fused LayerNorm+GEMM kernels have no float form
+      float* vals = full();
+      int rc = float_layernorm(*fnorm, stride, rows, LN, vals);
+      if (rc || (vals && (rc = ddv_f32(vals, T, D)))) return rc;                                                 // norm1 / norm2
+      return gemm(k_gemm, few, epi, LN, D, rows, Dk, N, lin, e, out, N);
+    }
     LnArgs ln{X, stride, rows, D, norm, LN, D};
     ln.pre = norm.pre;
     if (float* vals = full()) {     // FULL DDV stages: the unfused pair, the LayerNorm's values reduced before the GEMM's tap reuses the buffer
@@ -692,23 +711,31 @@ struct Fwd {
     p2v_epilogue eq{};
     eq.inv_s_out = b.inv_s_qkv[bq];
     eq.tap_out = o.qkv_tap ? o.qkv_tap[i] : (o.lin_tap ? o.lin_tap[1 + 4 * i] : nullptr);
-    if ((rc = ln_linear(P2V_K_LN_GEMM_QKV, P2V_K_GEMM_QKV, P2V_EPI_REQUANT, D, M, b.ln1[bq], qkv, eq, 3 * D, QKV, false))) return rc;
+    const p2v_float_block& fb = p->fblocks[i];
+    if ((rc = ln_linear(P2V_K_LN_GEMM_QKV, P2V_K_GEMM_QKV, P2V_EPI_REQUANT, D, M, b.ln1[bq], p->float_norm ? &fb.ln1[bq] : nullptr, qkv, eq, 3 * D, QKV,
+                        false)))
+      return rc;
     if ((rc = ddv_tap(T, 3 * D)) || (rc = ddv_i8(QKV, T, 3 * D, nullptr))) return rc;                           // attn.qkv, attn.qact1
     // scores -> qact_attn1 -> log-int-softmax -> @v -> qact2                  vit_fquant.py:309-326
-    AttnArgs at{{QKV, batch, T, p->d.num_heads, b.attn, ATT, nullptr}};
-    at.nq = rs.nq;
-    int8_t* planes = (!done && o.ddv) ? o.ddv->attn : nullptr;              // P2V_DDV_STAGES_ATTN: the tapped launch, both planes of this block
-    const int pitch = round_up(T, 16), HT = p->d.num_heads * T;
-    if (planes) {
-      at.score_codes = planes;
-      at.probs_kp = planes + (size_t)batch * HT * pitch;
-      at.pitch = pitch;
+    if (p->float_softmax) {        // scores -> qact_attn1 -> softmax (table) -> @v -> qact2
+      const SmAttnArgs sa{QKV, batch, T, p->d.num_heads, b.attn.s_qkv_sq, b.attn.qk_scale, b.attn.inv_s_attn, b.attn.av_mul, fb.softmax_table, ATT, nullptr, 0, rs.nq};
+      if ((rc = step(P2V_K_ATTENTION, [&] { return launch_rc(p2v_launch_softmax_attention(sa, hd, st), "softmax_attention"); }))) return rc;
+    } else {
+      AttnArgs at{{QKV, batch, T, p->d.num_heads, b.attn, ATT, nullptr}};
+      at.nq = rs.nq;
+      int8_t* planes = (!done && o.ddv) ? o.ddv->attn : nullptr;              // P2V_DDV_STAGES_ATTN: the tapped launch, both planes of this block
+      const int pitch = round_up(T, 16), HT = p->d.num_heads * T;
+      if (planes) {
+        at.score_codes = planes;
+        at.probs_kp = planes + (size_t)batch * HT * pitch;
+        at.pitch = pitch;
+      }
+      if ((rc = step(P2V_K_ATTENTION, [&] { return launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"); }))) return rc;
+      if (planes && !done &&
+          ((rc = ddv_reduce(o.ddv, at.score_codes, HT, T, P2V_COS_I8, nullptr, st, 0, pitch)) ||                      // attn.qact_attn1
+           (rc = ddv_reduce(o.ddv, at.probs_kp, HT, T, P2V_COS_LOG2K, nullptr, st, 0, pitch))))                        // attn.log_int_softmax
+        return rc;
     }
-    if ((rc = step(P2V_K_ATTENTION, [&] { return launch_rc(p2v_launch_attention(at, hd, st), "lis_attention"); }))) return rc;
-    if (planes && !done &&
-        ((rc = ddv_reduce(o.ddv, at.score_codes, HT, T, P2V_COS_I8, nullptr, st, 0, pitch)) ||                      // attn.qact_attn1
-         (rc = ddv_reduce(o.ddv, at.probs_kp, HT, T, P2V_COS_LOG2K, nullptr, st, 0, pitch))))                        // attn.log_int_softmax
-      return rc;
     if ((rc = ddv_i8(ATT, T, D, nullptr))) return rc;                                                            // attn.qact2
     // proj -> qact3 -> + x -> Block.qact2, in place on x                      vit_fquant.py:334-338,431
     p2v_epilogue ep = b.proj_epi;
@@ -724,7 +751,9 @@ struct Fwd {
     e1.inv_s_out = b.inv_s_fc1;
     e1.gelu = b.gelu_fc1;
     e1.tap_out = o.fc1_tap ? o.fc1_tap[i] : (o.lin_tap ? o.lin_tap[3 + 4 * i] : nullptr);
-    if ((rc = ln_linear(P2V_K_LN_GEMM_FC1, P2V_K_GEMM_FC1, P2V_EPI_GELU, rs.stride, rs.rows, b.ln2[bq][b1], fc1, e1, Hd, HID, rs.few))) return rc;
+    if ((rc = ln_linear(P2V_K_LN_GEMM_FC1, P2V_K_GEMM_FC1, P2V_EPI_GELU, rs.stride, rs.rows, b.ln2[bq][b1], p->float_norm ? &fb.ln2[bq][b1] : nullptr, fc1, e1,
+                        Hd, HID, rs.few)))
+      return rc;
     if ((rc = ddv_tap(T, Hd)) || (rc = ddv_i8(HID, T, Hd, nullptr))) return rc;                                 // mlp.fc1, mlp.qact1
     // fc2 -> qact2 -> + x -> Block.qact4, in place on x                       layers_quant.py:342-346, vit_fquant.py:468
     p2v_epilogue e2 = b.fc2_epi;
@@ -750,6 +779,13 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
   if (!p->embed_set || !p->head_set) return fail(P2V_E_STATE, "plan incomplete (embed/head)");
   for (int i = 0; i < p->d.depth; ++i)
     if (!p->block_set[i]) return fail(P2V_E_STATE, "plan incomplete (block %d)", i);
+  if (p->float_norm || p->float_softmax) {
+    for (int i = 0; i < p->d.depth; ++i)
+      if (!p->fblock_set[i]) return fail(P2V_E_STATE, "plan incomplete (float operators of block %d: p2v_plan_set_float_block)", i);
+    if (p->float_norm && !p->fhead_set) return fail(P2V_E_STATE, "plan incomplete (float final norm: p2v_plan_set_float_head)");
+    if (p->float_softmax && o.ddv && o.ddv->attn)
+      return fail(P2V_E_UNSUPPORTED, "P2V_DDV_STAGES_ATTN: the plan's softmax is the float one, its probabilities are not codes");
+  }
   const WsLayout w = ws_layout(p, batch);
   if (workspace_bytes < w.total) return fail(P2V_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, w.total);
   if (o.lin_tap && o.lin_tap[0] && !(p->inv_s_input > 0.f))
@@ -804,21 +840,29 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
   // fc1 and fc2 on `batch` rows - proj and fc2 in place on the class rows of x (stride T * D), the rows between them compact at the
   // start of ln / hid.  The patch rows of x / att / hid keep what the launches before left there.  So the last block runs on the class
   // rows when nothing but the logits is asked for (parity runs read the workspace), and T * D fits the int strides of a GEMM.
-  const bool cls_only = g_cls_rows && o.stop_after < 0 && !o.qkv_tap && !o.fc1_tap && !o.lin_tap && !o.ddv && (long long)T * D <= 0x7fffffffLL;
+  const bool cls_only = g_cls_rows && !p->float_norm && !p->float_softmax && o.stop_after < 0 && !o.qkv_tap && !o.fc1_tap && !o.lin_tap && !o.ddv && (long long)T * D <= 0x7fffffffLL;
   const RowSet all_rows{f.M, D, 0, false}, cls_rows{batch, (long long)T * D, 1, true};
   for (int i = 0; i < d.depth && !f.done; ++i)
     if ((rc = f.block(i, bit_config + 1 + 4 * i, (cls_only && i == d.depth - 1) ? cls_rows : all_rows))) return rc;
 
   // norm over the cls rows only ([:,0]) -> qact2 -> head -> act_out         vit_fquant.py:766-796
-  if (float* vals = f.full()) {      // FULL DDV stages: the hook on `norm` sits in front of [:, 0] - the final norm once more, over every row (codes into ln)
-    LnArgs la{f.X, D, f.M, D, p->final_ln, f.LN, D};
-    la.pre = p->final_ln.pre;
-    la.tap_out = vals;
-    if ((rc = launch_rc(p2v_launch_layernorm(la, st), "int_layernorm")) || (rc = f.ddv_f32(vals, T, D))) return rc;   // norm
+  if (p->float_norm) {
+    if (float* vals = f.full()) {    // FULL DDV stages: the final norm once more, over every row, for its values
+      const FloatLnArgs a{f.X, D, f.M, D, (double)p->final_fln.s_in, (double)p->final_fln.eps, p->final_fln.gamma, p->final_fln.beta, p->final_fln.g, f.LN, D, vals};
+      if ((rc = launch_rc(p2v_launch_float_layernorm(a, st), "float_layernorm")) || (rc = f.ddv_f32(vals, T, D))) return rc;   // norm
+    }
+    if ((rc = f.float_layernorm(p->final_fln, (long long)T * D, batch, f.CLS, nullptr)) || (rc = f.ddv_i8(f.CLS, 1, D, nullptr))) return rc;   // qact2
+  } else {
+    if (float* vals = f.full()) {      // FULL DDV stages: the hook on `norm` sits in front of [:, 0] - the final norm once more, over every row (codes into ln)
+      LnArgs la{f.X, D, f.M, D, p->final_ln, f.LN, D};
+      la.pre = p->final_ln.pre;
+      la.tap_out = vals;
+      if ((rc = launch_rc(p2v_launch_layernorm(la, st), "int_layernorm")) || (rc = f.ddv_f32(vals, T, D))) return rc;   // norm
+    }
+    LnArgs lf{f.X, (long long)T * D, batch, D, p->final_ln, f.CLS, D};
+    lf.pre = p->final_ln.pre;
+    if ((rc = f.layernorm(lf)) || (rc = f.ddv_i8(f.CLS, 1, D, nullptr))) return rc;                               // qact2
   }
-  LnArgs lf{f.X, (long long)T * D, batch, D, p->final_ln, f.CLS, D};
-  lf.pre = p->final_ln.pre;
-  if ((rc = f.layernorm(lf)) || (rc = f.ddv_i8(f.CLS, 1, D, nullptr))) return rc;                               // qact2
   const p2v_linear& head = p->lin[bit_index(bit_config[n_cfg - 1])][n_cfg - 1];
   p2v_epilogue eh{};
   eh.inv_s_out = p->head_inv_s;
@@ -1140,6 +1184,102 @@ int p2v_lis_attention(const int8_t* qkv, int batch, int tokens, int heads, int h
 int p2v_lis_attention_rows(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int query_rows,
                            int8_t* out, void* stream) {
   return lis_attention("p2v_lis_attention_rows", qkv, batch, tokens, heads, head_dim, at, 1, query_rows, out, nullptr, stream);
+}
+
+// ---- float LayerNorm / table softmax (Config(ptf=False) / Config(lis=False)) -------------------------------------------------------------
+static int check_float_ln(const char* who, const p2v_float_ln& l) {
+  if (!l.gamma || !l.beta || !l.g) return fail(P2V_E_ARG, "%s: float LayerNorm constants missing", who);
+  if ((uintptr_t)l.gamma % 16 || (uintptr_t)l.beta % 16 || (uintptr_t)l.g % 16) return fail(P2V_E_ARG, "%s: gamma / beta / g must be 16-byte aligned", who);
+  if (!is_pot(l.s_in) || l.s_in < 0x1p-40f || l.s_in > 0x1p40f) return fail(P2V_E_UNSUPPORTED, "%s: input scale %g must be a power of two", who, l.s_in);
+  if (!(l.eps > 0.f)) return fail(P2V_E_ARG, "%s: eps must be positive", who);
+  return P2V_OK;
+}
+static int check_softmax_attn(const char* who, const p2v_softmax_attn& at) {
+  if (!at.table || (uintptr_t)at.table % 4) return fail(P2V_E_ARG, "%s: null or misaligned softmax table", who);
+  if (!is_pot(at.s_qkv_sq * at.inv_s_attn)) return fail(P2V_E_UNSUPPORTED, "%s: s_qkv_sq * inv_s_attn must be a power of two", who);
+  if (!(at.qk_scale > 0.f)) return fail(P2V_E_ARG, "%s: qk_scale must be positive", who);
+  if (!is_pot(at.av_mul) || at.av_mul > 0x1p15f || at.av_mul < 0x1p-40f)
+    return fail(P2V_E_UNSUPPORTED, "%s: av_mul %g must be a power of two in [2^-40, 2^15]", who, at.av_mul);
+  return P2V_OK;
+}
+static int check_softmax_shape(const char* who, int head_dim, int tokens) {
+  if (head_dim != 32 && head_dim != 64) return fail(P2V_E_UNSUPPORTED, "%s: head_dim %d (the table-softmax attention covers 32 and 64)", who, head_dim);
+  if (tokens > P2V_MAX_TOKENS) return fail(P2V_E_UNSUPPORTED, "%s: %d tokens per image, the table-softmax attention covers up to %d", who, tokens, P2V_MAX_TOKENS);
+  return P2V_OK;
+}
+
+int p2v_float_layernorm(const int8_t* x, long long row_stride, int rows, int C, const p2v_float_ln* ln, int8_t* out, long long out_stride,
+                        float* tap_out, void* stream) {
+  if (!x || !ln || !out) return fail(P2V_E_ARG, "p2v_float_layernorm: null argument");
+  if (C % 4 || row_stride % 4 || out_stride % 4) return fail(P2V_E_UNSUPPORTED, "C and strides must be multiples of 4");
+  if (rows <= 0) return fail(P2V_E_SHAPE, "rows must be positive");
+  if (C < 16 || C > 2048) return fail(P2V_E_SHAPE, "p2v_float_layernorm: C=%d, the kernel covers 16 .. 2048 channels", C);
+  if (row_stride < 0 || out_stride < C) return fail(P2V_E_SHAPE, "p2v_float_layernorm: row_stride non-negative, out_stride >= C");
+  if ((uintptr_t)x % 4 || (uintptr_t)out % 4 || (uintptr_t)tap_out % 16) return fail(P2V_E_ARG, "p2v_float_layernorm: x / out 4-byte, tap_out 16-byte aligned");
+  if (const int rc = check_float_ln("p2v_float_layernorm", *ln)) return rc;
+  const FloatLnArgs a{x, row_stride, rows, C, (double)ln->s_in, (double)ln->eps, ln->gamma, ln->beta, ln->g, out, out_stride, tap_out};
+  return launch_rc(p2v_launch_float_layernorm(a, (hipStream_t)stream), "float_layernorm");
+}
+
+int p2v_softmax_attention_taps(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_softmax_attn* at, int8_t* out,
+                               int8_t* score_codes, int pitch, void* stream) {
+  const char* who = "p2v_softmax_attention";
+  if (!qkv || !at || !out) return fail(P2V_E_ARG, "%s: null argument", who);
+  if (batch <= 0 || tokens <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad attention shape");
+  int rc = check_softmax_shape(who, head_dim, tokens);
+  if (rc == P2V_OK) rc = check_softmax_attn(who, *at);
+  if (rc == P2V_OK) rc = check_tap_planes(who, tokens, pitch, {score_codes});
+  if (rc != P2V_OK) return rc;
+  if ((uintptr_t)qkv % 16 || (uintptr_t)out % 4) return fail(P2V_E_ARG, "%s: qkv 16-byte, out 4-byte aligned", who);
+  read_env_once();
+  const SmAttnArgs a{qkv, batch, tokens, heads, at->s_qkv_sq, at->qk_scale, at->inv_s_attn, at->av_mul, at->table, out, score_codes, pitch, 0};
+  return launch_rc(p2v_launch_softmax_attention(a, head_dim, (hipStream_t)stream), who);
+}
+
+int p2v_softmax_attention(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_softmax_attn* at, int8_t* out,
+                          void* stream) {
+  return p2v_softmax_attention_taps(qkv, batch, tokens, heads, head_dim, at, out, nullptr, 0, stream);
+}
+
+int p2v_plan_set_float_ops(p2v_plan* plan, int float_norm, int float_softmax) {
+  if (!plan) return fail(P2V_E_ARG, "p2v_plan_set_float_ops: null plan");
+  if (float_softmax)
+    if (const int rc = check_softmax_shape("p2v_plan_set_float_ops", plan->d.embed_dim / plan->d.num_heads, plan->tokens)) return rc;
+  plan->float_norm = float_norm != 0;
+  plan->float_softmax = float_softmax != 0;
+  return P2V_OK;
+}
+
+int p2v_plan_set_float_block(p2v_plan* plan, int block, const p2v_float_block* blk) {
+  if (!plan || !blk) return fail(P2V_E_ARG, "p2v_plan_set_float_block: null argument");
+  if (block < 0 || block >= plan->d.depth) return fail(P2V_E_ARG, "block %d out of range", block);
+  if (plan->float_norm)
+    for (int i = 0; i < 6; ++i)
+      if (const int rc = check_float_ln("p2v_plan_set_float_block", block_ln(*blk, i))) return rc;
+  if (plan->float_softmax) {
+    if (!blk->softmax_table || (uintptr_t)blk->softmax_table % 4) return fail(P2V_E_ARG, "p2v_plan_set_float_block: null or misaligned softmax table");
+    // den >= table[0] > 0 and the three 7-bit digits: read back once (synchronises, like the LayerNorm fold of p2v_plan_set_block)
+    OwnerDevice own(blk->softmax_table);
+    uint32_t tab[256];
+    if (!own.ok() || hipDeviceSynchronize() != hipSuccess || hipMemcpy(tab, blk->softmax_table, sizeof tab, hipMemcpyDeviceToHost) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(P2V_E_ARG, "p2v_plan_set_float_block: cannot read the softmax table (a device pointer?)");
+    }
+    if (tab[0] == 0) return fail(P2V_E_ARG, "p2v_plan_set_float_block: softmax table entry 0 must be positive");
+    for (int d = 0; d < 256; ++d)
+      if (tab[d] >= (1u << 21)) return fail(P2V_E_ARG, "p2v_plan_set_float_block: softmax table entry %d = %u, must be below 2^21", d, tab[d]);
+  }
+  plan->fblocks[block] = *blk;
+  plan->fblock_set[block] = 1;
+  return P2V_OK;
+}
+
+int p2v_plan_set_float_head(p2v_plan* plan, const p2v_float_ln* final_ln) {
+  if (!plan || !final_ln) return fail(P2V_E_ARG, "p2v_plan_set_float_head: null argument");
+  if (const int rc = check_float_ln("p2v_plan_set_float_head", *final_ln)) return rc;
+  plan->final_fln = *final_ln;
+  plan->fhead_set = true;
+  return P2V_OK;
 }
 
 int p2v_patch_merge_gather(const int8_t* x, int batch, int H, int W, int C, int8_t* out, void* stream) {

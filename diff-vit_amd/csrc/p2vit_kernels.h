@@ -194,3 +194,32 @@ int p2v_launch_profile_diversity(const float* logits, long long ld, int n, int c
 // weight freeze (p2vit_freeze.hip): one streaming launch, every argument checked by p2v_freeze_weights
 int p2v_launch_freeze_weights(const float* w, long long ldw, int N, int K, const float* scale, int n_scale, int bits, int layout, void* out,
                               hipStream_t st);
+
+// float LayerNorm -> QAct and table-softmax attention (p2vit_float_ln.hip, p2vit_attn_softmax.hip): the two operators of the
+// Config(ptf=False) / Config(lis=False) plans
+struct FloatLnArgs {
+  const int8_t* x;
+  long long row_stride;
+  long long rows;
+  int C;
+  double s_in, eps;     // fp32 values of the caller, widened
+  const float* gamma;
+  const float* beta;
+  const float* g;       // [C] output multiplier 1 / (channel_scale * s_out), a power of two
+  int8_t* out;
+  long long out_stride;
+  float* tap_out;       // optional: fp32 [rows][C], RN of the fp64 LayerNorm value
+};
+struct SmAttnArgs {
+  const int8_t* qkv;
+  int B, N, H;
+  float s_qkv_sq, qk_scale, inv_s_attn, av_mul;
+  const unsigned* tab;  // dev [256]: fixed-point exp of max - code, entries below 2^21
+  int8_t* out;
+  int8_t* score_codes;  // optional pitched tap [B][H][N][pitch] of the qact_attn1 codes
+  int pitch;
+  int nq;               // query rows to compute in whole 16-row blocks (0 = all)
+};
+int p2v_launch_float_layernorm(const FloatLnArgs& a, hipStream_t st);
+// head_dim 32 / 64, 1 .. P2V_MAX_TOKENS tokens; -1: no instantiation
+int p2v_launch_softmax_attention(const SmAttnArgs& a, int head_dim, hipStream_t st);

@@ -49,7 +49,9 @@ bypasses the module graph (hooks on QLinear / QConv2d are served, see ``cka``).
 
 ``python -m diff_vit_amd.ddv --model deit_small --bits 8 --n 50`` (or ``--model swin_tiny``; ``--bits mixed`` is refused for Swin) prints
 the float-vs-quantized similarity per stage on the synthetic data of ``harness`` and writes ``ddv_result/ddv.pkl``; ``--stages full``
-prints every hook point of the reference's list, ``--attention`` also the stages inside the attention kernels.  ``--inputs blackbox
+prints every hook point of the reference's list, ``--attention`` also the stages inside the attention kernels; ``--no-ptf --no-lis`` diffs the configuration of the reference's modeldiff_p2.py
+(``Config(False, False, 'minmax')``: float LayerNorm and float softmax between int8 codes, on the engine; ``attention=True`` is refused
+for a quantized ``lis=False`` model).  ``--inputs blackbox
 --mut-iters 1000`` takes the perturbed twins from ``profiling.gen_profiling_inputs_in_blackbox`` on (float model, quantized model) instead
 of PGD (the default, ``--inputs pgd``)."""
 import argparse
@@ -255,6 +257,9 @@ def compute_ddv(model, normal_inputs, adv_inputs, bit_config=None, with_linear=T
         names, sums = _compute_ddv_swin(model, normal_inputs, adv_inputs, bit_config, with_linear, attention)
         d = ddv_from_sums(sums)
         return {nm: d[k] for k, nm in enumerate(names)}
+    if attention and bit_config is not None and not model.cfg.INT_SOFTMAX:
+        raise NotImplementedError('compute_ddv(attention=True): under Config(lis=False) the quantized softmax is the float one, its '
+                                  'probabilities are not codes')
     dev = _device_of(model)
     x, xa = normal_inputs.to(dev).float(), adv_inputs.to(dev).float()
     has_fp = bit_config is not None and any(int(b) == -1 for b in bit_config)
@@ -387,9 +392,11 @@ def main(argv=None):
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--device', default='cuda')
     p.add_argument('--result-name', default='ddv_result')
+    p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT)')
+    p.add_argument('--no-lis', action='store_true', help='Config(lis=False): float softmax (ViT / DeiT; not with --attention)')
     args = p.parse_args(argv)
     device = torch.device(args.device)
-    fp = harness.str2model(args.model)(cfg=Config(True, True, 'minmax'))
+    fp = harness.str2model(args.model)(cfg=Config(not args.no_ptf, not args.no_lis, 'minmax'))
     is_swin = harness._is_swin(fp)
     if not hasattr(fp, 'arch') or not (is_swin or hasattr(fp, 'depth')):
         raise NotImplementedError('the DDV tool covers the ViT / DeiT and the Swin models')

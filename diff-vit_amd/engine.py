@@ -61,6 +61,20 @@ class Epilogue(C.Structure):
                 ('tap_out', _p), ('resid_tab', _p)]
 
 
+class FloatLn(C.Structure):
+    """``p2v_float_ln``: QIntLayerNorm in mode 'ln' -> QAct (Config(ptf=False))."""
+    _fields_ = [('s_in', _f), ('eps', _f), ('gamma', _p), ('beta', _p), ('g', _p)]
+
+
+class SoftmaxAttn(C.Structure):
+    """``p2v_softmax_attn``: attention with the float softmax as a 256-entry fixed-point table (Config(lis=False))."""
+    _fields_ = [('s_qkv_sq', _f), ('qk_scale', _f), ('inv_s_attn', _f), ('av_mul', _f), ('table', _p)]
+
+
+class FloatBlock(C.Structure):
+    _fields_ = [('ln1', FloatLn * 2), ('ln2', (FloatLn * 2) * 2), ('softmax_table', _p)]
+
+
 class Block(C.Structure):
     _fields_ = [('ln1', Ln * 2), ('inv_s_qkv', _f * 2), ('attn', Attn), ('proj_epi', Epilogue), ('ln2', (Ln * 2) * 2),
                 ('inv_s_fc1', _f), ('gelu_fc1', GeluTab), ('fc2_epi', Epilogue)]
@@ -190,6 +204,13 @@ def lib():
         L.p2v_profile_candidates.argtypes = [_p, _i, _ll, _i, _ll, _f, _p, _p]
         L.p2v_profile_step.argtypes = [_p, C.c_size_t, _i, _i, _p, _p, _p, _p, _ll, _i, _ll, _p, _p]
         L.p2v_profile_diversity.argtypes = [_p, _ll, _i, _i, _p, _p, C.c_size_t, _p]
+    if hasattr(L, 'p2v_float_layernorm'):         # float LayerNorm / table softmax (Config(ptf=False) / Config(lis=False)), additive
+        L.p2v_float_layernorm.argtypes = [_p, _ll, _i, _i, C.POINTER(FloatLn), _p, _ll, _p, _p]
+        L.p2v_softmax_attention.argtypes = [_p, _i, _i, _i, _i, C.POINTER(SoftmaxAttn), _p, _p]
+        L.p2v_softmax_attention_taps.argtypes = [_p, _i, _i, _i, _i, C.POINTER(SoftmaxAttn), _p, _p, _i, _p]
+        L.p2v_plan_set_float_ops.argtypes = [_p, _i, _i]
+        L.p2v_plan_set_float_block.argtypes = [_p, _i, C.POINTER(FloatBlock)]
+        L.p2v_plan_set_float_head.argtypes = [_p, C.POINTER(FloatLn)]
     if hasattr(L, 'p2v_freeze_weights'):          # the weight freeze is additive, found by its symbols
         L.p2v_freeze_bytes.argtypes = [_i, _i, _i]
         L.p2v_freeze_bytes.restype = C.c_size_t

@@ -54,11 +54,30 @@ def lis_consts(sf):
     return x0, b, c
 
 
+SOFTMAX_FRAC_BITS = 21
+
+
+def softmax_table(s_attn):
+    """the 256-entry fixed-point exp table of the float softmax (Config(lis=False)): tab[d] = min(rne(exp(-s d) 2^21), 2^21 - 1) for
+    d = max - code, in fp64 on the host; operator input of p2v_softmax_attention (the kernel never evaluates exp)."""
+    s = float(torch.as_tensor(s_attn).reshape(-1)[0])
+    e = np.rint(np.exp(-s * np.arange(256, dtype=np.float64)) * float(1 << SOFTMAX_FRAC_BITS))
+    return np.minimum(e, float((1 << SOFTMAX_FRAC_BITS) - 1)).astype(np.uint32)
+
+
+def _per_channel(t, D):
+    """a QAct scale as D per-channel values: the PTF vector, or the one layer-wise scale of Config(ptf=False) repeated"""
+    t = t.detach().float().reshape(-1)
+    return t.expand(D).contiguous() if t.numel() == 1 else t
+
+
 class FrozenPlan:
     """Device-resident integer plan + handle of the C plan object."""
 
-    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, input_quant=True):
+    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, input_quant=True, int_norm=True, int_softmax=True, ln_eps=1e-6):
         self.arch = dict(arch)
+        # Config(ptf, lis): False selects the float LayerNorm (F.layer_norm -> QAct) / the float softmax as the engine's fp64 / table operators
+        self.int_norm, self.int_softmax, self.ln_eps = bool(int_norm), bool(int_softmax), float(ln_eps)
         self.input_quant = bool(input_quant)      # False: the fp32 image feeds the patch-embed convolution (vit_fquant.py:705, :925)
         self.device = torch.device(device)
         if self.device.type != 'cuda':
@@ -80,6 +99,15 @@ class FrozenPlan:
         desc = E.ModelDesc(E.P2V_ABI_VERSION, a['img_size'], a['patch_size'], in_chans, self.D, self.depth, self.H,
                            self.hidden, a['num_classes'])
         E.check(L.p2v_plan_create(C.byref(desc), C.byref(self._handle)))
+        if not (self.int_norm and self.int_softmax):
+            if not hasattr(L, 'p2v_plan_set_float_ops'):
+                raise RuntimeError('libp2vit_hip.so lacks p2v_plan_set_float_ops (Config(ptf=False) / Config(lis=False)): rebuild')
+            try:      # refused where the plan is created: head_dim other than 32 / 64 or more than 608 tokens under lis=False
+                E.check(L.p2v_plan_set_float_ops(self._handle, int(not self.int_norm), int(not self.int_softmax)))
+            except Exception:
+                L.p2v_plan_destroy(self._handle)
+                self._handle = C.c_void_p()
+                raise
         W = {k: v.detach().float().cpu() for k, v in state_dict.items()}
         # every upload and the plan-time fold of p2v_plan_set_block (a hipMalloc + copies) happen with the plan's device current,
         # whichever device the caller has selected (a plan for cuda:1 built while cuda:0 is current)
@@ -96,7 +124,9 @@ class FrozenPlan:
     @property
     def attention_kernel(self):
         """'resident' | 'packed' | 'stream': the attention kernel the forward of this geometry launches under the current switches - the
-        library's own selection (p2v_attention_kernel), asked at every read."""
+        library's own selection (p2v_attention_kernel), asked at every read; 'softmax' for a lis=False plan (k_softmax_attention)."""
+        if not self.int_softmax:
+            return 'softmax'
         which = E.lib().p2v_attention_kernel(self.D // self.H, self.tokens, 0)
         if which < 0:
             raise NotImplementedError('no attention kernel for head_dim %d at %d tokens' % (self.D // self.H, self.tokens))
@@ -150,6 +180,15 @@ class FrozenPlan:
         return E.Ln(float(s1), E.ptr(self._dev(mask)), E.ptr(self._dev(gamma)), E.ptr(self._dev(beta)),
                     E.ptr(self._dev(1.0 / out_scale)), E.ptr(self._dev(post_mul)))
 
+    def _fln(self, s_in, gamma, beta, g):
+        """constants of the float LayerNorm -> QAct (p2v_float_ln): ONE power-of-two input scale, g = 1 / (channel scale * s_out)"""
+        s_in = _need_pot('float LayerNorm input scale', s_in.reshape(-1))
+        if float(s_in.min()) != float(s_in.max()):
+            raise NotImplementedError('float LayerNorm behind a per-channel input scale')
+        D = gamma.numel()
+        g = _need_pot('float LayerNorm output multiplier', g.reshape(-1).expand(D).contiguous())
+        return E.FloatLn(float(s_in[0]), self.ln_eps, E.ptr(self._dev(gamma)), E.ptr(self._dev(beta)), E.ptr(self._dev(g)))
+
     def _build(self, W, c):
         L = E.lib()
         a, D = self.arch, self.D
@@ -164,7 +203,7 @@ class FrozenPlan:
         s_pe = _need_pot('patch_embed.qact', c['patch_embed.qact'])
         s_e = _need_pot('qact_embed', c['qact_embed'])
         s_p = _need_pot('qact_pos', c['qact_pos'])
-        s_res = c['qact1'].detach().float().reshape(-1)                       # PTF: arbitrary fp32
+        s_res = _per_channel(c['qact1'], D)                                   # PTF: arbitrary fp32
         pos_deq = (_q8(W['pos_embed'], s_p) * s_p).reshape(self.tokens, D)
         cls_v = _q8(W['cls_token'].reshape(1, D), s_e) * s_e + pos_deq[0:1]   # vit_fquant.py:718-725
         cls_codes = _q8(cls_v, s_res.reshape(1, -1)).reshape(D)
@@ -190,8 +229,9 @@ class FrozenPlan:
             cs_m, s_m0 = c[p + 'mlp.best_scale'], c[p + 'mlp.best_act_scale']
             g1, b1 = W[p + 'norm1.weight'], W[p + 'norm1.bias']
             g2, b2 = W[p + 'norm2.weight'], W[p + 'norm2.bias']
-            s_b2 = c[p + 'qact2'].detach().float().reshape(-1)
-            s_b4 = c[p + 'qact4'].detach().float().reshape(-1)
+            s_b2 = _per_channel(c[p + 'qact2'], D)
+            s_b4 = _per_channel(c[p + 'qact4'], D)
+            fblk = E.FloatBlock()
             s_q1 = _need_pot(p + 'attn.qact1', c[p + 'attn.qact1'])
             s_at = _need_pot(p + 'attn.qact_attn1', c[p + 'attn.qact_attn1'])
             s_a2 = _need_pot(p + 'attn.qact2', c[p + 'attn.qact2'])
@@ -201,19 +241,27 @@ class FrozenPlan:
                 sab = _need_pot(p + 'attn.qact0', s_a0[bi])
                 out_scale = sab * csb                                          # layers.py:264-265
                 blk.ln1[bi] = self._ln(s_res, g1, b1, out_scale, out_scale / csb / sab)
+                if not self.int_norm:
+                    fblk.ln1[bi] = self._fln(s_res, g1, b1, 1.0 / (csb * sab))
                 blk.inv_s_qkv[bi] = float(1.0 / s_q1)
                 for bm in range(2):
                     csm = _need_pot(p + 'mlp.channel_scale', cs_m[bm])
                     smb = _need_pot(p + 'mlp.qact0', s_m0[bm])
                     o2 = smb * csb                                             # attention's scale: vit_fquant.py:464
                     blk.ln2[bi][bm] = self._ln(s_b2, g2, b2, o2, o2 / csm / smb)
+                    if not self.int_norm:
+                        fblk.ln2[bi][bm] = self._fln(s_b2, g2, b2, 1.0 / (csm * smb))
             # qkv / fc1 depend on the bit-pool index through best_* (identical when |alpha_pool| == 1)
             self._linear_per_bit(1 + 4 * i, W[p + 'attn.qkv.weight'], cs_a, s_a0, c[p + 'attn.best_weight_scale'], W[p + 'attn.qkv.bias'])
-            x0, bb, cc = lis_consts(s_at)
+            if self.int_softmax:
+                x0, bb, cc = lis_consts(s_at)
+            else:      # the table softmax reads none of them (any valid triple passes the block's checks)
+                x0, bb, cc = -1, 0, 1
+                fblk.softmax_table = E.ptr(self._dev(torch.from_numpy(softmax_table(s_at).astype(np.int32)), torch.int32))
             blk.attn = E.Attn(float(s_q1 * s_q1), float(np.float32(hd ** -0.5)), float(1.0 / s_at), float(s_q1 / s_a2), x0, bb, cc)
             self._linear(2 + 4 * i, W[p + 'attn.proj.weight'], None, s_a2, c[p + 'attn.proj'], W[p + 'attn.proj.bias'])
             pe = E.Epilogue()
-            pe.s_mid = E.ptr(self._dev(c[p + 'attn.qact3'].reshape(-1)))
+            pe.s_mid = E.ptr(self._dev(_per_channel(c[p + 'attn.qact3'], D)))
             pe.s_res = E.ptr(self._dev(s_res))
             pe.s_next = E.ptr(self._dev(s_b2))
             blk.proj_epi = pe
@@ -222,11 +270,13 @@ class FrozenPlan:
             blk.gelu_fc1 = E.gelu_table(float(1.0 / s_m1), self.device)      # exact GELU -> qact1 threshold table (cached per scale)
             self._linear(4 + 4 * i, W[p + 'mlp.fc2.weight'], None, s_m1, c[p + 'mlp.fc2'], W[p + 'mlp.fc2.bias'])
             fe = E.Epilogue()
-            fe.s_mid = E.ptr(self._dev(c[p + 'mlp.qact2'].reshape(-1)))
+            fe.s_mid = E.ptr(self._dev(_per_channel(c[p + 'mlp.qact2'], D)))
             fe.s_res = E.ptr(self._dev(s_b2))
             fe.s_next = E.ptr(self._dev(s_b4))
             blk.fc2_epi = fe
             E.check(L.p2v_plan_set_block(self._handle, i, C.byref(blk)))
+            if not (self.int_norm and self.int_softmax):
+                E.check(L.p2v_plan_set_float_block(self._handle, i, C.byref(fblk)))
             if L.p2v_plan_block_prefolded(self._handle, i) != 1:        # same results either way: the kernels then fold per workgroup
                 warnings.warn('block %d: LayerNorm constants not folded at plan time: %s' % (i, (L.p2v_last_error() or b'').decode()))
             s_res = s_b4
@@ -235,6 +285,9 @@ class FrozenPlan:
         s_o = _need_pot('act_out', c['act_out'])
         fl = self._ln(s_res, W['norm.weight'], W['norm.bias'], s_f, s_f / s_f)
         E.check(L.p2v_plan_set_head(self._handle, C.byref(fl), float(1.0 / s_o), float(s_o)))
+        if not self.int_norm:
+            ff = self._fln(s_res, W['norm.weight'], W['norm.bias'], 1.0 / s_f)
+            E.check(L.p2v_plan_set_float_head(self._handle, C.byref(ff)))
         self._linear(self.n_layers - 1, W['head.weight'], None, s_f, c['head'], W['head.bias'])
         self.s_out = float(s_o)
 
@@ -452,6 +505,8 @@ class FrozenPlan:
         n = B // 2
         L = E.lib()
         names = self.ddv_stage_names(with_linear, stages, attention)
+        if attention and not self.int_softmax:
+            raise NotImplementedError('forward_ddv(attention=True): the softmax of a lis=False plan is the float one, its probabilities are not codes')
         if attention:
             return self._forward_ddv_attention(images, cfg, len(bit_config), n, names, with_linear, stages)
         full = stages == 'full'

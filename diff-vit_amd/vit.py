@@ -418,11 +418,10 @@ class VisionTransformer(nn.Module):
     def freeze(self, device=None):
         """build (once) the integer plan the HIP engine executes; called lazily by the first quantized forward."""
         from .plan import FrozenPlan
-        if not (self.cfg.INT_NORM and self.cfg.INT_SOFTMAX):
-            raise NotImplementedError('the HIP engine implements the ptf=True, lis=True configuration')
         dev = device or self.cls_token.device
         sd = {k: v for k, v in self.state_dict().items()}
-        self._plan = FrozenPlan(self.arch, sd, self.export_calib(), device=dev, in_chans=self.in_chans, input_quant=self.input_quant)
+        self._plan = FrozenPlan(self.arch, sd, self.export_calib(), device=dev, in_chans=self.in_chans, input_quant=self.input_quant,
+                                int_norm=bool(self.cfg.INT_NORM), int_softmax=bool(self.cfg.INT_SOFTMAX), ln_eps=float(self.norm.eps))
         return self._plan
 
     def flops(self):
@@ -465,11 +464,13 @@ class VisionTransformer(nn.Module):
         """the fused engine replaces the module-by-module graph only in the state ``model_quant()`` leaves behind: the model
         flag AND every Q-module's own ``.quant`` set (the reference's forward reads the per-module flags, so
         ``model_dequant()`` or a single ``m.quant = False`` sends it down the float branch of that module) AND every
-        QIntLayerNorm still in mode 'int' (a ``-1`` entry flips its block's norm to float for good, vit_fquant.py:429-430)."""
+        QIntLayerNorm still in mode 'int' (a ``-1`` entry flips its block's norm to float for good, vit_fquant.py:429-430).  Under
+        Config(ptf=False) ``model_quant()`` leaves every norm in mode 'ln': the engine then runs its float LayerNorm, and every norm must
+        still be in that mode."""
         if self._lnmods is None:
             self._lnmods = [m for m in self.modules() if type(m) is QIntLayerNorm]
         return (self.quant and all(m.quant and not m.calibrate for m in self._q_modules())
-                and all(m.mode == 'int' for m in self._lnmods))
+                and all(m.mode == ('int' if self.cfg.INT_NORM else 'ln') for m in self._lnmods))
 
     def forward(self, x, bit_config=None, plot=False, hessian_statistic=False):
         # bit_config == -1 is the reference's per-layer fp32 fallback (layers.py:144,171: plain F.linear / F.conv2d; for qkv / fc1

@@ -66,7 +66,10 @@
  *   - LayerNorm output scale: p2v_ln.inv_out is MULTIPLIED by where the reference divides by the scale - identical for the power-of-two
  *     scales of this path; for any other scale pass p2v_ln.out_scale too and the kernel divides (exact, ABI 3);
  *   - REQUANT epilogues fold 1/scale into the column constants: it must be a power of two;
- *   - log-int-softmax constants: c_int < 2^24 (qact_attn1 scale >= 2^-11).
+ *   - log-int-softmax constants: c_int < 2^24 (qact_attn1 scale >= 2^-11);
+ *   - Config(ptf=False) / Config(lis=False) of a ViT / DeiT plan (p2v_plan_set_float_ops, at the end of this header): the float LayerNorm for
+ *     16 .. 2048 channels under one power-of-two input scale; the table-softmax attention for head_dim 32 / 64 and up to P2V_MAX_TOKENS
+ *     tokens.  Swin plans run the ptf = True, lis = True configuration only.
  */
 #ifndef P2VIT_H
 #define P2VIT_H
@@ -837,6 +840,61 @@ enum { P2V_W_ROWS_I8 = 0, P2V_W_FRAG_I8 = 1, P2V_W_TILES_P4 = 2, P2V_W_FRAG_P4 =
 size_t p2v_freeze_bytes(int N, int K, int layout);
 int p2v_freeze_weights(const float* w, long long ldw, int N, int K, const float* scale, int n_scale, int bits, int layout, void* out,
                        size_t out_bytes, void* stream);
+
+/* ---- Float LayerNorm and float softmax: Config(ptf=False) / Config(lis=False) (additive: no structure, existing entry point or
+ *      P2V_ABI_VERSION changes; found by their symbols) -----------------------------------------------------------------------------------
+ * The reference's two float operators between int8 codes (QIntLayerNorm in mode 'ln': F.layer_norm, layers.py:241-243; QIntSoftmax with
+ * log_i_softmax = False: x.softmax, layers.py:387-395), each followed by a QAct, restated so that no result depends on a summation order.
+ *
+ * p2v_float_layernorm: a row of C codes q_c under ONE power-of-two input scale s_in.  S1 = sum q, S2 = sum q^2 (exact integers); in fp64,
+ * every operation rounded on its own:
+ *     var = ((C S2 - S1^2) / (C C)) s_in s_in;   r = 1 / sqrt(var + eps);   y_c = ((((C q_c - S1) / C) s_in) r) gamma_c + beta_c
+ *     out_c = clamp(rne(y_c g_c), -128, 127)
+ * gamma, beta, g: dev fp32 [C], 16-byte aligned; g_c = 1 / (channel_scale_c * s_out), a power of two (the caller's to guarantee: the kernel
+ * multiplies).  tap_out (optional, NULL): dev fp32 dense [rows][C], 16-byte aligned, receives RN32(y_c) - what a hook on the module sees, up
+ * to the distance between this expression and the platform's fp32 F.layer_norm.  C: a multiple of 4 in 16 .. 2048; row_stride / out_stride
+ * as p2v_int_layernorm (multiples of 4, out_stride >= C); bytes [C, out_stride) of an output row are not written.
+ *
+ * p2v_softmax_attention: p2v_lis_attention's layouts and score requantisation (the qact_attn1 codes c_ij), then
+ *     d_ij = max_j c_ij - c_ij in [0, 255];  E_ij = table[d_ij];  num_ic = sum_j E_ij v_jc;  den_i = sum_j E_ij        (exact integers)
+ *     out_ic = clamp(rne((double(num_ic) / double(den_i)) av_mul), -128, 127)                                          (one IEEE fp64 division)
+ * table: dev uint32 [256], every entry below 2^21 and table[0] > 0 - the caller's to guarantee at the operator (p2v_plan_set_float_block reads
+ * the array back once and refuses others with P2V_E_ARG); the plan builds it as min(rne(exp(-s_attn d) 2^21), 2^21 - 1) in fp64 on the host,
+ * the kernel never evaluates exp.  av_mul = s_q1 /
+ * qact2 scale, a power of two in [2^-40, 2^15].  head_dim 32 or 64, 1 .. P2V_MAX_TOKENS tokens (P2V_E_UNSUPPORTED otherwise).
+ * p2v_softmax_attention_taps also writes the score codes as p2v_lis_attention_taps does (pitched plane, columns [0, tokens) only). */
+typedef struct p2v_float_ln {
+  float s_in;          /* scale of the input codes, a power of two */
+  float eps;
+  const float* gamma;  /* dev [C] */
+  const float* beta;   /* dev [C] */
+  const float* g;      /* dev [C] */
+} p2v_float_ln;
+typedef struct p2v_softmax_attn {
+  float s_qkv_sq, qk_scale, inv_s_attn, av_mul;   /* as p2v_attn */
+  const uint32_t* table;                          /* dev [256] */
+} p2v_softmax_attn;
+int p2v_float_layernorm(const int8_t* x, long long row_stride, int rows, int C, const p2v_float_ln* ln, int8_t* out, long long out_stride,
+                        float* tap_out, void* stream);
+int p2v_softmax_attention(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_softmax_attn* at, int8_t* out,
+                          void* stream);
+int p2v_softmax_attention_taps(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_softmax_attn* at, int8_t* out,
+                               int8_t* score_codes, int pitch, void* stream);
+/* The plan side.  p2v_plan_set_float_ops (right after p2v_plan_create) selects per plan the float LayerNorm (float_norm != 0) and / or the
+ * table softmax (float_softmax != 0); P2V_E_UNSUPPORTED when the geometry is outside the operators' (float_softmax: head_dim other than 32 /
+ * 64, more than P2V_MAX_TOKENS tokens).  p2v_plan_set_float_block carries a block's constants, indexed like p2v_block.ln1 / ln2 (members of a
+ * kind the plan does not use are ignored; the arrays stay the caller's); p2v_plan_set_float_head the final norm's (channel scale all ones: g = 1 / qact2 scale).  p2v_block /
+ * p2v_plan_set_block / p2v_plan_set_head are still required and unchanged: they carry everything else.  In such a plan the fused
+ * LayerNorm+GEMM kernels do not run behind a float LayerNorm, the last block computes every row, and P2V_DDV_STAGES_ATTN is refused
+ * (P2V_E_UNSUPPORTED) under the table softmax: its probabilities are not codes. */
+typedef struct p2v_float_block {
+  p2v_float_ln ln1[2];
+  p2v_float_ln ln2[2][2];
+  const uint32_t* softmax_table;   /* dev [256] */
+} p2v_float_block;
+int p2v_plan_set_float_ops(p2v_plan* plan, int float_norm, int float_softmax);
+int p2v_plan_set_float_block(p2v_plan* plan, int block, const p2v_float_block* blk);
+int p2v_plan_set_float_head(p2v_plan* plan, const p2v_float_ln* final_ln);
 
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
