@@ -465,15 +465,17 @@ def copy_stream(device):
     bound at 53 - 57 GB/s: 88 - 95 k; profiles/r04_pcie.txt)."""
     idx = _dev_index(device)
     st = side_streams(idx, MAX_SIDE_STREAMS)[MAX_SIDE_STREAMS - 1]
-    _COPY_STREAM[idx] = _COPY_STREAM.get(idx, 0) + 1
+    with _SIDE_LOCK:
+        _COPY_STREAM[idx] = _COPY_STREAM.get(idx, 0) + 1
     return st
 
 
 def release_copy_stream(device):
     """the input pipeline is done: the sliced forward may use all side streams again"""
     idx = _dev_index(device)
-    if _COPY_STREAM.get(idx, 0) > 0:
-        _COPY_STREAM[idx] -= 1
+    with _SIDE_LOCK:
+        if _COPY_STREAM.get(idx, 0) > 0:
+            _COPY_STREAM[idx] -= 1
 
 
 def compute_side_streams(device):
@@ -481,7 +483,7 @@ def compute_side_streams(device):
     return MAX_SIDE_STREAMS - (1 if _COPY_STREAM.get(_dev_index(device), 0) > 0 else 0)
 
 
-# ---- host threads that enqueue the side streams' slices (FrozenPlan.forward_streams) ----------------------------------------------------
+# ---- the sliced forward's fork / enqueue / join, and the host threads that enqueue the side streams' slices ---------------------------
 THREADED_ENQUEUE = os.environ.get('P2V_THREADED_ENQUEUE', '1') != '0'
 _ENQUEUE_POOL = None
 
@@ -495,3 +497,39 @@ def enqueue_pool():
                 from concurrent.futures import ThreadPoolExecutor
                 _ENQUEUE_POOL = ThreadPoolExecutor(MAX_SIDE_STREAMS, thread_name_prefix='p2v-enqueue')
     return _ENQUEUE_POOL
+
+
+def run_on_streams(device, side, jobs, threads=True):
+    """Fork / enqueue / join of a sliced forward (``FrozenPlan.forward_streams``, ``SwinPlan.forward``).  ``jobs[j]`` holds the callables
+    of side stream ``side[j]``, ``jobs[len(side)]`` those of the caller's current stream on ``device``; each is called with its stream,
+    the ones of one stream in list order.  The side streams that have jobs wait for the caller's stream first, and the caller's stream
+    waits for them at the end.
+
+    One host thread per such side stream (the C calls release the interpreter lock and only read the plan), the caller's jobs on the
+    calling thread meanwhile: the launch sequences reach their queues together instead of one after the other - a synchronous step
+    (forward, then read the logits) takes 2.61 instead of 2.79 ms at DeiT-S / 256, back-to-back steps 2.43 instead of 2.48 ms
+    (profiles/r04_threaded_enqueue.txt).  Not under THREADED_ENQUEUE = False, not while the stream is capturing, and not when the caller
+    says ``threads=False``; a worker's exception is raised here."""
+    import torch
+    cur = torch.cuda.current_stream(device)
+    used = [(st, js) for st, js in zip(side, jobs) if js]
+    for st, _ in used:
+        st.wait_stream(cur)
+    idx = _dev_index(device)
+
+    def enqueue(st, js, worker):
+        if worker:
+            torch.cuda.set_device(idx)                     # (the current device is a per-thread setting)
+        for job in js:
+            job(st)
+
+    if THREADED_ENQUEUE and threads and not torch.cuda.is_current_stream_capturing():
+        futs = [enqueue_pool().submit(enqueue, st, js, True) for st, js in used]
+        enqueue(cur, jobs[len(side)], False)
+        for f in futs:
+            f.result()
+    else:
+        for st, js in used + [(cur, jobs[len(side)])]:
+            enqueue(st, js, False)
+    for st, _ in used:
+        cur.wait_stream(st)

@@ -89,6 +89,8 @@ class FrozenPlan:
         self._handle = C.c_void_p()
         self._ws = None
         self._ws_batch = 0
+        self._ws_multi = []      # grow-only workspace of slice i of the sliced forward
+        self._streams = []       # the side streams the last sliced forward borrowed (engine.side_streams)
         a = self.arch
         self.D, self.depth, self.H = a['embed_dim'], a['depth'], a['num_heads']
         self.hidden = int(self.D * a['mlp_ratio'])
@@ -138,32 +140,37 @@ class FrozenPlan:
         self._keep.append(t)
         return t
 
-    def _linear(self, layer, w, cs, s_x, dic, bias, pack4=True):
+    def _linear(self, layer, w, cs, s_x, dic, bias, pack4=True, per_bit=False):
         """QLinear/QConv2d weight for both bit widths (layers.py:173-178; uniform.py:82-88).  ``pack4`` False keeps 4-bit codes one
-        per byte (the fp32-input patch embedding reads unpacked codes)."""
+        per byte (the fp32-input patch embedding reads unpacked codes).  ``per_bit`` (qkv / fc1): ``cs``, ``s_x`` and ``dic`` are lists,
+        the SmoothQuant state is looked up per bit-pool index (vit_fquant.py:282-292); these layers follow a LayerNorm, so a second copy
+        in MFMA-fragment order feeds the fused LayerNorm+GEMM kernel."""
         L = E.lib()
-        w2 = w.reshape(w.shape[0], -1)
-        if cs is not None:
-            w2 = w2 * cs.reshape((1, -1))                    # weight_smoothed, vit_fquant.py:285
-        N, K = w2.shape
+        w = w.reshape(w.shape[0], -1)
+        N, K = w.shape
         n_pad = (N + GEMM_N_PAD - 1) // GEMM_N_PAD * GEMM_N_PAD
         k_pad = (K + GEMM_K_PAD - 1) // GEMM_K_PAD * GEMM_K_PAD
-        for bits in BIT_POOL:
+        for bi, bits in enumerate(BIT_POOL):
             name = 'int%d' % bits
-            s_w = _need_pot('%d.%s weight scale' % (layer, name), dic[name]).reshape(-1)
+            cs_b, s_x_b, dic_b = (cs[bi], s_x[bi], dic[bi]) if per_bit else (cs, s_x, dic)
+            w2 = w if cs_b is None else w * cs_b.reshape((1, -1))          # weight_smoothed, vit_fquant.py:285
+            s_w = _need_pot('%d.%s weight scale' % (layer, name), dic_b[name]).reshape(-1)
+            s_x_b = _need_pot('%d act scale' % layer, s_x_b).reshape(-1)
             lo, hi = BOUNDS[bits]
-            codes = torch.clamp(torch.round(w2 / s_w.reshape(-1, 1)), lo, hi)
             wp = torch.zeros(n_pad, k_pad, dtype=torch.int8)
-            wp[:N, :K] = codes.to(torch.int8)
+            wp[:N, :K] = torch.clamp(torch.round(w2 / s_w.reshape(-1, 1)), lo, hi).to(torch.int8)
             cs_col = torch.zeros(n_pad)
-            cs_col[:N] = (s_x.reshape(-1) * s_w).expand(N)
+            cs_col[:N] = (s_x_b * s_w).expand(N)
             bp = torch.zeros(n_pad)
             if bias is not None:
                 bp[:N] = bias
             # 4-bit weights travel packed, two codes per byte (half the HBM bytes of BASELINE config 5), as LDS tile images
             packed = bits == 4 and pack4
             wdev = self._dev(E.pack_int4_tiles(wp), torch.uint8) if packed else self._dev(wp, torch.int8)
-            lin = E.Linear(E.ptr(wdev), E.ptr(self._dev(cs_col)), E.ptr(self._dev(bp)), None, 1 if packed else 0)
+            frag = None
+            if per_bit and self.D <= 384:        # 4-bit layers: the fragment copy travels packed too (two codes per byte, ABI 4)
+                frag = E.ptr(self._dev(E.fragment_order_packed4(wp), torch.uint8) if bits == 4 else self._dev(E.fragment_order(wp), torch.int8))
+            lin = E.Linear(E.ptr(wdev), E.ptr(self._dev(cs_col)), E.ptr(self._dev(bp)), frag, 1 if packed else 0)
             E.check(L.p2v_plan_set_linear(self._handle, layer, bits, C.byref(lin)))
 
     def _ln(self, in_scale, gamma, beta, out_scale, post_mul):
@@ -252,7 +259,7 @@ class FrozenPlan:
                     if not self.int_norm:
                         fblk.ln2[bi][bm] = self._fln(s_b2, g2, b2, 1.0 / (csm * smb))
             # qkv / fc1 depend on the bit-pool index through best_* (identical when |alpha_pool| == 1)
-            self._linear_per_bit(1 + 4 * i, W[p + 'attn.qkv.weight'], cs_a, s_a0, c[p + 'attn.best_weight_scale'], W[p + 'attn.qkv.bias'])
+            self._linear(1 + 4 * i, W[p + 'attn.qkv.weight'], cs_a, s_a0, c[p + 'attn.best_weight_scale'], W[p + 'attn.qkv.bias'], per_bit=True)
             if self.int_softmax:
                 x0, bb, cc = lis_consts(s_at)
             else:      # the table softmax reads none of them (any valid triple passes the block's checks)
@@ -265,7 +272,7 @@ class FrozenPlan:
             pe.s_res = E.ptr(self._dev(s_res))
             pe.s_next = E.ptr(self._dev(s_b2))
             blk.proj_epi = pe
-            self._linear_per_bit(3 + 4 * i, W[p + 'mlp.fc1.weight'], cs_m, s_m0, c[p + 'mlp.best_weight_scale'], W[p + 'mlp.fc1.bias'])
+            self._linear(3 + 4 * i, W[p + 'mlp.fc1.weight'], cs_m, s_m0, c[p + 'mlp.best_weight_scale'], W[p + 'mlp.fc1.bias'], per_bit=True)
             blk.inv_s_fc1 = float(1.0 / s_m1)
             blk.gelu_fc1 = E.gelu_table(float(1.0 / s_m1), self.device)      # exact GELU -> qact1 threshold table (cached per scale)
             self._linear(4 + 4 * i, W[p + 'mlp.fc2.weight'], None, s_m1, c[p + 'mlp.fc2'], W[p + 'mlp.fc2.bias'])
@@ -291,43 +298,34 @@ class FrozenPlan:
         self._linear(self.n_layers - 1, W['head.weight'], None, s_f, c['head'], W['head.bias'])
         self.s_out = float(s_o)
 
-    def _linear_per_bit(self, layer, w, cs_list, s_x_list, dic_list, bias):
-        """qkv / fc1: SmoothQuant state is looked up per bit-pool index (vit_fquant.py:282-292)."""
-        L = E.lib()
-        N, K = w.shape
-        n_pad = (N + GEMM_N_PAD - 1) // GEMM_N_PAD * GEMM_N_PAD
-        k_pad = (K + GEMM_K_PAD - 1) // GEMM_K_PAD * GEMM_K_PAD
-        for bi, bits in enumerate(BIT_POOL):
-            name = 'int%d' % bits
-            w2 = w * cs_list[bi].reshape((1, -1))
-            s_w = _need_pot('%d.%s weight scale' % (layer, name), dic_list[bi][name]).reshape(-1)
-            s_x = _need_pot('%d act scale' % layer, s_x_list[bi]).reshape(-1)
-            lo, hi = BOUNDS[bits]
-            wp = torch.zeros(n_pad, k_pad, dtype=torch.int8)
-            wp[:N, :K] = torch.clamp(torch.round(w2 / s_w.reshape(-1, 1)), lo, hi).to(torch.int8)
-            cs_col = torch.zeros(n_pad)
-            cs_col[:N] = (s_x * s_w).expand(N)
-            bp = torch.zeros(n_pad)
-            bp[:N] = bias
-            # qkv / fc1 follow a LayerNorm: a second copy in MFMA-fragment order feeds the fused LayerNorm+GEMM kernel
-            wdev = self._dev(E.pack_int4_tiles(wp), torch.uint8) if bits == 4 else self._dev(wp, torch.int8)
-            frag = None
-            if self.D <= 384:        # 4-bit layers: the fragment copy travels packed too (two codes per byte, ABI 4)
-                frag = E.ptr(self._dev(E.fragment_order_packed4(wp), torch.uint8) if bits == 4 else self._dev(E.fragment_order(wp), torch.int8))
-            lin = E.Linear(E.ptr(wdev), E.ptr(self._dev(cs_col)), E.ptr(self._dev(bp)), frag, 1 if bits == 4 else 0)
-            E.check(L.p2v_plan_set_linear(self._handle, layer, bits, C.byref(lin)))
-
     # ---------------------------------------------------------------------------------------------
-    def workspace(self, batch):
-        if self._ws is None or self._ws_batch < batch:
-            n = E.lib().p2v_workspace_bytes(self._handle, batch)
+    def workspace(self, batch, min_bytes=0):
+        """the plan's grow-only workspace: enough for a forward of ``batch`` images, and at least ``min_bytes``"""
+        if self._ws is None or self._ws_batch < batch or self._ws.numel() < min_bytes:
+            self._ws_batch = max(self._ws_batch, batch)
+            n = max(E.lib().p2v_workspace_bytes(self._handle, self._ws_batch), min_bytes)
             self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-            self._ws_batch = batch
         return self._ws
+
+    def _check_here(self, images):
+        """a device pointer on THIS plan's GPU, and something to run"""
+        if not images.is_cuda:
+            raise RuntimeError('the quantized forward runs on the HIP engine only: move the input to the GPU')
+        if images.device != self.device:
+            raise RuntimeError('images live on %s, the frozen plan on %s' % (images.device, self.device))
+        if images.shape[0] < 1:
+            raise AssertionError('empty batch')
+
+    @staticmethod
+    def _cfg(bit_config):
+        """``bit_config`` as the int8 array of the C ABI (an entry that does not fit a byte becomes 127, which the library refuses)"""
+        if bit_config is None:
+            raise ValueError('None is not in list')        # bit_pool.index(None), vit_fquant.py:282
+        return (C.c_int8 * len(bit_config))(*[int(b) if -128 <= int(b) <= 127 else 127 for b in bit_config])
 
     def _check(self, images, bit_config):
         """the reference's input checks (layers_quant.py:437-439, vit_fquant.py:282) plus what the C ABI trusts: the geometry in
-        the plan descriptor, a device pointer on THIS plan's GPU.  Shared by ``forward``, ``forward_streams`` and ``profile``
+        the plan descriptor, a device pointer on THIS plan's GPU.  Shared by every entry point that takes fp32 images
         (a wrong-sized or foreign tensor would otherwise be an out-of-bounds read in ``k_quantize_patchify``)."""
         a = self.arch
         if images.dim() != 4 or images.shape[2] != a['img_size'] or images.shape[3] != a['img_size']:
@@ -335,21 +333,20 @@ class FrozenPlan:
                 images.shape[2] if images.dim() > 2 else -1, images.shape[3] if images.dim() > 3 else -1, a['img_size'], a['img_size']))
         if images.shape[1] != self.in_chans:
             raise AssertionError('expected %d input channels' % self.in_chans)
-        if not images.is_cuda:
-            raise RuntimeError('the quantized forward runs on the HIP engine only: move the input to the GPU')
-        if images.device != self.device:
-            raise RuntimeError('images live on %s, the frozen plan on %s' % (images.device, self.device))
-        if images.shape[0] < 1:
-            raise AssertionError('empty batch')
-        if bit_config is None:
-            raise ValueError('None is not in list')        # bit_pool.index(None), vit_fquant.py:282
-        cfg = (C.c_int8 * len(bit_config))(*[int(b) if -128 <= int(b) <= 127 else 127 for b in bit_config])
-        return images.contiguous().float(), cfg
+        self._check_here(images)
+        return images.contiguous().float(), self._cfg(bit_config)
 
     def _check_out(self, out, B):
         # the C ABI writes B x classes floats through the raw pointer
         if tuple(out.shape) != (B, self.arch['num_classes']) or out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous():
             raise AssertionError('out must be a contiguous fp32 [%d, %d] tensor on %s' % (B, self.arch['num_classes'], self.device))
+
+    def _out(self, out, B):
+        """the logits of B images: the caller's ``out``, checked, or a new tensor"""
+        if out is None:
+            return torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
+        self._check_out(out, B)
+        return out
 
     def input_lut(self, lut_f32):
         """the device table ``forward_uint8`` reads for the fp32 table ``lut_f32`` [C, 256] (data.uint8_lut): its codes under this plan's
@@ -370,20 +367,12 @@ class FrozenPlan:
         want = (S, S, Cin) if layout == 'NHWC' else (Cin, S, S)
         if images.dim() != 4 or tuple(images.shape[1:]) != want:
             raise AssertionError('uint8 images in layout %s must be [B, %d, %d, %d], got %s' % ((layout,) + want + (tuple(images.shape),)))
-        if not images.is_cuda:
-            raise RuntimeError('the quantized forward runs on the HIP engine only: move the input to the GPU')
-        if images.device != self.device:
-            raise RuntimeError('images live on %s, the frozen plan on %s' % (images.device, self.device))
-        if images.shape[0] < 1:
-            raise AssertionError('empty batch')
+        self._check_here(images)
         lut_dtype = torch.int8 if self.input_quant else torch.float32
         if (not isinstance(lut, torch.Tensor) or lut.dtype != lut_dtype or tuple(lut.shape) != (Cin, 256) or lut.device != self.device
                 or not lut.is_contiguous()):
             raise AssertionError('lut must be a contiguous %s [%d, 256] tensor on %s (FrozenPlan.input_lut)' % (lut_dtype, Cin, self.device))
-        if bit_config is None:
-            raise ValueError('None is not in list')        # bit_pool.index(None), vit_fquant.py:282
-        cfg = (C.c_int8 * len(bit_config))(*[int(b) if -128 <= int(b) <= 127 else 127 for b in bit_config])
-        return images.contiguous(), cfg
+        return images.contiguous(), self._cfg(bit_config)
 
     def forward_uint8(self, images, lut, bit_config, layout='NHWC', out=None, stop_after=-1):
         """``forward`` on uint8 images: p2v_forward_u8 reads them through ``lut`` (``input_lut``) in its first launch; the logits equal
@@ -391,11 +380,7 @@ class FrozenPlan:
         images, cfg = self._check_u8(images, lut, bit_config, layout)
         B = images.shape[0]
         with torch.cuda.device(self.device):
-            ws = self.workspace(B)
-            if out is None:
-                out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
-            else:
-                self._check_out(out, B)
+            ws, out = self.workspace(B), self._out(out, B)
             E.check(E.lib().p2v_forward_u8(self._handle, E.ptr(images), E.LAYOUTS[layout], E.ptr(lut), B, cfg, len(bit_config), E.ptr(out),
                                            E.ptr(ws), ws.numel(), stop_after, E.stream_ptr(self.device)))
         return out
@@ -404,16 +389,8 @@ class FrozenPlan:
         """``forward_streams`` on uint8 images: the same slices (contiguous in the batch dimension in both layouts), each one
         p2v_forward_u8 call."""
         images, cfg = self._check_u8(images, lut, bit_config, layout)
-        B = images.shape[0]
-        n_streams = min(n_streams, E.compute_side_streams(self.device))
-        sizes = list(slices) if slices is not None else self.slice_sizes(B, n_streams)
-        if sum(sizes) != B or min(sizes) < 1:
-            raise AssertionError('slices %r do not cover a batch of %d' % (sizes, B))
-        self._check_out(out, B)
-        if len(sizes) == 1:
-            return self.forward_uint8(images, lut, bit_config, layout, out=out)
         L, handle, n_cfg, lay, lp = E.lib(), self._handle, len(bit_config), E.LAYOUTS[layout], E.ptr(lut)
-        return self._run_slices(images, sizes, out, n_streams,
+        return self._run_slices(images, out, n_streams, slices, lambda: self.forward_uint8(images, lut, bit_config, layout, out=out),
                                 lambda xi, n_i, oi, ws, ws_n, st: L.p2v_forward_u8(handle, xi, lay, lp, n_i, cfg, n_cfg, oi, ws, ws_n, -1, st))
 
     def forward(self, images, bit_config, stop_after=-1, out=None, taps=None):
@@ -424,11 +401,7 @@ class FrozenPlan:
         images, cfg = self._check(images, bit_config)
         B = images.shape[0]
         with torch.cuda.device(self.device):
-            ws = self.workspace(B)
-            if out is None:
-                out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
-            else:
-                self._check_out(out, B)
+            ws, out = self.workspace(B), self._out(out, B)
             if taps is None:
                 E.check(E.lib().p2v_forward(self._handle, E.ptr(images), B, cfg, len(bit_config), E.ptr(out), E.ptr(ws),
                                             ws.numel(), stop_after, E.stream_ptr(self.device)))
@@ -458,11 +431,7 @@ class FrozenPlan:
         shapes = self.tap_shapes(B)
         want = set(range(len(shapes))) if want is None else set(want)
         with torch.cuda.device(self.device):
-            ws = self.workspace(B)
-            if out is None:
-                out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
-            else:
-                self._check_out(out, B)
+            ws, out = self.workspace(B), self._out(out, B)
             bufs = [torch.empty(s, dtype=torch.float32, device=self.device) if k in want else None for k, s in enumerate(shapes)]
             ptrs = (C.c_void_p * len(bufs))(*[None if t is None else t.data_ptr() for t in bufs])
             E.check(E.lib().p2v_forward_linear_taps(self._handle, E.ptr(images), B, cfg, len(bit_config), E.ptr(out), E.ptr(ws),
@@ -507,58 +476,22 @@ class FrozenPlan:
         names = self.ddv_stage_names(with_linear, stages, attention)
         if attention and not self.int_softmax:
             raise NotImplementedError('forward_ddv(attention=True): the softmax of a lis=False plan is the float one, its probabilities are not codes')
-        if attention:
-            return self._forward_ddv_attention(images, cfg, len(bit_config), n, names, with_linear, stages)
         full = stages == 'full'
-        stage_set = E.DDV_STAGES_FULL if full else E.DDV_STAGES_ENGINE
         if full and not self.input_quant:
             raise NotImplementedError("forward_ddv(stages='full'): no qact_input stage on an input_quant=False plan")
-        if full and not hasattr(L, 'p2v_forward_ddv_ex'):
-            raise RuntimeError("forward_ddv(stages='full'): libp2vit_hip.so lacks p2v_forward_ddv_ex: rebuild")
-        assert len(names) == (L.p2v_ddv_stage_count_ex(self._handle, int(with_linear), stage_set) if full
-                              else L.p2v_ddv_stage_count(self._handle, int(with_linear)))
-        with torch.cuda.device(self.device):
-            nbytes = L.p2v_ddv_workspace_bytes_ex(self._handle, n, stage_set) if full else L.p2v_ddv_workspace_bytes(self._handle, n)
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                self._ws_batch = max(self._ws_batch, B)
-            ws = self._ws
-            out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
-            sums = torch.empty(len(names), n, 3, dtype=torch.float64, device=self.device)
-            tap = torch.empty(self.ddv_tap_bytes(n), dtype=torch.uint8, device=self.device) if (with_linear or full) else None
-            if full:
-                E.check(L.p2v_forward_ddv_ex(self._handle, E.ptr(images), n, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(),
-                                             int(with_linear), stage_set, E.ptr(tap), tap.numel(), E.ptr(sums), E.stream_ptr(self.device)))
-            else:
-                E.check(L.p2v_forward_ddv(self._handle, E.ptr(images), n, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(),
-                                          int(with_linear), E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(sums),
-                                          E.stream_ptr(self.device)))
-        return out, names, sums
-
-    def _forward_ddv_attention(self, images, cfg, n_cfg, n, names, with_linear, stages):
-        """``forward_ddv(attention=True)``: the one p2v_forward_ddv_ex2 call with the attention scratch"""
-        L = E.lib()
-        full = stages == 'full'
-        if not hasattr(L, 'p2v_forward_ddv_ex2'):
-            raise RuntimeError('forward_ddv(attention=True): libp2vit_hip.so lacks p2v_forward_ddv_ex2: rebuild')
-        if full and not self.input_quant:
-            raise NotImplementedError("forward_ddv(stages='full'): no qact_input stage on an input_quant=False plan")
-        stage_set = (E.DDV_STAGES_FULL if full else E.DDV_STAGES_ENGINE) | E.DDV_STAGES_ATTN
+        # one entry point for every stage set: without P2V_DDV_STAGES_ATTN p2v_forward_ddv_ex2 is p2v_forward_ddv(_ex), and the forward's
+        # workspace does not depend on the stage set
+        stage_set = (E.DDV_STAGES_FULL if full else E.DDV_STAGES_ENGINE) | (E.DDV_STAGES_ATTN if attention else 0)
         assert len(names) == L.p2v_ddv_stage_count_ex2(self._handle, int(with_linear), stage_set)
-        B = images.shape[0]
         with torch.cuda.device(self.device):
-            nbytes = L.p2v_ddv_workspace_bytes(self._handle, n)
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                self._ws_batch = max(self._ws_batch, B)
-            ws = self._ws
-            out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
+            ws = self.workspace(B, L.p2v_ddv_workspace_bytes(self._handle, n))
+            out = self._out(None, B)
             sums = torch.empty(len(names), n, 3, dtype=torch.float64, device=self.device)
             tap = torch.empty(self.ddv_tap_bytes(n), dtype=torch.uint8, device=self.device) if (with_linear or full) else None
-            att = torch.empty(self.ddv_attn_bytes(n), dtype=torch.uint8, device=self.device)
-            E.check(L.p2v_forward_ddv_ex2(self._handle, E.ptr(images), n, cfg, n_cfg, E.ptr(out), E.ptr(ws), ws.numel(), int(with_linear), stage_set,
-                                          E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(att), att.numel(), E.ptr(sums),
-                                          E.stream_ptr(self.device)))
+            att = torch.empty(self.ddv_attn_bytes(n), dtype=torch.uint8, device=self.device) if attention else None
+            E.check(L.p2v_forward_ddv_ex2(self._handle, E.ptr(images), n, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(), int(with_linear),
+                                          stage_set, E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(att), 0 if att is None else att.numel(),
+                                          E.ptr(sums), E.stream_ptr(self.device)))
         return out, names, sums
 
     def slice_sizes(self, batch, n_streams=3):
@@ -592,6 +525,33 @@ class FrozenPlan:
         independent, so this is only a scheduling choice: kernels of one slice (e.g. a VALU-bound GELU epilogue) overlap latency-
         or MFMA-bound phases of another slice's kernels."""
         images, cfg = self._check(images, bit_config)
+        L, handle, n_cfg = E.lib(), self._handle, len(bit_config)
+        return self._run_slices(images, out, n_streams, slices, lambda: self.forward(images, bit_config, out=out),
+                                lambda xi, n_i, oi, ws, ws_n, st: L.p2v_forward(handle, xi, n_i, cfg, n_cfg, oi, ws, ws_n, -1, st))
+
+    @staticmethod
+    def slice_streams(n_slices, n_side):
+        """the stream of every slice: round robin over the ``n_side`` side streams and, as index ``n_side``, the caller's stream"""
+        return [i % (n_side + 1) for i in range(n_slices)]
+
+    def _slices(self, sizes, n_streams):
+        """what a sliced run needs, for ``_run_slices`` and ``profile_streams``: the borrowed side streams (the process's shared ones of this
+        device, never new ones) and per slice (lo, hi, stream index of ``slice_streams``, its own grow-only workspace)"""
+        n_side = min(len(sizes), max(n_streams, 1))
+        self._streams = E.side_streams(self.device, n_side)
+        self._ws_multi += [None] * (len(sizes) - len(self._ws_multi))
+        L, rows, hi = E.lib(), [], 0
+        for i, (n_i, j) in enumerate(zip(sizes, self.slice_streams(len(sizes), n_side))):
+            n = L.p2v_workspace_bytes(self._handle, n_i)
+            if self._ws_multi[i] is None or self._ws_multi[i].numel() < n:
+                self._ws_multi[i] = torch.empty(n, dtype=torch.uint8, device=self.device)
+            rows.append((hi, hi + n_i, j, self._ws_multi[i]))
+            hi += n_i
+        return self._streams, rows
+
+    def _run_slices(self, images, out, n_streams, slices, whole, launch):
+        """the body of ``forward_streams`` / ``forward_uint8_streams`` behind their input checks: ``whole()`` runs a batch that stays in one
+        piece, ``launch(images_ptr, n, out_ptr, ws_ptr, ws_bytes, stream_ptr)`` enqueues one slice (``engine.run_on_streams``)"""
         B = images.shape[0]
         n_streams = min(n_streams, E.compute_side_streams(self.device))      # (one less while an input pipeline copies on engine.copy_stream)
         sizes = list(slices) if slices is not None else self.slice_sizes(B, n_streams)
@@ -599,58 +559,26 @@ class FrozenPlan:
             raise AssertionError('slices %r do not cover a batch of %d' % (sizes, B))
         self._check_out(out, B)
         if len(sizes) == 1:
-            return self.forward(images, bit_config, out=out)
-        L, handle, n_cfg = E.lib(), self._handle, len(bit_config)
-        return self._run_slices(images, sizes, out, n_streams,
-                                lambda xi, n_i, oi, ws, ws_n, st: L.p2v_forward(handle, xi, n_i, cfg, n_cfg, oi, ws, ws_n, -1, st))
-
-    def _run_slices(self, images, sizes, out, n_streams, launch):
-        """the scheduling of ``forward_streams``: contiguous batch slices (``sizes``, more than one) on their own workspaces, round robin
-        over the side streams and the caller's stream; ``launch(images_ptr, n, out_ptr, ws_ptr, ws_bytes, stream_ptr)`` enqueues one slice"""
+            return whole()
         with torch.cuda.device(self.device):
-            n_side = min(len(sizes), max(n_streams, 1))
-            self._streams = E.side_streams(self.device, n_side)         # the process's shared side streams of this device, never new ones
-            if getattr(self, '_ws_multi', None) is None or len(self._ws_multi) < len(sizes):
-                self._ws_multi = (getattr(self, '_ws_multi', None) or []) + [None] * (len(sizes) - len(getattr(self, '_ws_multi', None) or []))
-            cur = torch.cuda.current_stream(self.device)
-            L = E.lib()
-            used = []
-            lo = hi = 0
-            per_stream = [[] for _ in range(n_side + 1)]             # the p2v_forward calls of every stream, in slice order
-            for i, n_i in enumerate(sizes):
-                lo, hi = hi, hi + n_i
-                j = i % (n_side + 1)                                 # round robin over the side streams and the caller's stream
-                st = self._streams[j] if j < n_side else cur
-                n = L.p2v_workspace_bytes(self._handle, n_i)
-                if self._ws_multi[i] is None or self._ws_multi[i].numel() < n:
-                    self._ws_multi[i] = torch.empty(n, dtype=torch.uint8, device=self.device)
-                if st is not cur and st not in used:
-                    st.wait_stream(cur)
-                    used.append(st)
-                per_stream[j].append((E.ptr(images[lo:hi]), n_i, E.ptr(out[lo:hi]), E.ptr(self._ws_multi[i]), self._ws_multi[i].numel(),
-                                      C.c_void_p(st.cuda_stream)))
-            dev_index = self.device.index
-
-            def enqueue(calls, worker):
-                if worker:
-                    torch.cuda.set_device(dev_index)                 # (the current device is a per-thread setting)
-                for xi, n_i, oi, ws, ws_n, st_ptr in calls:
-                    E.check(launch(xi, n_i, oi, ws, ws_n, st_ptr))
-
-            # One host thread per side stream (the C call releases the interpreter lock; p2v_forward only reads the plan): the four launch
-            # sequences reach their queues together instead of one after the other - a synchronous step (forward, then read the logits) takes
-            # 2.61 instead of 2.79 ms at DeiT-S / 256, and back-to-back steps 2.43 instead of 2.48 ms (profiles/r04_threaded_enqueue.txt)
-            if E.THREADED_ENQUEUE and not torch.cuda.is_current_stream_capturing():
-                futs = [E.enqueue_pool().submit(enqueue, calls, True) for calls in per_stream[:n_side] if calls]
-                enqueue(per_stream[n_side], False)
-                for f in futs:
-                    f.result()
-            else:
-                for calls in per_stream:
-                    enqueue(calls, False)
-            for st in used:
-                cur.wait_stream(st)
+            side, rows = self._slices(sizes, n_streams)
+            jobs = [[] for _ in range(len(side) + 1)]                 # the calls of every stream, in slice order
+            for lo, hi, j, ws in rows:
+                args = (E.ptr(images[lo:hi]), hi - lo, E.ptr(out[lo:hi]), E.ptr(ws), ws.numel())
+                jobs[j].append(lambda st, args=args: E.check(launch(*args, C.c_void_p(st.cuda_stream))))
+            E.run_on_streams(self.device, side, jobs)
         return out
+
+    def _profile_buffers(self):
+        n_max = 7 * self.depth + 10
+        return (C.c_float * n_max)(), (C.c_int32 * n_max)(), n_max
+
+    @staticmethod
+    def _profile_rows(n, ms, kind):
+        """[(kind_name, ms), ...] of the ``n`` intervals a profiling call has filled in (or its error)"""
+        if n < 0:
+            E.check(n)
+        return [(E.KERNEL_KINDS[kind[i]], float(ms[i])) for i in range(min(n, len(ms)))]
 
     def profile(self, images, bit_config):
         """per-launch times (ms, HIP events on the launch stream) of one forward: [(kind_name, ms), ...]; the last entry, 'event_gap', is an
@@ -658,16 +586,11 @@ class FrozenPlan:
         images, cfg = self._check(images, bit_config)
         B = images.shape[0]
         with torch.cuda.device(self.device):
-            ws = self.workspace(B)
-            out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
-            n_max = 7 * self.depth + 10
-            ms = (C.c_float * n_max)()
-            kind = (C.c_int32 * n_max)()
+            ws, out = self.workspace(B), self._out(None, B)
+            ms, kind, n_max = self._profile_buffers()
             n = E.lib().p2v_forward_profile(self._handle, E.ptr(images), B, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(),
                                             E.stream_ptr(self.device), ms, kind, n_max)
-        if n < 0:
-            E.check(n)
-        return [(E.KERNEL_KINDS[kind[i]], float(ms[i])) for i in range(min(n, n_max))]
+        return self._profile_rows(n, ms, kind)
 
     def profile_streams(self, images, bit_config, n_streams=3, slices=None, rounds=3):
         """per-launch times UNDER OVERLAP: the slices of ``forward_streams`` run concurrently on their streams, each with HIP events
@@ -681,39 +604,30 @@ class FrozenPlan:
         if len(sizes) == 1:
             per = self.profile(images, bit_config)
             return [per], sum(ms for _, ms in per)
-        out = torch.empty(B, self.arch['num_classes'], dtype=torch.float32, device=self.device)
+        out = self._out(None, B)
         L = E.lib()
-        n_max = 7 * self.depth + 10
         with torch.cuda.device(self.device):
-            self.forward_streams(images, bit_config, out, n_streams, sizes)          # streams and workspaces exist
+            self.forward_streams(images, bit_config, out, n_streams, sizes)          # (refuses slices that do not cover the batch; warms up)
             torch.cuda.synchronize(self.device)
-            cur = torch.cuda.current_stream(self.device)
-            n_side = min(len(sizes), max(n_streams, 1))
+            side, rows = self._slices(sizes, n_streams)
+            streams = side + [torch.cuda.current_stream(self.device)]
             tokens = []
             try:
                 for r in range(rounds):
-                    lo = hi = 0
                     row = []
                     tokens.append(row)
-                    for i, n_i in enumerate(sizes):
-                        lo, hi = hi, hi + n_i
-                        j = i % (n_side + 1)
-                        st = self._streams[j] if j < n_side else cur
+                    for lo, hi, j, ws in rows:
                         tok = C.c_void_p()
-                        E.check(L.p2v_forward_profile_begin(self._handle, E.ptr(images[lo:hi]), n_i, cfg, len(bit_config), E.ptr(out[lo:hi]),
-                                                            E.ptr(self._ws_multi[i]), self._ws_multi[i].numel(), C.c_void_p(st.cuda_stream), C.byref(tok)))
+                        E.check(L.p2v_forward_profile_begin(self._handle, E.ptr(images[lo:hi]), hi - lo, cfg, len(bit_config), E.ptr(out[lo:hi]),
+                                                            E.ptr(ws), ws.numel(), C.c_void_p(streams[j].cuda_stream), C.byref(tok)))
                         row.append(tok)
                 res = []
                 for row in tokens:
                     per = []
                     for j, tok in enumerate(row):
-                        ms = (C.c_float * n_max)()
-                        kind = (C.c_int32 * n_max)()
+                        ms, kind, n_max = self._profile_buffers()
                         row[j] = None                                                     # ended (also when the call below fails)
-                        n = L.p2v_forward_profile_end(tok, ms, kind, n_max)
-                        if n < 0:
-                            E.check(n)
-                        per.append([(E.KERNEL_KINDS[kind[i]], float(ms[i])) for i in range(min(n, n_max))])
+                        per.append(self._profile_rows(L.p2v_forward_profile_end(tok, ms, kind, n_max), ms, kind))
                     res.append(per)
             finally:                         # a failed begin / end must not leak the tokens (events + bookkeeping) already handed out
                 for row in tokens:

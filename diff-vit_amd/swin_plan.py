@@ -746,32 +746,26 @@ class SwinPlan:
         if sum(slices) != B or min(slices) < 1:
             raise AssertionError('slices %r do not cover a batch of %d' % (list(slices), B))
         self._streams = E.side_streams(self.device, n_streams)          # the process's shared side streams of this device (engine.side_streams)
-        cur = torch.cuda.current_stream(self.device)
-        parts, lo = [], 0
-        for i, n_i in enumerate(slices):
-            parts.append(images[lo:lo + n_i])
-            lo += n_i
-        for st in self._streams[:min(n_streams, len(slices))]:
-            st.wait_stream(cur)
-
-        def on_side_stream(i, worker):
-            if worker:
-                torch.cuda.set_device(self.device)     # (current device and current stream are per-thread settings)
-            with torch.cuda.stream(self._streams[i]):
-                return replay(parts[i], i + 1)
-
-        # one host thread per side stream once the launch sequences are recorded (the replay is one C call of ~1 ms of host time per slice),
-        # like FrozenPlan.forward_streams; slices beyond the side streams run on the caller's own stream (slot 0: its single-stream record)
         n_side = min(n_streams, len(slices))
+        parts = images.split(list(slices))
+        outs = [None] * len(parts)
+
+        # side slice i on side stream i with its own recording (slot i + 1); slices beyond the side streams run on the caller's own stream
+        # (slot 0: its single-stream record).  Worker threads (engine.run_on_streams) once the launch sequences are recorded: the replay is
+        # one C call of ~1 ms of host time per slice
+        def job(i):
+            def on_side_stream(st):
+                with torch.cuda.stream(st):            # (the current stream is a per-thread setting)
+                    outs[i] = replay(parts[i], i + 1)
+
+            def on_callers_stream(st):
+                outs[i] = replay(parts[i], 0)
+            return on_side_stream if i < n_side else on_callers_stream
+
+        jobs = [[job(i)] for i in range(n_side)] + [[job(i) for i in range(n_side, len(parts))]]
         recorded = all((parts[i].shape[0], i + 1, True) in self._recorded for i in range(n_side))
-        if E.THREADED_ENQUEUE and recorded and not torch.cuda.is_current_stream_capturing():
-            futs = [E.enqueue_pool().submit(on_side_stream, i, True) for i in range(n_side)]
-            tail = [replay(xi, 0) for xi in parts[n_side:]]
-            outs = [f.result() for f in futs] + tail
-        else:
-            outs = [on_side_stream(i, False) for i in range(n_side)] + [replay(xi, 0) for xi in parts[n_side:]]
-        for st in self._streams[:min(n_streams, len(slices))]:
-            cur.wait_stream(st)
+        E.run_on_streams(self.device, self._streams[:n_side], jobs, threads=recorded)
+        cur = torch.cuda.current_stream(self.device)
         for o in outs:
             o.record_stream(cur)
         return torch.cat(outs, 0)
