@@ -211,8 +211,8 @@ def main(argv=None):
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--device', default='cuda')
     p.add_argument('--result-name', default='cka_result')
-    p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT)')
-    p.add_argument('--no-lis', action='store_true', help='Config(lis=False): float softmax (ViT / DeiT)')
+    p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT; a Swin model needs ptf)')
+    p.add_argument('--no-lis', action='store_true', help='Config(lis=False): float softmax (ViT / DeiT and Swin)')
     args = p.parse_args(argv)
     device = torch.device(args.device)
     fp = harness.str2model(args.model)(cfg=Config(not args.no_ptf, not args.no_lis, 'minmax'))

@@ -1336,6 +1336,32 @@ int p2v_window_attention_taps(const int8_t* qkv, int batch, int tokens_per_image
                           qact2_codes, probs_k, pitch);
 }
 
+// Config(lis=False) of a Swin plan: the table softmax behind the qact2 codes.  Every refusal comes before the launch
+int p2v_window_softmax_attention(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                                 const uint32_t* table, int8_t* out, void* stream) {
+  const char* who = "p2v_window_softmax_attention";
+  if (!qkv || !wa || !table || !out || !wa->table_codes || !wa->win_index) return fail(P2V_E_ARG, "%s: null argument", who);
+  if ((uintptr_t)qkv % 16 || (uintptr_t)out % 4 || (uintptr_t)table % 4 || (uintptr_t)wa->win_index % 4)
+    return fail(P2V_E_ARG, "%s: qkv 16-byte, out / table / win_index 4-byte aligned", who);
+  if (batch <= 0 || tokens_per_image <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "%s: bad shape", who);
+  if (head_dim != 32) return fail(P2V_E_UNSUPPORTED, "%s: head_dim must be 32", who);
+  if (wa->ws < 1 || wa->ws > 12 || wa->n_windows < 1 || wa->ws * wa->ws * wa->n_windows > tokens_per_image)
+    return fail(P2V_E_SHAPE, "%s: window size must be 1..12 and windows must fit the token count", who);
+  const float pots[5] = {wa->s_q1, wa->s_attn, wa->s_table, wa->s_q2, wa->s_q3};
+  for (float s : pots)
+    if (!is_pot(s)) return fail(P2V_E_UNSUPPORTED, "%s: activation scales must be powers of two", who);
+  if (wa->qkv_stride % 16 || wa->out_stride % 4 || (wa->qkv_stride && wa->qkv_stride < 3 * heads * head_dim) ||
+      (wa->out_stride && wa->out_stride < heads * head_dim))
+    return fail(P2V_E_SHAPE, "%s: row strides must cover a row and be 16 / 4 byte aligned", who);
+  // a masked key counts as exactly zero: 100 / s_q2 > 255 codes below every key of the region, and exp(-(100 - 255 s_q2)) 2^21 rounds to 0
+  if (wa->s_q2 > 0x1p-2f) return fail(P2V_E_UNSUPPORTED, "%s: qact2 scale %g above 2^-2 (a masked key would not round to zero)", who, wa->s_q2);
+  const float av_mul = wa->s_q1 / wa->s_q3;
+  if (!is_pot(av_mul) || av_mul > 0x1p15f || av_mul < 0x1p-40f)
+    return fail(P2V_E_UNSUPPORTED, "%s: qact1 scale / qact3 scale = %g must be a power of two in [2^-40, 2^15]", who, av_mul);
+  const WinSmArgs a{qkv, batch, tokens_per_image, heads, *wa, table, out};
+  return launch_rc(p2v_launch_window_softmax_attention(a, (hipStream_t)stream), who);
+}
+
 // the layer output fmaf(acc, colscale, bias) as dense fp32 (P2V_OP_GEMM_F32): what a QLinear / QConv2d hook sees.  The public p2v_gemm_i8
 // goes on refusing the internal epilogue kind.
 static int gemm_f32_op(const p2v_op& o, void* stream) {
@@ -1399,6 +1425,10 @@ static int run_one_op(const p2v_op& o, void* stream) {
       return cos_combine_op(o, stream);
     case P2V_OP_GEMM_F32:
       return gemm_f32_op(o, stream);
+    case P2V_OP_WINATTN_SOFTMAX:
+      // P2V_OP_WINATTN's members; lin.w_codes (a tap plane there) names the softmax table
+      return p2v_window_softmax_attention((const int8_t*)o.in, o.i0, o.i1, o.i2, o.i3, &o.wa, reinterpret_cast<const uint32_t*>(o.lin.w_codes),
+                                          (int8_t*)o.out, stream);
     default:
       return fail(P2V_E_ARG, "p2v_run_ops: unknown op kind %d", o.kind);
   }

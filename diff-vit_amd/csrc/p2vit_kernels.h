@@ -223,3 +223,13 @@ struct SmAttnArgs {
 int p2v_launch_float_layernorm(const FloatLnArgs& a, hipStream_t st);
 // head_dim 32 / 64, 1 .. P2V_MAX_TOKENS tokens; -1: no instantiation
 int p2v_launch_softmax_attention(const SmAttnArgs& a, int head_dim, hipStream_t st);
+// Swin window attention with the table softmax (p2vit_winattn_softmax.hip): Config(lis=False) of a Swin plan
+struct WinSmArgs {
+  const int8_t* qkv;
+  int B, T, H;          // images, tokens per image, heads
+  p2v_winattn wa;       // x0_int / b_int / c_int are not read
+  const unsigned* tab;  // dev [256]: fixed-point exp of (max - code) * s_q2, entries below 2^21
+  int8_t* out;
+};
+// head_dim 32, windows of 1 x 1 ... 12 x 12; -1: no instantiation
+int p2v_launch_window_softmax_attention(const WinSmArgs& a, hipStream_t st);

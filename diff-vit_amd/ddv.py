@@ -220,6 +220,9 @@ def _compute_ddv_swin(model, x, xa, bit_config, with_linear, attention=False):
     if isinstance(bit_config, (list, tuple)):
         raise NotImplementedError('compute_ddv: a Swin model has one weight width and no per-layer bit_config list '
                                   '(swin_quant.py:813-817); pass 8, 4 or None')
+    if attention and bit_config is not None and not model.cfg.INT_SOFTMAX:
+        raise NotImplementedError('compute_ddv(attention=True): under Config(lis=False) the quantized softmax is the float one, its '
+                                  'probabilities are not codes')
     dev = _device_of(model)
     x, xa = x.to(dev).float(), xa.to(dev).float()
     quant_state = model.quant and all(m.quant and not m.calibrate for m in model._q_modules())
@@ -392,9 +395,12 @@ def main(argv=None):
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--device', default='cuda')
     p.add_argument('--result-name', default='ddv_result')
-    p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT)')
-    p.add_argument('--no-lis', action='store_true', help='Config(lis=False): float softmax (ViT / DeiT; not with --attention)')
+    p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT; a Swin model needs ptf)')
+    p.add_argument('--no-lis', action='store_true', help='Config(lis=False): float softmax (ViT / DeiT and Swin; not with --attention)')
     args = p.parse_args(argv)
+    if args.attention and args.no_lis and args.model.startswith('swin'):      # refused before anything is built
+        raise NotImplementedError('--attention --no-lis: under Config(lis=False) the quantized softmax of a Swin model is the float one, '
+                                  'its probabilities are not codes')
     device = torch.device(args.device)
     fp = harness.str2model(args.model)(cfg=Config(not args.no_ptf, not args.no_lis, 'minmax'))
     is_swin = harness._is_swin(fp)

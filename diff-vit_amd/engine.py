@@ -82,6 +82,7 @@ class Block(C.Structure):
 
 OP_PATCHIFY, OP_GEMM, OP_LAYERNORM, OP_WINATTN, OP_MERGE, OP_AVGPOOL, OP_LN_GEMM = range(7)
 OP_COS, OP_COS_COMBINE, OP_GEMM_F32 = 7, 8, 9      # one DDV stage / the closing combine / a dense fp32 layer output (op table of include/p2vit.h)
+OP_WINATTN_SOFTMAX = 10                           # window attention with the table softmax (Config(lis=False)): lin.w_codes names the table
 
 
 class Op(C.Structure):
@@ -211,6 +212,8 @@ def lib():
         L.p2v_plan_set_float_ops.argtypes = [_p, _i, _i]
         L.p2v_plan_set_float_block.argtypes = [_p, _i, C.POINTER(FloatBlock)]
         L.p2v_plan_set_float_head.argtypes = [_p, C.POINTER(FloatLn)]
+    if hasattr(L, 'p2v_window_softmax_attention'):      # Swin Config(lis=False), additive
+        L.p2v_window_softmax_attention.argtypes = [_p, _i, _i, _i, _i, C.POINTER(WinAttn), _p, _p, _p]
     if hasattr(L, 'p2v_freeze_weights'):          # the weight freeze is additive, found by its symbols
         L.p2v_freeze_bytes.argtypes = [_i, _i, _i]
         L.p2v_freeze_bytes.restype = C.c_size_t

@@ -31,8 +31,9 @@ def build_parser():
     p.add_argument('--quant', default=False, action='store_true')
     p.add_argument('--ptf', default=True)
     p.add_argument('--lis', default=True)
-    p.add_argument('--no-ptf', dest='ptf', action='store_false', help='Config(ptf=False): layer-wise QActs around a float LayerNorm')
-    p.add_argument('--no-lis', dest='lis', action='store_false', help='Config(lis=False): float softmax instead of the log-int-softmax')
+    p.add_argument('--no-ptf', dest='ptf', action='store_false', help='Config(ptf=False): layer-wise QActs around a float LayerNorm (ViT / DeiT; a Swin model needs ptf)')
+    p.add_argument('--no-lis', dest='lis', action='store_false',
+                   help='Config(lis=False): float softmax instead of the log-int-softmax (ViT / DeiT and Swin)')
     p.add_argument('--quant-method', default='minmax', choices=['minmax', 'ema', 'omse', 'percentile'])
     p.add_argument('--mixed', default=False, action='store_true')
     p.add_argument('--calib-batchsize', default=50, type=int, help='batchsize of calibration set')

@@ -335,10 +335,12 @@ class SwinTransformer(nn.Module):
         from .swin_plan import SwinPlan
         if not self.input_quant:
             raise NotImplementedError('the HIP engine fuses qact_input into the patch gather: input_quant=True models only')
-        if not (self.cfg.INT_NORM and self.cfg.INT_SOFTMAX):
-            raise NotImplementedError('the HIP engine implements the ptf=True, lis=True configuration')
+        if not self.cfg.INT_NORM:
+            raise NotImplementedError('the HIP engine runs a Swin model with ptf=True only (lis=True or False): Config(ptf=False) needs a '
+                                      'float LayerNorm the Swin engine does not have')
         dev = device or self.head.weight.device
-        self._plan = SwinPlan(self.arch, dict(self.state_dict()), self.export_calib(), device=dev, in_chans=self.in_chans, bits=bits, pack4=pack4)
+        self._plan = SwinPlan(self.arch, dict(self.state_dict()), self.export_calib(), device=dev, in_chans=self.in_chans, bits=bits, pack4=pack4,
+                              int_softmax=bool(self.cfg.INT_SOFTMAX))
         return self._plan
 
     # ---- per-layer widths -----------------------------------------------------------------------------------------------

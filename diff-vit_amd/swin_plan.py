@@ -1,6 +1,7 @@
 """Frozen integer plan of a calibrated Swin model: int8 weight codes and per-channel requant constants on the GPU, and a forward
 that is a fixed sequence of HIP kernels called through the C ABI (``p2v_quantize_patchify``, ``p2v_gemm_i8``,
-``p2v_int_layernorm``, ``p2v_window_attention``, ``p2v_patch_merge_gather``, ``p2v_avgpool_quant``).  Window partition, cyclic
+``p2v_int_layernorm``, ``p2v_window_attention`` - under Config(lis=False) ``p2v_window_softmax_attention`` -, ``p2v_patch_merge_gather``,
+``p2v_avgpool_quant``).  Window partition, cyclic
 shift and their inverses are index tables consumed by the attention kernel; nothing runs on the CPU and nothing falls back.
 
 Call order = swin_quant.py (forward_features :790-811, SwinTransformerBlock.forward :351-399, PatchMerging.forward :438-461).
@@ -36,12 +37,16 @@ class SwinPlan:
     The plan holds the fp32 weights on the GPU and freezes the codes of a (layer, width, layout) with ``p2v_freeze_weights`` when a
     forward first asks for them, so ``forward(..., bit_config=[...])`` takes one width per layer - in the order of ``linear_tap_names()`` -
     without rebuilding anything.  ``pack4``: 4-bit layers of the fused forward stream packed codes (two per byte); False keeps them
-    one per byte (A/B comparison).  The tapped / model-diff sequences always read int8-stored codes."""
+    one per byte (A/B comparison).  The tapped / model-diff sequences always read int8-stored codes.
+    ``int_softmax=False`` (Config(lis=False)): every window-attention record of every sequence is ``P2V_OP_WINATTN_SOFTMAX`` - the float
+    softmax behind the qact2 codes as a 256-entry fixed-point table per block (``plan.softmax_table`` of the block's qact2 scale), which
+    needs that scale to be at most 2^-2 (``NotImplementedError`` here otherwise, naming the layer)."""
 
-    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, bits=8, pack4=True):
+    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, bits=8, pack4=True, int_softmax=True):
         if bits not in (4, 8):
             raise KeyError('int%s' % (bits,))          # (the weight scale a width has none of: what the lookup below raised)
         self.arch, self.device, self.in_chans, self.bits, self.pack4 = dict(arch), torch.device(device), in_chans, bits, bool(pack4)
+        self.int_softmax = bool(int_softmax)
         if self.device.type != 'cuda':
             raise RuntimeError('SwinPlan needs a GPU device: the quantized forward has no CPU path')
         if self.device.index is None:
@@ -238,6 +243,14 @@ class SwinPlan:
                 b['wa'] = E.WinAttn(s_q1, float(np.float32(32 ** -0.5)), self._pot(p + 'attn.qact_attn1'), self._pot(p + 'attn.qact_table'),
                                     s_q2, s_q3, x0, bb, cc, E.ptr(b['tab']), E.ptr(b['idx']),
                                     E.ptr(b['reg']) if b['reg'] is not None else None, wsz, idx.shape[0])
+                b['sm_tab'] = None
+                if not self.int_softmax:
+                    # a masked key is exactly zero only while 100 / s_q2 > 255 codes and exp(-(100 - 255 s_q2)) 2^21 rounds to 0
+                    if s_q2 > 2.0 ** -2:
+                        raise NotImplementedError('%sattn.qact2: scale %g above 2^-2, the table softmax of Config(lis=False) needs a masked '
+                                                  'key to round to zero' % (p, s_q2))
+                    from .plan import softmax_table
+                    b['sm_tab'] = self._dev(torch.from_numpy(softmax_table(s_q2).astype(np.int32)), torch.int32)
                 b['proj'] = self._linear(p + 'attn.proj', s_q3)
                 s_b2 = c[p + 'qact2'].reshape(-1)
                 b['proj_epi'] = self._resid_epi(self._pot(p + 'attn.qact4'), s_res, s_b2, Cc, b['proj'])
@@ -298,6 +311,9 @@ class SwinPlan:
         moves the recording to another list.  Every other sequence runs the plan's default width on int8-stored codes (the RESID mid-code
         tap and the records of ``p2v_gemm_i8`` behind it take those)."""
         a = self.arch
+        if attention and not self.int_softmax:
+            raise NotImplementedError('the attention stages of the DDV need the log-int-softmax: the probabilities of the float softmax '
+                                      '(Config(lis=False)) are not codes')
         if not fused or cfg is None:
             cfg = (self.bits,) * len(self._names)
         lin_ops = []
@@ -462,6 +478,8 @@ class SwinPlan:
                 o.i0, o.i1, o.i2, o.i3 = B, T, b['heads'], 32
                 o.wa = b['wa']
                 o.wa.out_stride = att.shape[1]
+                if b['sm_tab'] is not None:  # Config(lis=False): the table softmax behind the same qact2 codes; the table in lin.w_codes
+                    o.kind, o.lin.w_codes = E.OP_WINATTN_SOFTMAX, E.ptr(b['sm_tab'])
                 if planes is not None:       # the tapped launch (op table of include/p2vit.h: members the record did not use before)
                     o.lin.w_codes, o.lin.w_frag, o.ep.tap_out, o.ldo = E.ptr(planes[0]), E.ptr(planes[1]), E.ptr(planes[2]), pitch
                 ops.append(o)
@@ -775,5 +793,6 @@ class SwinPlan:
         images = self._check_images(images)
         _, ms = self._replay(images, 0, profile=True)
         r = self._recorded[(images.shape[0], 0, True)]
-        names = ('patchify', 'gemm', 'layernorm', 'window_attention', 'merge_gather', 'avgpool', 'ln_gemm')
+        names = {E.OP_PATCHIFY: 'patchify', E.OP_GEMM: 'gemm', E.OP_LAYERNORM: 'layernorm', E.OP_WINATTN: 'window_attention',
+                 E.OP_MERGE: 'merge_gather', E.OP_AVGPOOL: 'avgpool', E.OP_LN_GEMM: 'ln_gemm', E.OP_WINATTN_SOFTMAX: 'window_softmax_attention'}
         return [(names[r['ops'][i].kind], int(r['ops'][i].epi), ms[i]) for i in range(r['n'])]

@@ -69,7 +69,8 @@
  *   - log-int-softmax constants: c_int < 2^24 (qact_attn1 scale >= 2^-11);
  *   - Config(ptf=False) / Config(lis=False) of a ViT / DeiT plan (p2v_plan_set_float_ops, at the end of this header): the float LayerNorm for
  *     16 .. 2048 channels under one power-of-two input scale; the table-softmax attention for head_dim 32 / 64 and up to P2V_MAX_TOKENS
- *     tokens.  Swin plans run the ptf = True, lis = True configuration only.
+ *     tokens.  Swin plans run ptf = True; lis = False through p2v_window_softmax_attention (head_dim 32, windows up to 12 x 12, qact2
+ *     scale <= 2^-2); Config(ptf=False) of a Swin model has no float LayerNorm on the engine and stays refused.
  */
 #ifndef P2VIT_H
 #define P2VIT_H
@@ -552,9 +553,13 @@ int p2v_avgpool_quant(const int8_t* x, int batch, int tokens, int C, float s_in,
  *   P2V_OP_WINATTN    optionally names the planes of p2v_window_attention_taps in members the kind did not read before (all NULL / 0 in
  *                     an earlier record: the untapped launch): lin.w_codes the qact_attn1 plane, lin.w_frag the qact2 plane, ep.tap_out the
  *                     exponent plane (all three written as int8_t*), ldo the pitch
- *   P2V_OP_COS        i1 may be P2V_COS_LOG2K (the exponent plane; lin.colscale must be NULL) */
+ *   P2V_OP_COS        i1 may be P2V_COS_LOG2K (the exponent plane; lin.colscale must be NULL)
+ *   P2V_OP_WINATTN_SOFTMAX  p2v_window_softmax_attention: the members of P2V_OP_WINATTN (in, out; i0 batch, i1 tokens per image, i2 heads,
+ *                     i3 head_dim; wa), and lin.w_codes - a tap plane of P2V_OP_WINATTN, which an untapped launch does not read - names
+ *                     the softmax table (written as const uint32_t*, dev [256]).  The kind has no taps: lin.w_frag, ep.tap_out and ldo
+ *                     are not read */
 enum { P2V_OP_PATCHIFY = 0, P2V_OP_GEMM = 1, P2V_OP_LAYERNORM = 2, P2V_OP_WINATTN = 3, P2V_OP_MERGE = 4, P2V_OP_AVGPOOL = 5, P2V_OP_LN_GEMM = 6,
-       P2V_OP_COS = 7, P2V_OP_COS_COMBINE = 8, P2V_OP_GEMM_F32 = 9 };
+       P2V_OP_COS = 7, P2V_OP_COS_COMBINE = 8, P2V_OP_GEMM_F32 = 9, P2V_OP_WINATTN_SOFTMAX = 10 };
 typedef struct p2v_op {
   int32_t kind, epi;
   const void* in;
@@ -895,6 +900,22 @@ typedef struct p2v_float_block {
 int p2v_plan_set_float_ops(p2v_plan* plan, int float_norm, int float_softmax);
 int p2v_plan_set_float_block(p2v_plan* plan, int block, const p2v_float_block* blk);
 int p2v_plan_set_float_head(p2v_plan* plan, const p2v_float_ln* final_ln);
+
+/* Swin plans run ptf = True; lis = False through p2v_window_softmax_attention (additive, found by its symbol): p2v_window_attention up to and
+ * including the qact2 codes c_ij (layouts, strides, window addressing, region ids and the output footprint are that entry point's: the
+ * padding behind out_stride rows is never written), then, with U_i the keys of query i's shifted-window region (every key of the window
+ * when wa->region is NULL; the row's own token is always in it),
+ *     m_i = max_{j in U_i} c_ij;  E_ij = table[m_i - c_ij] for j in U_i, 0 for every other key;  num_ic = sum_j E_ij v_jc;  den_i = sum_j E_ij
+ *     out_ic = clamp(rne((double(num_ic) / double(den_i)) (s_q1 / s_q3)), -128, 127)                                  (one IEEE fp64 division)
+ * A masked key is exactly zero because the reference's -100 lies 100 / s_q2 >= 400 codes below every key of U_i and exp(-(100 - 255 s_q2)) 2^21
+ * rounds to 0: that needs s_q2 <= 2^-2.  table: dev uint32 [256] with p2v_softmax_attention's entry rules (every entry below 2^21,
+ * table[0] > 0; the plan builds min(rne(exp(-s_q2 d) 2^21), 2^21 - 1) in fp64 on the host).  wa->x0_int / b_int / c_int are ignored.
+ * P2V_E_UNSUPPORTED: head_dim other than 32, s_q2 > 2^-2, s_q1 / s_q3 outside [2^-40, 2^15] or a scale that is no power of two;
+ * P2V_E_SHAPE: ws outside 1 .. 12, windows beyond the token count, bad strides; P2V_E_ARG: a null pointer, qkv not 16-byte or out / table /
+ * win_index not 4-byte aligned.  All before any launch.  Config(ptf=False) of a Swin model (a float LayerNorm of up to 3072 channels) is
+ * not on the engine. */
+int p2v_window_softmax_attention(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                                 const uint32_t* table, int8_t* out, void* stream);
 
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
