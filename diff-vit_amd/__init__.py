@@ -44,6 +44,8 @@ from . import ddv  # noqa: F401
 from .ddv import AttackPGD, compute_ddv, gen_adv_inputs  # noqa: F401
 from . import score  # noqa: F401
 from .score import DeviceMeter, score_rows_reference  # noqa: F401
+from . import stats  # noqa: F401
+from .stats import StageStats, code_stats_cpu, compute_stats  # noqa: F401
 from . import profiling  # noqa: F401
 from .profiling import gen_profiling_inputs_in_blackbox, metrics_output_diversity  # noqa: F401
 
@@ -53,4 +55,4 @@ __all__ = ['BIT_TYPE_DICT', 'QAct', 'QConv2d', 'QIntLayerNorm', 'QIntSoftmax', '
            'swin_small_patch4_window7_224', 'swin_base_patch4_window7_224', 'swin_base_patch4_window12_384',
            'swin_large_patch4_window12_384', 'SwinPlan', 'get_activations', 'MinibatchCKA',
            'MinibatchAdvCKA', 'compute_cka', 'compute_ddv', 'gen_adv_inputs', 'AttackPGD', 'DeviceMeter', 'score_rows_reference',
-           'gen_profiling_inputs_in_blackbox', 'metrics_output_diversity']
+           'gen_profiling_inputs_in_blackbox', 'metrics_output_diversity', 'compute_stats', 'StageStats', 'code_stats_cpu']

@@ -577,7 +577,32 @@ struct DdvCtx {
   int stage;
   float* scratch = nullptr;       // P2V_DDV_STAGES_FULL: the same buffer, for the fp32 LayerNorm values (set whatever with_linear says); null = the engine stages
   int8_t* attn = nullptr;         // P2V_DDV_STAGES_ATTN: the two planes of one block's attention taps (p2v_ddv_attn_scratch_bytes); null = no such stages
+  struct StatsCtx* stats = nullptr;   // p2v_forward_stats: the stage sites reduce all n samples into records instead of pairs into cosines
 };
+// p2v_forward_stats: stage k's record lies at the running offset in the arena; a layout pass (no launches) lists the records instead
+struct StatsStage { size_t off; int cols, kind; const float* scale; };
+struct StatsCtx {
+  char* arena;
+  size_t bytes, off;
+  std::vector<StatsStage>* layout;    // non-null: the layout pass
+};
+static int stats_check(const p2v_stat_layer& a, const void* rec, bool aligned, const char* what, int l);
+static int stats_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st, long long sample_stride,
+                        long long row_stride) {
+  StatsCtx* s = c->stats;
+  const int kind = dtype == P2V_COS_F32 ? P2V_STAT_F32 : dtype == P2V_COS_LOG2K ? P2V_STAT_U8 : P2V_STAT_I8;      // (I8_DEQ: the codes, its scales in the layout)
+  const size_t off = s->off;
+  s->off += p2v_stats_bytes(cols);
+  ++c->stage;
+  if (s->layout) {
+    s->layout->push_back(StatsStage{off, cols, kind, scale});
+    return P2V_OK;
+  }
+  if (s->off > s->bytes) return fail(P2V_E_WORKSPACE, "p2v_forward_stats: the records need more than %zu bytes", s->bytes);
+  const p2v_stat_layer l{base, sample_stride, row_stride, c->n, rows, cols, kind};
+  const int rc = stats_check(l, s->arena + off, false, "p2v_forward_stats", c->stage - 1);
+  return rc != P2V_OK ? rc : launch_rc(p2v_launch_stats(p2v_stats_desc(l, s->arena + off), st), "stage_stats");
+}
 // sample_stride (elements): 0 = the samples are dense, rows * cols apart; else e.g. the patch rows of a [T][cols] token layout
 // row_stride (elements): 0 = dense rows; else the pitch of the attention planes
 static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st, long long sample_stride = 0,
@@ -585,6 +610,7 @@ static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype
   const size_t esz = dtype == P2V_COS_F32 ? 4 : 1;
   if (!row_stride) row_stride = cols;
   if (!sample_stride) sample_stride = (long long)rows * row_stride;
+  if (c->stats) return stats_reduce(c, base, rows, cols, dtype, scale, st, sample_stride, row_stride);
   const p2v_cos_layer l{base, reinterpret_cast<const char*>(base) + (size_t)c->n * sample_stride * esz, scale, sample_stride, row_stride, rows, cols, dtype};
   const CosDesc d = p2v_cos_desc(l, c->n, 0);        // (logits / head rows of a class count that is no multiple of 4: d.vec = 0, scalar loads)
   if ((long long)c->n * d.nsplit > c->slots)
@@ -605,7 +631,8 @@ struct FwdOpts {
   Prof* prof = nullptr;               // p2v_forward_profile / _begin: an event before every launch
   float *const *qkv_tap = nullptr, *const *fc1_tap = nullptr;      // p2v_forward_taps: fp32 qkv / fc1 outputs [block]
   float* const* lin_tap = nullptr;    // p2v_forward_linear_taps: fp32 output of linear layer [layer]
-  DdvCtx* ddv = nullptr;              // p2v_forward_ddv
+  DdvCtx* ddv = nullptr;              // p2v_forward_ddv / p2v_forward_stats (ddv->stats)
+  bool dry = false;                   // the layout pass of p2v_forward_stats: the sequence runs, no launch is made
 };
 
 // The rows a block's launches behind the qkv GEMM run on.  ln and hid hold them compact from their start (strides D and hidden) either way.
@@ -643,16 +670,19 @@ struct Fwd {
       hipEventRecord(prof->ev[prof->used++], st);
       prof->kind.push_back(kind);
     }
-    const int rc = launch();
+    const int rc = o.dry ? P2V_OK : launch();
     if (rc == P2V_OK) launched += (kind == P2V_K_LN_GEMM_QKV || kind == P2V_K_LN_GEMM_FC1) ? 2 : 1;   // a fused launch fills two slots
     return rc;
   }
   // layer-output tap of p2v_forward_linear_taps: a P2V_EPI_F32 GEMM over the layer's int8 input, still in the workspace right after the
   // layer's own launch (not counted by stop_after: the entry point that passes lin_tap runs everything)
   int lin_tap(int layer, const int8_t* A, int lda, int rows, int K, int N, const p2v_linear& lin) {
-    if (done || !o.lin_tap || !o.lin_tap[layer]) return P2V_OK;
+    if (done || o.dry || !o.lin_tap || !o.lin_tap[layer]) return P2V_OK;
     return run_gemm(P2V_EPI_F32, A, lda, rows, K, N, lin, p2v_epilogue{}, o.lin_tap[layer], N, nullptr, st);
   }
+  // a launch outside the stop_after numbering (the extra launches of the FULL stages)
+  template <class Launch>
+  int extra(Launch&& launch) { return o.dry ? P2V_OK : launch(); }
   // DDV stages (p2v_forward_ddv): the int8 codes a launch has just completed, fp32 values, and the fp32 tap that sits in the one tap buffer
   int ddv_i8(const void* buf, int rows, int cols, const float* scale) { return (done || !o.ddv) ? P2V_OK : ddv_reduce(o.ddv, buf, rows, cols, P2V_COS_I8, scale, st); }
   int ddv_f32(const void* buf, int rows, int cols) { return (done || !o.ddv) ? P2V_OK : ddv_reduce(o.ddv, buf, rows, cols, P2V_COS_F32, nullptr, st); }
@@ -811,10 +841,12 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
       int8_t *pe = f.QKV, *em = f.QKV + (size_t)f.M * D;
       GemmArgs g = gemm_args(f.P, Kp, rows_p, embed.w_codes, Kp, D, embed, p->embed_epi, f.X, D, pe);
       g.out_codes2 = em;
-      if ((rc = f.ddv_i8(f.P, p->patches, Kp, nullptr)) ||                                                        // qact_input
+      // (the statistics take the real C * P^2 columns of the patch matrix, not the zero columns up to k_pad; a cosine does not see those)
+      const int Kc = o.ddv->stats ? d.in_chans * d.patch_size * d.patch_size : Kp;
+      if ((rc = ddv_reduce(o.ddv, f.P, p->patches, Kc, P2V_COS_I8, nullptr, st, (long long)p->patches * Kp, Kp)) ||   // qact_input
           (rc = f.step(P2V_K_GEMM_EMBED, [&] { return launch_rc(p2v_launch_gemm(P2V_EPI_EMBED, g, st), "gemm_i8"); })) ||
           (rc = ddv_reduce(o.ddv, pe + D, p->patches, D, P2V_COS_I8, nullptr, st, (long long)T * D)) ||           // patch_embed.qact
-          (rc = launch_rc(p2v_launch_fill_cls(em, batch, T, D, p->embed_cls_codes, st), "fill_cls")) ||
+          (rc = f.extra([&] { return launch_rc(p2v_launch_fill_cls(em, batch, T, D, p->embed_cls_codes, st), "fill_cls"); })) ||
           (rc = f.ddv_i8(em, T, D, nullptr)))                                                                     // qact_embed
         return rc;
     } else if ((rc = f.gemm(P2V_K_GEMM_EMBED, false, P2V_EPI_EMBED, f.P, Kp, rows_p, Kp, D, embed, p->embed_epi, f.X, D))) {
@@ -849,7 +881,7 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
   if (p->float_norm) {
     if (float* vals = f.full()) {    // FULL DDV stages: the final norm once more, over every row, for its values
       const FloatLnArgs a{f.X, D, f.M, D, (double)p->final_fln.s_in, (double)p->final_fln.eps, p->final_fln.gamma, p->final_fln.beta, p->final_fln.g, f.LN, D, vals};
-      if ((rc = launch_rc(p2v_launch_float_layernorm(a, st), "float_layernorm")) || (rc = f.ddv_f32(vals, T, D))) return rc;   // norm
+      if ((rc = f.extra([&] { return launch_rc(p2v_launch_float_layernorm(a, st), "float_layernorm"); })) || (rc = f.ddv_f32(vals, T, D))) return rc;   // norm
     }
     if ((rc = f.float_layernorm(p->final_fln, (long long)T * D, batch, f.CLS, nullptr)) || (rc = f.ddv_i8(f.CLS, 1, D, nullptr))) return rc;   // qact2
   } else {
@@ -857,7 +889,7 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
       LnArgs la{f.X, D, f.M, D, p->final_ln, f.LN, D};
       la.pre = p->final_ln.pre;
       la.tap_out = vals;
-      if ((rc = launch_rc(p2v_launch_layernorm(la, st), "int_layernorm")) || (rc = f.ddv_f32(vals, T, D))) return rc;   // norm
+      if ((rc = f.extra([&] { return launch_rc(p2v_launch_layernorm(la, st), "int_layernorm"); })) || (rc = f.ddv_f32(vals, T, D))) return rc;   // norm
     }
     LnArgs lf{f.X, (long long)T * D, batch, D, p->final_ln, f.CLS, D};
     lf.pre = p->final_ln.pre;
@@ -1398,6 +1430,14 @@ static int cos_combine_op(const p2v_op& o, void* stream) {
   return launch_rc(p2v_launch_cos_combine(reinterpret_cast<const CosDesc*>(o.in), o.i1, o.i0, reinterpret_cast<const unsigned long long*>(o.lin.w_codes),
                                           reinterpret_cast<double*>(o.out), (hipStream_t)stream), "cos_combine");
 }
+// one stage of the stage statistics in a recorded sequence (addressing in the members P2V_OP_COS uses): every refusal before the launch
+static int stats_check(const p2v_stat_layer& a, const void* rec, bool aligned, const char* what, int l);
+static int stats_op(const p2v_op& o, void* stream) {
+  const long long sample = (long long)(((unsigned long long)(unsigned)o.i3 << 32) | (unsigned)o.i2);
+  const p2v_stat_layer l{o.in, sample, o.lda, o.i0, o.M, o.N, o.i1};
+  const int rc = stats_check(l, o.out, false, "P2V_OP_STATS", 0);
+  return rc != P2V_OK ? rc : launch_rc(p2v_launch_stats(p2v_stats_desc(l, o.out), (hipStream_t)stream), "stats_stage");
+}
 
 static int run_one_op(const p2v_op& o, void* stream) {
   switch (o.kind) {
@@ -1429,6 +1469,8 @@ static int run_one_op(const p2v_op& o, void* stream) {
       // P2V_OP_WINATTN's members; lin.w_codes (a tap plane there) names the softmax table
       return p2v_window_softmax_attention((const int8_t*)o.in, o.i0, o.i1, o.i2, o.i3, &o.wa, reinterpret_cast<const uint32_t*>(o.lin.w_codes),
                                           (int8_t*)o.out, stream);
+    case P2V_OP_STATS:
+      return stats_op(o, stream);
     default:
       return fail(P2V_E_ARG, "p2v_run_ops: unknown op kind %d", o.kind);
   }
@@ -1636,6 +1678,53 @@ long long p2v_cos_stage_descs(const p2v_cos_layer* layers, int n_layers, int n, 
   return w.items;
 }
 
+// ---- stage statistics (p2vit_stats.hip) ------------------------------------------------------------------------------------------------
+// aligned: the public rule (base and strides multiples of 16 bytes); the forward's own stages (logits of a class count that is no multiple
+// of 4) pass false and read with scalar loads
+static int stats_check(const p2v_stat_layer& a, const void* rec, bool aligned, const char* what, int l) {
+  if (!a.base || !rec) return fail(P2V_E_ARG, "%s: layer %d has a null plane or record", what, l);
+  if (a.dtype != P2V_STAT_I8 && a.dtype != P2V_STAT_F32 && a.dtype != P2V_STAT_U8)
+    return fail(P2V_E_ARG, "%s: layer %d: dtype %d (0 = int8, 1 = fp32, 2 = uint8)", what, l, a.dtype);
+  if (a.cols < 1) return fail(P2V_E_SHAPE, "%s: layer %d: %d cols", what, l, a.cols);
+  if (a.rows < 0 || a.samples < 0) return fail(P2V_E_ARG, "%s: layer %d: %d samples x %d rows", what, l, a.samples, a.rows);
+  if (a.row_stride < a.cols) return fail(P2V_E_ARG, "%s: layer %d: row_stride %lld < cols %d", what, l, a.row_stride, a.cols);
+  if (a.sample_stride < 0) return fail(P2V_E_ARG, "%s: layer %d: negative sample_stride %lld", what, l, a.sample_stride);
+  const long long esz = a.dtype == P2V_STAT_F32 ? 4 : 1;
+  if (aligned && ((uintptr_t)a.base % 16 || a.sample_stride * esz % 16 || a.row_stride * esz % 16))
+    return fail(P2V_E_ARG, "%s: layer %d: pointers and strides must be multiples of 16 bytes", what, l);
+  if ((uintptr_t)a.base % esz) return fail(P2V_E_ARG, "%s: layer %d: the plane is not aligned to its element", what, l);
+  if ((uintptr_t)rec % 16) return fail(P2V_E_ARG, "%s: layer %d: the record must be 16-byte aligned", what, l);
+  if ((long long)a.samples * a.rows >= (1LL << 31))
+    return fail(P2V_E_UNSUPPORTED, "%s: layer %d: %d samples x %d rows", what, l, a.samples, a.rows);
+  return P2V_OK;
+}
+
+size_t p2v_stats_bytes(int cols) { return cols < 1 ? 0 : ((size_t)2080 + (size_t)24 * cols + 15) / 16 * 16; }
+
+int p2v_stats_init(void* out, size_t bytes, int dtype, int cols, void* stream) {
+  if (!out) return fail(P2V_E_ARG, "p2v_stats_init: null record");
+  if (dtype != P2V_STAT_I8 && dtype != P2V_STAT_F32 && dtype != P2V_STAT_U8)
+    return fail(P2V_E_ARG, "p2v_stats_init: dtype %d (0 = int8, 1 = fp32, 2 = uint8)", dtype);
+  if (cols < 1 || cols > (1 << 26)) return fail(P2V_E_SHAPE, "p2v_stats_init: %d cols", cols);
+  if ((uintptr_t)out % 16) return fail(P2V_E_ARG, "p2v_stats_init: the record must be 16-byte aligned");
+  if (bytes < p2v_stats_bytes(cols)) return fail(P2V_E_WORKSPACE, "p2v_stats_init: record %zu < %zu bytes", bytes, p2v_stats_bytes(cols));
+  return launch_rc(p2v_launch_stats_init(out, p2v_stats_bytes(cols), dtype, cols, (hipStream_t)stream), "stats_init");
+}
+
+int p2v_code_stats(const p2v_stat_layer* layers, int n_layers, void* const* records, void* ws, size_t ws_bytes, void* stream) {
+  (void)ws; (void)ws_bytes;
+  if (!layers || !records || n_layers <= 0) return fail(P2V_E_ARG, "p2v_code_stats: no layers");
+  for (int l = 0; l < n_layers; ++l) {
+    const int rc = stats_check(layers[l], records[l], true, "p2v_code_stats", l);
+    if (rc != P2V_OK) return rc;
+  }
+  for (int l = 0; l < n_layers; ++l) {
+    const int rc = launch_rc(p2v_launch_stats(p2v_stats_desc(layers[l], records[l]), (hipStream_t)stream), "code_stats");
+    if (rc != P2V_OK) return rc;
+  }
+  return P2V_OK;
+}
+
 // ---- scoring of the logits (p2vit_score.hip) -------------------------------------------------------------------------------------------
 int p2v_score_logits(const float* logits, long long ld, int rows, int classes, const long long* labels, int32_t* ranks, double* loss,
                      void* stream) {
@@ -1830,4 +1919,96 @@ int p2v_forward_ddv(p2v_plan* plan, const float* images, int n, const int8_t* bi
                     size_t ws_bytes, int with_linear, float* tap_scratch, size_t tap_scratch_bytes, double* sums, void* stream) {
   return p2v_forward_ddv_ex(plan, images, n, bit_config, n_cfg, logits, ws, ws_bytes, with_linear, P2V_DDV_STAGES_ENGINE, tap_scratch,
                             tap_scratch_bytes, sums, stream);
+}
+
+// ---- stage statistics inside the fused forward: p2v_forward_ddv_ex2's sequence, stage sets and refusals, with every stage site reducing all
+// `batch` samples into its record (DdvCtx::stats) ------------------------------------------------------------------------------------------
+static int stats_stage_set_check(const p2v_plan* plan, int stage_set, const char* who) {
+  if (!plan) return fail(P2V_E_ARG, "%s: null argument", who);
+  if (stage_set < 0 || stage_set > (P2V_DDV_STAGES_FULL | P2V_DDV_STAGES_ATTN))
+    return fail(P2V_E_ARG, "%s: unknown stage_set %d (ENGINE = 0 or FULL = 1, optionally | P2V_DDV_STAGES_ATTN = 2)", who, stage_set);
+  if ((stage_set & P2V_DDV_STAGES_FULL) && !(plan->inv_s_input > 0.f))
+    return fail(P2V_E_UNSUPPORTED, "%s: the FULL stage set needs the input QAct (input_quant = False has no qact_input stage)", who);
+  if ((stage_set & P2V_DDV_STAGES_FULL) && !plan->embed_cls_codes)
+    return fail(P2V_E_STATE, "%s: the FULL stage set needs the class row of qact_embed (p2v_plan_set_embed_tap_cls)", who);
+  return P2V_OK;
+}
+
+// the layout pass: forward_impl's own sequence with no launch made, every stage site listing its record
+static int stats_layout(const p2v_plan* plan, int with_linear, int stage_set, std::vector<StatsStage>* out, size_t* total) {
+  int rc = stats_stage_set_check(plan, stage_set, "p2v_forward_stats_layout");
+  if (rc != P2V_OK) return rc;
+  void* const some = reinterpret_cast<void*>(256);      // never dereferenced: nothing is launched
+  std::vector<int8_t> cfg(plan->n_layers);
+  for (int i = 0; i < plan->n_layers; ++i) cfg[i] = plan->lin_set[bit_index(8)][i] ? 8 : 4;
+  StatsCtx sc{nullptr, 0, 0, out};
+  DdvCtx ctx{1, nullptr, 0, nullptr, with_linear ? reinterpret_cast<float*>(some) : nullptr, 0};
+  ctx.scratch = (stage_set & P2V_DDV_STAGES_FULL) ? reinterpret_cast<float*>(some) : nullptr;
+  ctx.attn = (stage_set & P2V_DDV_STAGES_ATTN) ? reinterpret_cast<int8_t*>(some) : nullptr;
+  ctx.stats = &sc;
+  FwdOpts o;
+  o.images = reinterpret_cast<const float*>(some); o.ddv = &ctx; o.dry = true;
+  rc = forward_impl(const_cast<p2v_plan*>(plan), 1, cfg.data(), plan->n_layers, reinterpret_cast<float*>(some), some, (size_t)-1, nullptr, o);
+  if (rc == P2V_OK && total) *total = sc.off;
+  return rc;
+}
+
+size_t p2v_forward_stats_bytes(const p2v_plan* plan, int with_linear, int stage_set) {
+  std::vector<StatsStage> st;
+  size_t total = 0;
+  return stats_layout(plan, with_linear, stage_set, &st, &total) == P2V_OK ? total : 0;
+}
+
+int p2v_forward_stats_layout(const p2v_plan* plan, int with_linear, int stage_set, int max_stages, long long* offsets, int32_t* cols,
+                             int32_t* kinds, const float** scales) {
+  std::vector<StatsStage> st;
+  const int rc = stats_layout(plan, with_linear, stage_set, &st, nullptr);
+  if (rc != P2V_OK) return rc;
+  for (int k = 0; k < (int)st.size() && k < max_stages; ++k) {
+    if (offsets) offsets[k] = (long long)st[k].off;
+    if (cols) cols[k] = st[k].cols;
+    if (kinds) kinds[k] = st[k].kind;
+    if (scales) scales[k] = st[k].scale;
+  }
+  return (int)st.size();
+}
+
+int p2v_forward_stats(p2v_plan* plan, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                      size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, int8_t* attn_scratch,
+                      size_t attn_scratch_bytes, void* stats, size_t stats_bytes, void* stream) {
+  if (!plan || !stats || !ws) return fail(P2V_E_ARG, "p2v_forward_stats: null argument");
+  int rc = stats_stage_set_check(plan, stage_set, "p2v_forward_stats");
+  if (rc != P2V_OK) return rc;
+  const bool full = stage_set & P2V_DDV_STAGES_FULL, attn = stage_set & P2V_DDV_STAGES_ATTN;
+  if (batch <= 0 || batch > (1 << 29)) return fail(P2V_E_SHAPE, "p2v_forward_stats: batch = %d", batch);
+  if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_forward_stats: the workspace must be 256-byte aligned");
+  if ((uintptr_t)stats % 16) return fail(P2V_E_ARG, "p2v_forward_stats: the records must be 16-byte aligned");
+  const int n = (batch + 1) / 2;                        // the scratch sizes are the DDV call's, which counts pairs of images
+  if (full && !tap_scratch)
+    return fail(P2V_E_WORKSPACE, "p2v_forward_stats: the FULL stage set needs tap_scratch (%zu bytes) whatever with_linear says", p2v_ddv_tap_scratch_bytes(plan, n));
+  if (with_linear || full) {
+    if (!tap_scratch) return fail(P2V_E_ARG, "p2v_forward_stats: with_linear needs tap_scratch");
+    if ((uintptr_t)tap_scratch % 16) return fail(P2V_E_ARG, "p2v_forward_stats: tap_scratch must be 16-byte aligned");
+    if (tap_scratch_bytes < p2v_ddv_tap_scratch_bytes(plan, n))
+      return fail(P2V_E_WORKSPACE, "p2v_forward_stats: tap_scratch %zu < %zu bytes", tap_scratch_bytes, p2v_ddv_tap_scratch_bytes(plan, n));
+  }
+  if (attn) {
+    const size_t need = p2v_ddv_attn_scratch_bytes(plan, n);
+    if (!attn_scratch) return fail(P2V_E_ARG, "p2v_forward_stats: P2V_DDV_STAGES_ATTN needs attn_scratch (%zu bytes)", need);
+    if ((uintptr_t)attn_scratch % 16) return fail(P2V_E_ARG, "p2v_forward_stats: attn_scratch must be 16-byte aligned");
+    if (attn_scratch_bytes < need) return fail(P2V_E_WORKSPACE, "p2v_forward_stats: attn_scratch %zu < %zu bytes", attn_scratch_bytes, need);
+  }
+  StatsCtx sc{reinterpret_cast<char*>(stats), stats_bytes, 0, nullptr};
+  DdvCtx ctx{batch, nullptr, 0, nullptr, with_linear ? tap_scratch : nullptr, 0};
+  ctx.scratch = full ? tap_scratch : nullptr;
+  ctx.attn = attn ? attn_scratch : nullptr;
+  ctx.stats = &sc;
+  std::vector<float*> taps;
+  if (with_linear) {
+    taps.assign(plan->n_layers, tap_scratch);      // every linear output goes through the one buffer; the patch embedding is no stage
+    taps[0] = nullptr;
+  }
+  FwdOpts o;
+  o.images = images; o.ddv = &ctx; o.lin_tap = with_linear ? taps.data() : nullptr;
+  return forward_impl(plan, batch, bit_config, n_cfg, logits, ws, ws_bytes, stream, o);
 }

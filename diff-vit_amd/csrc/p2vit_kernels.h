@@ -172,6 +172,23 @@ int p2v_launch_pair_cosine_one(const CosDesc& d, int n, unsigned long long* part
 int p2v_launch_cos_stage(const CosDesc* desc_dev, long long items, unsigned long long* partials, hipStream_t st);
 int p2v_launch_cos_combine(const CosDesc* descs_dev, int L, int n, const unsigned long long* partials, double* sums, hipStream_t st);
 
+// stage statistics (p2vit_stats.hip): one plane into one record (p2v_code_stats / p2v_forward_stats / P2V_OP_STATS)
+struct StatsDesc {
+  const void* base;
+  void* rec;             // the record (p2v_stats_bytes(cols)), accumulated into
+  long long sample_stride, row_stride;   // in elements
+  long long flat_rows;   // samples * rows (< 2^31): the plane as one list of rows
+  int rows, cols;
+  int kind;              // P2V_STAT_*
+  int vec;               // base and strides are 16-byte aligned: whole column groups are read with one 16-byte load
+  int tiles;             // column tiles of 1024
+  int nsplit;            // row ranges; the grid is tiles * nsplit
+  int rows_per_split;    // <= 2^16
+};
+StatsDesc p2v_stats_desc(const p2v_stat_layer& l, void* rec);
+int p2v_launch_stats(const StatsDesc& d, hipStream_t st);
+int p2v_launch_stats_init(void* rec, size_t bytes, int kind, int cols, hipStream_t st);
+
 // scoring of the logits (p2vit_score.hip): one record per row, then the fold into a totals slot (p2v_score_logits / p2v_score_accumulate)
 int p2v_launch_score_rows(const float* logits, long long ld, int rows, int classes, const long long* labels, int* ranks, double* loss,
                           hipStream_t st);

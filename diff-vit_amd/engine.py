@@ -111,6 +111,16 @@ class CosLayer(C.Structure):
     _fields_ = [('a', _p), ('b', _p), ('scale', _p), ('sample_stride', _ll), ('row_stride', _ll), ('rows', _i), ('cols', _i), ('dtype', _i)]
 
 
+STAT_I8, STAT_F32, STAT_U8 = 0, 1, 2          # P2V_STAT_*: the element kinds of the stage statistics
+OP_STATS = 11                                 # one stage of the statistics in a recorded sequence (op table of include/p2vit.h)
+
+
+class StatLayer(C.Structure):
+    """``p2v_stat_layer``: one plane of ``p2v_code_stats`` (samples x rows x cols int8 codes, unsigned bytes or fp32 values; strides in
+    elements)."""
+    _fields_ = [('base', _p), ('sample_stride', _ll), ('row_stride', _ll), ('samples', _i), ('rows', _i), ('cols', _i), ('dtype', _i)]
+
+
 class P2VError(RuntimeError):
     pass
 
@@ -193,6 +203,16 @@ def lib():
         L.p2v_cos_stage_desc_bytes.restype = C.c_size_t
         L.p2v_cos_stage_descs.argtypes = [C.POINTER(CosLayer), _i, _i, _p]
         L.p2v_cos_stage_descs.restype = _ll
+    if hasattr(L, 'p2v_code_stats'):              # the stage statistics are additive, found by their symbols
+        L.p2v_stats_bytes.argtypes = [_i]
+        L.p2v_stats_bytes.restype = C.c_size_t
+        L.p2v_stats_init.argtypes = [_p, C.c_size_t, _i, _i, _p]
+        L.p2v_code_stats.argtypes = [C.POINTER(StatLayer), _i, C.POINTER(_p), _p, C.c_size_t, _p]
+        L.p2v_forward_stats_bytes.argtypes = [_p, _i, _i]
+        L.p2v_forward_stats_bytes.restype = C.c_size_t
+        L.p2v_forward_stats_layout.argtypes = [_p, _i, _i, _i, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), C.POINTER(_p)]
+        L.p2v_forward_stats.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _i, _p, C.c_size_t, _p, C.c_size_t, _p,
+                                        C.c_size_t, _p]
     if hasattr(L, 'p2v_score_logits'):            # the scoring entry points are additive, found by their symbols
         L.p2v_score_logits.argtypes = [_p, _ll, _i, _i, _p, _p, _p, _p]
         L.p2v_score_totals_bytes.argtypes = [_i]

@@ -16,6 +16,7 @@ one without the built library raises ``RuntimeError`` from ``engine.lib()``.
     torch.ops.p2vit.pair_cosine(a, b, scales)                                   per-sample cosine sums     modeldiff_p2.py:101-108
     torch.ops.p2vit.score_logits(logits, labels)                                tie-aware ranks + fp64 loss  test_quant.py:430-436, 488-501
     torch.ops.p2vit.score_accumulate(ranks, loss, ks, totals)                   running totals of a pass   test_quant.py:437-439
+    torch.ops.p2vit.code_stats(tensors)                                         per-channel ranges, histogram, sums   plot_distrib.py:30-61
 """
 import ctypes as C
 
@@ -38,6 +39,7 @@ _LIB.define('hsic_accumulate(Tensor g1, Tensor g2, Tensor(a!) acc, Tensor(b!)? s
 _LIB.define('pair_cosine(Tensor[] a, Tensor[] b, Tensor?[] scales) -> Tensor')
 _LIB.define('score_logits(Tensor logits, Tensor labels) -> (Tensor ranks, Tensor loss)')
 _LIB.define('score_accumulate(Tensor ranks, Tensor loss, int[] ks, Tensor(a!) totals) -> ()')
+_LIB.define('code_stats(Tensor[] tensors) -> Tensor[]')
 
 
 def _f32(t):
@@ -295,6 +297,76 @@ def _score_accumulate(ranks, loss, ks, totals):
                                              E.stream_ptr(ranks.device)))
 
 
+def _stat_view(t):
+    """(tensor kept alive, kind, samples, rows, cols, sample stride, row stride) of ``t`` = [samples, ..., cols] int8 codes, uint8 bytes or
+    floats for ``p2v_code_stats``.  A [samples, rows, cols] view whose base and strides are 16-byte aligned is read in place; anything
+    else is made contiguous, its rows padded to whole 16-byte groups when cols is no multiple (the padding is never read)."""
+    if t.dim() < 2:
+        raise AssertionError('code_stats: every tensor is [samples, ..., cols] (got shape %s)' % (tuple(t.shape),))
+    kind = {torch.int8: E.STAT_I8, torch.uint8: E.STAT_U8}.get(t.dtype, E.STAT_F32)
+    if kind == E.STAT_F32 and t.dtype != torch.float32:
+        t = t.float()
+    vec = 16 // t.element_size()
+    S, cols = t.shape[0], t.shape[-1]
+    if cols < 1:
+        raise AssertionError('code_stats: a tensor without columns (shape %s)' % (tuple(t.shape),))
+    if t.dim() == 3 and t.stride(2) == 1 and t.stride(1) % vec == 0 and t.stride(0) % vec == 0 and t.stride(1) >= cols and t.data_ptr() % 16 == 0:
+        return t, kind, S, t.shape[1], cols, t.stride(0), t.stride(1)
+    if t.numel() == 0:                      # nothing to read: the record keeps what it holds
+        return t, kind, 0, 0, cols, 0, cols
+    x = t.reshape(S, -1, cols)
+    R = x.shape[1]
+    if cols % vec or not x.is_contiguous() or x.data_ptr() % 16:
+        Cp = (cols + vec - 1) // vec * vec
+        buf = torch.empty(S, R, Cp, dtype=x.dtype, device=x.device)
+        buf[..., :cols] = x
+        x = buf
+    return x, kind, S, R, cols, R * x.shape[2], x.shape[2]
+
+
+def stats_record_bytes(cols):
+    """``p2v_stats_bytes``: 260 int64 (hist[256], count, nonfinite[3]), lo / hi [cols] 4 bytes each, sum / sumsq [cols] int64, to 16 bytes"""
+    return (2080 + 24 * cols + 15) // 16 * 16
+
+
+def _code_stats(tensors, records=None):
+    """one record (uint8 [stats_record_bytes(cols)], the layout of ``p2v_code_stats`` in include/p2vit.h) per tensor, reduced over every
+    sample and row per column of the LAST dimension.  ``records``: existing records to accumulate into (``stats.code_stats``); the op
+    itself returns fresh ones."""
+    if not tensors:
+        raise AssertionError('code_stats: no tensors')
+    dev = tensors[0].device
+    views = []
+    for k, t in enumerate(tensors):
+        if t.device != dev:
+            raise AssertionError('code_stats: every tensor must be on %s' % dev)
+        views.append(_stat_view(t))
+    L = E.lib()
+    out = []
+    with torch.cuda.device(dev):
+        st = E.stream_ptr(dev)
+        for k, v in enumerate(views):
+            if records is None:
+                rec = torch.empty(stats_record_bytes(v[4]), dtype=torch.uint8, device=dev)
+                E.check(L.p2v_stats_init(E.ptr(rec), rec.numel(), v[1], v[4], st))
+            else:
+                rec = records[k]
+                if rec.dtype != torch.uint8 or rec.numel() < stats_record_bytes(v[4]) or not rec.is_contiguous() or rec.device != dev:
+                    raise AssertionError('code_stats: record %d must be a contiguous uint8 tensor of %d bytes on %s' % (k, stats_record_bytes(v[4]), dev))
+            out.append(rec)
+        live = [k for k, v in enumerate(views) if v[0].numel() > 0]         # an empty plane launches nothing (and has no pointer)
+        if live:
+            lays = (E.StatLayer * len(live))()
+            recs = (C.c_void_p * len(live))()
+            for j, k in enumerate(live):
+                x, kind, S, R, cols, ss, rs = views[k]
+                d = lays[j]
+                d.base, d.sample_stride, d.row_stride, d.samples, d.rows, d.cols, d.dtype = x.data_ptr(), ss, rs, S, R, cols, kind
+                recs[j] = out[k].data_ptr()
+            E.check(L.p2v_code_stats(lays, len(live), recs, None, 0, st))
+    return out
+
+
 _LIB.impl('fake_quant', _fake_quant, 'CUDA')
 _LIB.impl('quantize_patchify', _quantize_patchify, 'CUDA')
 _LIB.impl('linear_requant', lambda x, w, cs, b, inv: _linear(E.EPI_REQUANT, x, w, cs, b, inv), 'CUDA')
@@ -308,6 +380,7 @@ _LIB.impl('hsic_accumulate', _hsic_accumulate, 'CUDA')
 _LIB.impl('pair_cosine', _pair_cosine, 'CUDA')
 _LIB.impl('score_logits', _score_logits, 'CUDA')
 _LIB.impl('score_accumulate', _score_accumulate, 'CUDA')
+_LIB.impl('code_stats', lambda tensors: _code_stats(tensors), 'CUDA')
 
 OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'lis_attention_rows', 'forward', 'cka_grams',
-       'hsic_accumulate', 'pair_cosine', 'score_logits', 'score_accumulate')
+       'hsic_accumulate', 'pair_cosine', 'score_logits', 'score_accumulate', 'code_stats')

@@ -228,6 +228,8 @@ class FrozenPlan:
         if hasattr(L, 'p2v_plan_set_embed_tap_cls'):      # (additive: side builds of older revisions lack it)
             E.check(L.p2v_plan_set_embed_tap_cls(self._handle, E.ptr(self._dev(_q8(W['cls_token'].reshape(D), s_e), torch.int8))))
         self.qact_pos_all_zero = not bool((_q8(W['pos_embed'], s_p) != 0).any())
+        # the one scale of every stage whose codes share it (forward_stats; the per-channel ones come with the library's layout)
+        self.stage_scales = {'qact_input': float(s_in), 'patch_embed.qact': float(s_pe), 'qact_embed': float(s_e)}
         # ---- blocks ----------------------------------------------------------------------------
         for i in range(self.depth):
             p = 'blocks.%d.' % i
@@ -243,6 +245,8 @@ class FrozenPlan:
             s_at = _need_pot(p + 'attn.qact_attn1', c[p + 'attn.qact_attn1'])
             s_a2 = _need_pot(p + 'attn.qact2', c[p + 'attn.qact2'])
             s_m1 = _need_pot(p + 'mlp.qact1', c[p + 'mlp.qact1'])
+            self.stage_scales.update({p + 'attn.qact1': float(s_q1), p + 'attn.qact_attn1': float(s_at), p + 'attn.qact2': float(s_a2),
+                                      p + 'mlp.qact1': float(s_m1)})
             for bi in range(2):
                 csb = _need_pot(p + 'attn.channel_scale', cs_a[bi])
                 sab = _need_pot(p + 'attn.qact0', s_a0[bi])
@@ -290,6 +294,7 @@ class FrozenPlan:
         # ---- head ------------------------------------------------------------------------------
         s_f = _need_pot('qact2', c['qact2'])
         s_o = _need_pot('act_out', c['act_out'])
+        self.stage_scales['qact2'] = float(s_f)
         fl = self._ln(s_res, W['norm.weight'], W['norm.bias'], s_f, s_f / s_f)
         E.check(L.p2v_plan_set_head(self._handle, C.byref(fl), float(1.0 / s_o), float(s_o)))
         if not self.int_norm:
@@ -493,6 +498,47 @@ class FrozenPlan:
                                           stage_set, E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(att), 0 if att is None else att.numel(),
                                           E.ptr(sums), E.stream_ptr(self.device)))
         return out, names, sums
+
+    def forward_stats(self, images, bit_config=None, with_linear=False, stages='engine', attention=False, into=None):
+        """p2v_forward_stats: the logits of ``images`` (any batch >= 1) and the ``stats.StageStats`` of every ``forward_ddv`` stage
+        (``ddv_stage_names``), each reduced over all images and tokens by ONE launch right behind the launch that completes the stage:
+        per channel the lowest and highest code, the integer sums, and the histogram of the codes (fp32 stages: of the exponent field).
+        ``into``: a result of an earlier call with the same arguments - the batch is accumulated into its records on the device, without
+        a host synchronisation, and it is returned.  Stage sets and refusals are ``forward_ddv``'s."""
+        from .stats import StageStats
+        images, cfg = self._check(images, bit_config)
+        B = images.shape[0]
+        L = E.lib()
+        names = self.ddv_stage_names(with_linear, stages, attention)
+        if attention and not self.int_softmax:
+            raise NotImplementedError('forward_stats(attention=True): the softmax of a lis=False plan is the float one, its probabilities are not codes')
+        full = stages == 'full'
+        if full and not self.input_quant:
+            raise NotImplementedError("forward_stats(stages='full'): no qact_input stage on an input_quant=False plan")
+        stage_set = (E.DDV_STAGES_FULL if full else E.DDV_STAGES_ENGINE) | (E.DDV_STAGES_ATTN if attention else 0)
+        key = ('plan', self.handle, bool(with_linear), stage_set)
+        n = (B + 1) // 2
+        with torch.cuda.device(self.device):
+            if into is None:
+                K = len(names)
+                off, cols, kinds, scales = (C.c_longlong * K)(), (C.c_int32 * K)(), (C.c_int32 * K)(), (C.c_void_p * K)()
+                got = L.p2v_forward_stats_layout(self._handle, int(with_linear), stage_set, K, off, cols, kinds, scales)
+                if got < 0:
+                    E.check(got)
+                assert got == K, (got, K)
+                by_ptr = {t.data_ptr(): t for t in self._keep}
+                sc = [by_ptr[scales[k]][:cols[k]] if scales[k] else self.stage_scales.get(names[k]) for k in range(K)]
+                into = StageStats.empty(names, list(cols), list(kinds), sc, self.device, offsets=list(off),
+                                        nbytes=int(L.p2v_forward_stats_bytes(self._handle, int(with_linear), stage_set)), key=key)
+            elif into.key != key or into.names != names:
+                raise AssertionError('forward_stats(into=...): the result was made by another plan or with other stages')
+            ws, out = self.workspace(B), self._out(None, B)
+            tap = torch.empty(self.ddv_tap_bytes(n), dtype=torch.uint8, device=self.device) if (with_linear or full) else None
+            att = torch.empty(self.ddv_attn_bytes(n), dtype=torch.uint8, device=self.device) if attention else None
+            E.check(L.p2v_forward_stats(self._handle, E.ptr(images), B, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(), int(with_linear),
+                                        stage_set, E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(att), 0 if att is None else att.numel(),
+                                        E.ptr(into.arena), into.arena.numel(), E.stream_ptr(self.device)))
+        return out, into
 
     def slice_sizes(self, batch, n_streams=3):
         """Batch slices of ``forward_streams`` for up to ``n_streams`` side streams plus the caller's own stream (256 -> 68 + 68 + 68 + 52).

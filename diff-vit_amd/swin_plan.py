@@ -295,7 +295,7 @@ class SwinPlan:
         return e
 
     # ---- forward -------------------------------------------------------------------------------------------------------
-    def _record(self, B, fused=True, ddv_n=0, with_linear=False, lin_taps=False, attention=False, cfg=None):
+    def _record(self, B, fused=True, ddv_n=0, with_linear=False, lin_taps=False, attention=False, cfg=None, stats=False):
         """the launch sequence of one forward at batch B as a ``p2v_op`` array with its own activation buffers (built once
         per batch size and stream slot, replayed by ``p2v_run_ops``).  ``fused``: norm1 + qkv and norm2 + fc1 of stages up to 384
         channels run as ONE launch each (``P2V_OP_LN_GEMM``: the LayerNorm output stays in LDS); the tap replay records the
@@ -307,12 +307,15 @@ class SwinPlan:
         ``attention`` (with ``ddv_n``): the window launches run tapped (the planes of ``p2v_window_attention_taps``, named in the WINATTN
         record) into three planes per stage that its blocks share - qact_attn1, qact2 (int8 codes) and the softmax exponents
         (``P2V_COS_LOG2K``) - each reduced right behind the launch.
+        ``stats`` (unfused, instead of ``ddv_n``): the same stage sites, mid codes, scratch and tapped window launches, but every site writes
+        a ``P2V_OP_STATS`` record that reduces all B samples of the live buffer into the stage's record (``forward_stats`` names the
+        records before each replay); no combine.
         ``cfg`` (fused only): the width of every layer (``bit_config()``); 4-bit layers read packed codes with ``pack4``.  ``_switch``
         moves the recording to another list.  Every other sequence runs the plan's default width on int8-stored codes (the RESID mid-code
         tap and the records of ``p2v_gemm_i8`` behind it take those)."""
         a = self.arch
         if attention and not self.int_softmax:
-            raise NotImplementedError('the attention stages of the DDV need the log-int-softmax: the probabilities of the float softmax '
+            raise NotImplementedError('the attention stages of the DDV and of the stage statistics need the log-int-softmax: the probabilities of the float softmax '
                                       '(Config(lis=False)) are not codes')
         if not fused or cfg is None:
             cfg = (self.bits,) * len(self._names)
@@ -326,7 +329,7 @@ class SwinPlan:
         P, g = a['patch_size'], self.g
         dev = self.device
         ops, taps, keep = [], [], []
-        n = ddv_n
+        n = B if stats else ddv_n           # (what the stage sites, the mid codes and the scratch are gated on)
         stages, lin_out = [], []
         scratch = None
         if n and with_linear:           # the largest single tap of the 2n images
@@ -338,6 +341,15 @@ class SwinPlan:
         def stage(name, t_, rows, cols, stride, dtype=E.COS_I8, scale=None):
             """DDV stage ``name``: per image rows x cols elements of ``t_`` (row stride ``stride`` elements: padding behind ``cols`` is never read)"""
             if not n:
+                return
+            if stats:       # one record per stage: every sample of the live buffer, the addressing in the members P2V_OP_COS uses
+                o = E.Op()
+                o.kind, o.inp = E.OP_STATS, E.ptr(t_)
+                o.i0, o.i1, o.M, o.N, o.lda = B, {E.COS_I8: E.STAT_I8, E.COS_F32: E.STAT_F32, E.COS_LOG2K: E.STAT_U8}[dtype], rows, cols, stride
+                ss = rows * stride
+                o.i2, o.i3 = ((ss & 0xffffffff) ^ 0x80000000) - 0x80000000, ss >> 32
+                stages.append((name, len(ops), (cols, o.i1, scale)))
+                ops.append(o)
                 return
             esz = 4 if dtype == E.COS_F32 else 1
             lay = E.CosLayer(E.ptr(t_), C.c_void_p(t_.data_ptr() + n * rows * stride * esz), scale, rows * stride, stride, rows, cols, dtype)
@@ -548,6 +560,11 @@ class SwinPlan:
             logits = torch.zeros(B, ldl, dtype=torch.float32, device=dev)
             o.out, o.ldo = E.ptr(logits), ldl
             stage('act_out', logits, 1, self.head['N'], ldl, E.COS_F32)
+            keep.append(logits)
+            rec.update(names=[st_[0] for st_ in stages], logits=logits)
+        if stats:
+            rec.update(stat_ops=[st_[1] for st_ in stages], stat_layout=[st_[2] for st_ in stages])
+        elif n:
             L = E.lib()
             lays = (E.CosLayer * len(stages))(*[st_[2] for st_ in stages])
             dbytes = L.p2v_cos_stage_desc_bytes()
@@ -566,8 +583,8 @@ class SwinPlan:
             o.i0, o.i1 = n, len(stages)
             o.lin.w_codes = E.ptr(partials)
             ops.append(o)
-            keep += [logits, descs, partials]
-            rec.update(names=[st_[0] for st_ in stages], sums=sums, logits=logits)
+            keep += [descs, partials]
+            rec.update(sums=sums)
         rec['ops'] = (E.Op * len(ops))(*ops)
         rec['n'] = len(ops)
         return rec
@@ -665,6 +682,43 @@ class SwinPlan:
         key = ('ddv', n, bool(with_linear)) + (('attn',) if attention else ())
         r, _ = self._replay_extra(images_2n, key, ddv_n=n, with_linear=bool(with_linear), attention=bool(attention))
         return r['logits'][:, :self.head['N']].clone(), list(r['names']), r['sums'].clone()
+
+    def forward_stats(self, x, with_linear=False, attention=False, into=None):
+        """(logits, ``stats.StageStats``) of the quantized model inside the forward, for any batch >= 1: the stages of ``forward_ddv``
+        (``ddv.swin_stage_names(depths, with_linear, attention)``), each reduced over all images and tokens by one ``P2V_OP_STATS`` record
+        right behind the launch that completes it - per channel the lowest and highest code and the integer sums, and the histogram of
+        the codes (fp32 stages: of the exponent field).  One recorded sequence, one ``p2v_run_ops`` call.  ``attention``: the window
+        launches run tapped, with the three planes.  ``into``: a result of an earlier call with the same arguments; the batch is
+        accumulated into its records on the device, without a host synchronisation."""
+        from .stats import StageStats
+        x = self._check_images(x)
+        B = x.shape[0]
+        key = ('stats', B, bool(with_linear)) + (('attn',) if attention else ())
+        with torch.cuda.device(self.device):
+            full_key = key + (self.bits,)
+            if full_key not in self._recorded:
+                self._recorded[full_key] = self._record(B, fused=False, with_linear=bool(with_linear), attention=bool(attention), stats=True)
+            r = self._recorded[full_key]
+            names = list(r['names'])
+            skey = ('swin', id(self), self.bits, bool(with_linear), bool(attention))
+            if into is None:
+                by_ptr = {t.data_ptr(): t for t in self._keep}
+                scales = []
+                for nm, (cols, kind, sc) in zip(names, r['stat_layout']):
+                    sc = getattr(sc, 'value', sc)
+                    if sc:
+                        scales.append(by_ptr[sc][:cols])
+                    else:
+                        c = self.c.get(nm) if kind == E.STAT_I8 else None
+                        scales.append(float(c.reshape(-1)[0]) if c is not None and c.numel() == 1 else None)
+                into = StageStats.empty(names, [l[0] for l in r['stat_layout']], [l[1] for l in r['stat_layout']], scales, self.device, key=skey)
+            elif into.key != skey or into.names != names:
+                raise AssertionError('forward_stats(into=...): the result was made by another plan or with other stages')
+            for k, i in enumerate(r['stat_ops']):
+                r['ops'][i].out = C.c_void_p(into.arena.data_ptr() + into.offsets[k])
+            r['ops'][0].inp = E.ptr(x)
+            E.check(E.lib().p2v_run_ops(r['ops'], r['n'], E.stream_ptr(self.device)))
+            return r['logits'][:, :self.head['N']].clone(), into
 
     def forward_linear_taps(self, images):
         """(logits, [fp32 tensors]): the output of every QConv2d / QLinear in ``named_modules`` order (patch_embed.proj; qkv, proj, fc1,

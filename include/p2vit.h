@@ -557,9 +557,12 @@ int p2v_avgpool_quant(const int8_t* x, int batch, int tokens, int C, float s_in,
  *   P2V_OP_WINATTN_SOFTMAX  p2v_window_softmax_attention: the members of P2V_OP_WINATTN (in, out; i0 batch, i1 tokens per image, i2 heads,
  *                     i3 head_dim; wa), and lin.w_codes - a tap plane of P2V_OP_WINATTN, which an untapped launch does not read - names
  *                     the softmax table (written as const uint32_t*, dev [256]).  The kind has no taps: lin.w_frag, ep.tap_out and ldo
- *                     are not read */
+ *                     are not read
+ *   P2V_OP_STATS      one stage of the stage statistics (p2v_code_stats below): every sample of the live buffer `in` is reduced into the
+ *                     record `out` (initialised by p2v_stats_init, accumulated into).  i0 samples, i1 kind (P2V_STAT_*), M rows, N cols,
+ *                     lda row stride, i2 | i3 << 32 sample stride (elements; p2v_stat_layer's rules).  One launch */
 enum { P2V_OP_PATCHIFY = 0, P2V_OP_GEMM = 1, P2V_OP_LAYERNORM = 2, P2V_OP_WINATTN = 3, P2V_OP_MERGE = 4, P2V_OP_AVGPOOL = 5, P2V_OP_LN_GEMM = 6,
-       P2V_OP_COS = 7, P2V_OP_COS_COMBINE = 8, P2V_OP_GEMM_F32 = 9, P2V_OP_WINATTN_SOFTMAX = 10 };
+       P2V_OP_COS = 7, P2V_OP_COS_COMBINE = 8, P2V_OP_GEMM_F32 = 9, P2V_OP_WINATTN_SOFTMAX = 10, P2V_OP_STATS = 11 };
 typedef struct p2v_op {
   int32_t kind, epi;
   const void* in;
@@ -916,6 +919,63 @@ int p2v_plan_set_float_head(p2v_plan* plan, const p2v_float_ln* final_ln);
  * not on the engine. */
 int p2v_window_softmax_attention(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
                                  const uint32_t* table, int8_t* out, void* stream);
+
+/* ---- Stage statistics (additive: no structure, existing entry point or P2V_ABI_VERSION changes; a binding finds it by its symbols) -----
+ * Which part of its code range a stage uses: one RECORD per stage, reduced over every sample and row of a strided plane, per column.
+ * One plane (the addressing of p2v_cos_layer with one operand): `samples` samples of rows x cols elements, sample i at + i * sample_stride,
+ * row r at + r * row_stride (both in ELEMENTS, row_stride >= cols; only columns [0, cols) of a row are read).  Element kinds:
+ *   P2V_STAT_I8    signed codes                                                     histogram bin = code + 128
+ *   P2V_STAT_U8    unsigned bytes (the exponents k of the log2 softmax, 16 ... 255 = probability 0)     bin = the byte
+ *   P2V_STAT_F32   fp32 values (layer outputs, LayerNorm values, logits)            bin = the biased exponent field (bits >> 23) & 255
+ * The record, p2v_stats_bytes(cols) = 2080 + 24 * cols bytes rounded up to 16, 16-byte aligned, in device memory:
+ *   int64 hist[256];  int64 count;  int64 nonfinite[3] (NaN, +Inf, -Inf; zero for the integer kinds)
+ *   lo[cols], hi[cols]      int32 for the integer kinds; for F32 the fp32 VALUE, over the finite elements only, in the total order of the
+ *                           sign-magnitude key (-0 < +0).  A column without a finite element keeps lo = +Inf, hi = -Inf (integer kinds
+ *                           without an element: INT32_MAX, INT32_MIN)
+ *   int64 sum[cols], sumsq[cols]     the integer kinds only; F32 leaves them zero (a float sum would depend on the order)
+ * p2v_stats_init writes the empty record (one launch); every later reduction ACCUMULATES into it, so one record serves any number of
+ * batches.  All quantities are integers or order-independent extrema: the result is defined exactly and is bitwise repeatable whatever the
+ * launch geometry.  The kernel keeps per-lane extrema and sums in registers and a histogram per wave in LDS, combines them per workgroup in
+ * LDS and adds the workgroup's result with integer atomics (a workgroup visits at most 2^16 rows of at most 1024 columns, so no 32-bit
+ * counter of it can overflow).  16-byte loads where a column group is whole and base and strides are 16-byte aligned, scalar loads otherwise.
+ * p2v_code_stats: layers is a HOST array, records[l] the record of layer l; one launch per layer on `stream`; a layer with rows == 0 or
+ * samples == 0 launches nothing.  ws / ws_bytes are reserved (the atomics form needs no workspace; NULL / 0).
+ * P2V_E_ARG: null pointer, unknown dtype, row_stride < cols, negative strides or counts, base or strides (in bytes) no multiples of 16,
+ * a record that is not 16-byte aligned; P2V_E_SHAPE: cols < 1; P2V_E_WORKSPACE: p2v_stats_init with bytes < p2v_stats_bytes(cols);
+ * P2V_E_UNSUPPORTED: samples * rows >= 2^31.  All before any launch. */
+enum { P2V_STAT_I8 = 0, P2V_STAT_F32 = 1, P2V_STAT_U8 = 2 };
+typedef struct p2v_stat_layer {
+  const void* base;    /* dev */
+  long long sample_stride, row_stride;   /* elements; row_stride >= cols */
+  int32_t samples, rows, cols;           /* samples, rows >= 0; cols >= 1 */
+  int32_t dtype;       /* P2V_STAT_* */
+} p2v_stat_layer;
+size_t p2v_stats_bytes(int cols);        /* 0 for cols < 1 */
+int p2v_stats_init(void* out, size_t bytes, int dtype, int cols, void* stream);
+int p2v_code_stats(const p2v_stat_layer* layers, int n_layers, void* const* records, void* ws, size_t ws_bytes, void* stream);
+
+/* The statistics of every stage inside the fused forward: p2v_forward_ddv_ex2's launch sequence, stage sets (P2V_DDV_STAGES_ENGINE / _FULL,
+ * optionally | P2V_DDV_STAGES_ATTN), stage order and refusals, with two differences: `batch` is any batch >= 1 (no pairs), and right after the
+ * launch that completes a stage ONE launch reduces all `batch` samples of the live buffer into the stage's record.  The attention stages are
+ * attn.qact_attn1 (I8) and attn.log_int_softmax (U8: the exponents k); attn.qact3 / mlp.qact2 are their codes (I8), the s_mid scales are in
+ * the layout; qact_input covers the real in_chans * patch^2 columns of the patch matrix, not the zero columns up to k_pad.  Every row of the
+ * last block is computed and the logits equal p2v_forward's.
+ *   p2v_forward_stats_bytes    bytes of the records of all stages, back to back in stage order (0: refused)
+ *   p2v_forward_stats_layout   per stage k < max_stages the byte offset of its record, its cols, its kind (P2V_STAT_*) and its per-channel
+ *                              scales (dev fp32 [cols], or NULL: one scale for the tensor); any array may be NULL.  Returns the number of
+ *                              stages (= p2v_ddv_stage_count_ex2) or a negative status.  Both run the forward's own sequence with no launch
+ *                              made, so they cannot disagree with it.
+ * The caller initialises every record once (p2v_stats_init) and may run any number of batches into them.  ws: p2v_workspace_bytes(plan,
+ * batch); tap_scratch / attn_scratch: p2v_ddv_tap_scratch_bytes / p2v_ddv_attn_scratch_bytes of n = (batch + 1) / 2 pairs, needed as in the
+ * DDV call (tap_scratch for with_linear or FULL, attn_scratch for the flag).  Refusals before any launch: those of p2v_forward_ddv_ex2 (the
+ * flag under the float softmax P2V_E_UNSUPPORTED, FULL on an input_quant = False plan P2V_E_UNSUPPORTED), stats not 16-byte aligned
+ * (P2V_E_ARG); a stats arena shorter than p2v_forward_stats_bytes is refused (P2V_E_WORKSPACE) at the first record that does not fit. */
+size_t p2v_forward_stats_bytes(const p2v_plan* plan, int with_linear, int stage_set);
+int p2v_forward_stats_layout(const p2v_plan* plan, int with_linear, int stage_set, int max_stages, long long* offsets, int32_t* cols,
+                             int32_t* kinds, const float** scales);
+int p2v_forward_stats(p2v_plan* plan, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                      size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, int8_t* attn_scratch,
+                      size_t attn_scratch_bytes, void* stats, size_t stats_bytes, void* stream);
 
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
