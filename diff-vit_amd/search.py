@@ -10,11 +10,27 @@ Kept from the reference, on purpose (same walk for the same ``random`` seed and 
   * candidates tie the two layers of each pair: ``[8] + [b for b in cfg for _ in range(2)] + [choice]`` (:269-273);
   * Omega indexes ``global_distance[i-1][k]`` with k = index of the bit in ``bit_choice`` = {0, 1}, i.e. it reads the
     uint3/uint4 weight MSEs of the calibration bookkeeping (models/ptq/layers.py:151-170), not int4/int8 (:293-296);
-  * a rejected mutation/crossover child is still appended with the PREVIOUS candidate's score (:355-361, :377-383).
+  * a rejected mutation/crossover child is still appended with the score of the configuration validated last before it
+    (:369-373, :390-394).  ``val_prec1`` is one variable of main(): into iteration 0 it carries the score of the last member of the
+    initial population in Omega order, ``omega_list[pop_size-1]``, taken BEFORE the population is sorted (:348-353) -- not the best
+    score -- and into every later iteration the score in force at the end of the one before.
+One deliberate deviation: the crossover loop leaves when the population has fewer than two members (``len(parent) < 2``).  The
+reference draws two parents until they differ and never returns from a population of one; the exit consumes no ``random`` draw the
+reference would have survived to make.
+The walk is pinned to the reference's own statements: oracle/gen_golden_search.py executes them with stubs and records them in
+tests/golden/search_walk.npz, tests/test_search.py replays every record exactly, sequentially and through ``score_many``.
 The per-layer Hessian sensitivities (``mean_hessian``; pyhessian in the reference, out of scope here, and undefined as
 shipped: test_quant.py:186) are an input; uniform sensitivities reduce Omega to the summed weight distance.
 """
 import random
+
+
+def synthetic_score(bit_config, step=0.0):
+    """the stand-in for top-1 that the recorded walks of tests/golden/search_walk.npz were scored with (oracle/gen_golden_search.py and
+    tests/test_search.py share it): more 8-bit layers late in the network -> higher.  ``step`` > 0 rounds down to multiples of it, as
+    top-1 over ``n`` images is a multiple of 100 / n (6.25 at 16 images): ties then decide the population's cut and the stable sorts."""
+    s = sum((i + 1) * (b == 8) for i, b in enumerate(bit_config)) / 10.0
+    return s // step * step if step else s
 
 
 def model_size(FLOPs, bit_config):
@@ -83,7 +99,7 @@ class _Pending:
 
     def resolve(self, entries, val):
         """``entries``: [config, score or placeholder or None] in generation order; None = rejected child, which carries the score
-        in force before it (test_quant.py:355-361).  Returns the score in force after the last entry."""
+        in force before it (test_quant.py:369-373, :390-394).  Returns the score in force after the last entry."""
         scores = iter(self.score_many(self.cfgs) if self.score_many is not None else ())
         for e in entries:
             if e[1] is self:
@@ -105,9 +121,8 @@ def evolutionary_search(score_fn, omega_list, FLOPs, constraint, rng, bit_choice
     bit_choice = list(bit_choice)
     score = _Pending(score_fn, score_many)
     parent = [[omega_list[i][0], score(omega_list[i][0])] for i in range(min(pop_size, len(omega_list)))]
-    score.resolve(parent, 0.0)
+    val = score.resolve(parent, 0.0)                   # val_prec1 of the LAST validated member, before the sort (:348-353)
     parent.sort(key=lambda x: x[-1], reverse=True)
-    val = parent[0][1] if parent else 0.0
     for evo in range(evo_iter):
         children, seen = [], []
         while True:
