@@ -87,6 +87,19 @@ def plan_flags(path):
     return bool(meta.get('int_norm', True)), bool(meta.get('int_softmax', True))
 
 
+def plan_softmax_bits(meta, calib):
+    """the width of every attention module's log-int-softmax in a plan file's calibration state, in model order: the entries
+    ``<attention path>.log_int_softmax.bits`` that ``export_calib`` writes where the width is not 4; files without them read as 4
+    (what the plans themselves read when their ``softmax_bits`` is None)"""
+    from .plan import calib_softmax_bits
+    arch = meta['arch']
+    if meta['kind'] == 'swin':
+        paths = ['layers.%d.blocks.%d.attn' % (li, bi) for li, d in enumerate(arch['depths']) for bi in range(d)]
+    else:
+        paths = ['blocks.%d.attn' % i for i in range(arch['depth'])]
+    return calib_softmax_bits(calib, paths)
+
+
 def load_plan(path, device='cuda', bits=8):
     """-> ``FrozenPlan`` (ViT/DeiT) or ``SwinPlan`` built from a file written by ``save_plan``."""
     import json

@@ -213,9 +213,10 @@ def main(argv=None):
     p.add_argument('--result-name', default='cka_result')
     p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT; a Swin model needs ptf)')
     p.add_argument('--no-lis', action='store_true', help='Config(lis=False): float softmax (ViT / DeiT and Swin)')
+    p.add_argument('--softmax-bits', default=None, type=int, choices=[3, 4], help='width of the log-int-softmax (Config.BIT_TYPE_S: uint3 / uint4; default 4)')
     args = p.parse_args(argv)
     device = torch.device(args.device)
-    fp = harness.str2model(args.model)(cfg=Config(not args.no_ptf, not args.no_lis, 'minmax'))
+    fp = harness.str2model(args.model)(cfg=Config(not args.no_ptf, not args.no_lis, 'minmax').set_softmax_bits(args.softmax_bits))
     is_swin = harness._is_swin(fp)
     if is_swin:
         if args.bits == 'mixed':

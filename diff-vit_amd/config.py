@@ -34,3 +34,15 @@ class Config:
             self.INT_NORM = False
             self.OBSERVER_A_LN = self.OBSERVER_A
             self.CALIBRATION_MODE_A_LN = self.CALIBRATION_MODE_A
+
+    def set_softmax_bits(self, bits):
+        """``--softmax-bits`` of the command lines: the width of the log-int-softmax (BIT_TYPE_S, uint4 by default; the reference's
+        config.py lists uint3 next to it), set before a model is built.  None leaves the configuration as it is."""
+        if bits is None:
+            return self
+        if bits not in (3, 4):
+            raise ValueError('softmax bits must be 3 or 4, got %r' % (bits,))
+        if not self.INT_SOFTMAX:
+            raise NotImplementedError('--softmax-bits: Config(lis=False) runs the float softmax, which has no width')
+        self.BIT_TYPE_S = BIT_TYPE_DICT['uint%d' % bits]
+        return self

@@ -112,7 +112,9 @@ __global__ __launch_bounds__(256, 3) void k_window_attention(std::conditional_t<
   const double sig_int = (double)sig_m;
   const float x_mul = ((1.0f / inv_u) * a.wa.s_q1) * inv_sa;                   // u / s_attn: a power of two
   const float m100 = (float)(int)(100.0f * inv_s2);                            // 100 / sf as an integer
-  const float av_mul = (a.wa.s_q1 / a.wa.s_q3) * P2V_PROB_SCALE;            // the probabilities are scaled by 2^-111 (lis_prob_pair)
+  const int klim = a.klim;                                                     // 2^softmax_bits: probability 0 from k = klim on
+  const unsigned kc = lis_prob_const(klim);
+  const float av_mul = (a.wa.s_q1 / a.wa.s_q3) * lis_prob_scale(klim);         // the probabilities are scaled by 2^-(127 - klim) (lis_prob_pair)
   const int c0 = (ws - 1) * (2 * ws - 1) + (ws - 1);
   const int nqb = (N + 15) >> 4;
   // per score slot of this lane: relative-position term and region of its key (the same for every query block)
@@ -208,12 +210,12 @@ __global__ __launch_bounds__(256, 3) void k_window_attention(std::conditional_t<
       const int E = (int)((__float_as_uint(ratio) + 0x00400000u) >> 23);         // biased exponent of 2^k
       if constexpr (TAP) if (valid) {
         const long long trow = (((long long)b * nW + w) * a.H + head) * N + (N - 1);
-        if (a.probs_k) a.probs_k[trow * N + j] = (int8_t)(E - 127 > 16 ? 16 : E - 127);
-        if (a.probs_kp) a.probs_kp[trow * a.pitch + j] = (int8_t)(E - 127 > 16 ? 16 : E - 127);
+        if (a.probs_k) a.probs_k[trow * N + j] = (int8_t)(E - 127 >= klim ? 16 : E - 127);
+        if (a.probs_kp) a.probs_kp[trow * a.pitch + j] = (int8_t)(E - 127 >= klim ? 16 : E - 127);
         if (a.attn1_codes) a.attn1_codes[trow * a.pitch + j] = (int8_t)(int)a1;
         if (a.qact2_codes) a.qact2_codes[trow * a.pitch + j] = (int8_t)(int)a2;
       }
-      sP[wave][g][l15] = (unsigned short)((E < 143 && l15 < 13) ? (143 - E) << 7 : 0);     // 2^-k * 2^-111 as bf16 (lis_prob_pair), 0 from k = 16 (and for padding: sum / 1 >= 2^32)
+      sP[wave][g][l15] = (unsigned short)((E < 127 + klim && l15 < 13) ? (127 + klim - E) << 7 : 0);     // 2^-k * 2^-(127 - klim) as bf16 (lis_prob_pair), 0 from k = klim (and for padding: sum / 1 >= 2^32)
       __builtin_amdgcn_wave_barrier();
       asm volatile("" ::: "memory");
       pb[0] = *reinterpret_cast<const v4i*>(&sP[wave][g][0]);                  // slots 0-7 = key blocks 0, 1;  8-15 = key blocks 2, 3 (13-15: zero)
@@ -282,11 +284,11 @@ __global__ __launch_bounds__(256, 3) void k_window_attention(std::conditional_t<
             if constexpr (TAP) if (qi < N && kb * 16 + 4 * g + r < N) {
               const int k = (int)((__float_as_uint(ratio[e]) + 0x00400000u) >> 23) - 127;
               const long long trow = (((long long)b * nW + w) * a.H + head) * N + qi;
-              if (a.probs_k) a.probs_k[trow * N + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
-              if (a.probs_kp) a.probs_kp[trow * a.pitch + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
+              if (a.probs_k) a.probs_k[trow * N + kb * 16 + 4 * g + r] = (int8_t)(k >= klim ? 16 : k);
+              if (a.probs_kp) a.probs_kp[trow * a.pitch + kb * 16 + 4 * g + r] = (int8_t)(k >= klim ? 16 : k);
             }
           }
-          pk[e2] = lis_prob_pair(ratio[0], ratio[1]);            // 2^-k * 2^-111 as bf16, 0 from k = 16 on (see k_lis_attention)
+          pk[e2] = lis_prob_pair(ratio[0], ratio[1], kc);        // 2^-k * 2^-(127 - klim) as bf16, 0 from k = klim on (see k_lis_attention)
         }
         pb[p] = (v4i){(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
       }
@@ -324,7 +326,9 @@ template <int NT, bool TAP>
 static void launch_window_t(const WinAttnArgs& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL((k_window_attention<NT, TAP>), grid, dim3(256), 0, st, a);
 }
-int p2v_launch_window_attention(const WinAttnArgs& a, hipStream_t st) {
+int p2v_launch_window_attention(const WinAttnArgs& a_, hipStream_t st) {
+  WinAttnArgs a = a_;
+  if ((a.klim = p2v_attn_klim(a.klim)) < 0) return -1;
   if (a.wa.ws > 8) return p2v_launch_window_attention_wide(a, st);
   const int hgroups = (a.H + 3) / 4;
   const dim3 grid((unsigned)(a.B * a.wa.n_windows * hgroups));
@@ -350,7 +354,9 @@ int p2v_attention_kernel_of(int head_dim, int tokens, int tapped) {
   return P2V_KERNEL_STREAMING;
 }
 
-int p2v_launch_attention(const AttnArgs& a, int head_dim, hipStream_t st) {
+int p2v_launch_attention(const AttnArgs& a_, int head_dim, hipStream_t st) {
+  AttnArgs a = a_;
+  if ((a.klim = p2v_attn_klim(a.klim)) < 0) return -1;
   const int nkb = (a.N + 31) / 32;
   {   // the kernel folds s_q1^2 / s_attn into qk_scale: exact only for a power of two (both are PoT scales in the reference)
     int ex;

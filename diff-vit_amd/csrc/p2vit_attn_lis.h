@@ -19,18 +19,21 @@ extern int g_attn_waves;     // P2V_ATTN_WAVES
 //   ~100 VGPRs -> 4 waves/SIMD, 3 workgroups (47 KB LDS each) per CU.
 // ---------------------------------------------------------------------------------------------------
 
-// log_round + the uint4 clamp of two ratios at once (layers.py:323-329, 372-375): E = (bits + 0x00400000) >> 23 is the biased exponent of 2^k
-// (ratio >= 1, so k = E - 127 >= 0) and the probability is 2^-k, or 0 from k = 16 on.  It goes into the P.V product as bf16 SCALED BY
-// 2^-111: exponent field 16 - k, i.e. (143 - E) << 7 with an UNSIGNED-SATURATING subtraction (v_pk_sub_u16 clamp) - from k = 16 on the field
-// saturates to the all-zero pattern, which IS +0.0, so the clamp costs nothing (round 3: (254 - E) << 7, a second subtraction, a shift and an
-// and-not to zero the small ones).  The scaled probabilities are normal bf16 numbers >= 2^-126, the products with the integer V codes and their
-// fp32 sums are multiples of 2^-126 below 2^-102: still exact in 24 bits, none denormal; the 2^111 is folded into av_mul (a power of two).
-#define P2V_PROB_SCALE 0x1p111f
-__device__ __forceinline__ unsigned lis_prob_pair(float r0, float r1) {
+// log_round + the clamp of two ratios at once (layers.py:323-329, 372-375): E = (bits + 0x00400000) >> 23 is the biased exponent of 2^k
+// (ratio >= 1, so k = E - 127 >= 0) and the probability is 2^-k, or 0 from k = klim = 2^softmax_bits on (16 for uint4, 8 for uint3).  It goes
+// into the P.V product as bf16 SCALED BY 2^-(127 - klim), 2^-111 at uint4: exponent field klim - k, i.e. (127 + klim - E) << 7 with an
+// UNSIGNED-SATURATING subtraction (v_pk_sub_u16 clamp) - from k = klim on the field saturates to the all-zero pattern, which IS +0.0, so the
+// clamp costs nothing (round 3: (254 - E) << 7, a second subtraction, a shift and an and-not to zero the small ones), and its width is the
+// scalar operand of that one instruction (lis_prob_const).  The scaled probabilities are normal bf16 numbers >= 2^-126, the products with the
+// integer V codes and their fp32 sums are multiples of 2^-126 below 2^-102: still exact in 24 bits, none denormal; the 2^(127 - klim) is
+// folded into av_mul (a power of two, lis_prob_scale): the C entry layer keeps av_mul * 2^(127 - klim) <= 2^126.
+__device__ __forceinline__ unsigned lis_prob_const(int klim) { return (unsigned)((127 + klim) << 7) * 0x00010001u; }      // uint4: 0x47804780
+__device__ __forceinline__ float lis_prob_scale(int klim) { return __uint_as_float((unsigned)(254 - klim) << 23); }         // uint4: 2^111
+__device__ __forceinline__ unsigned lis_prob_pair(float r0, float r1, unsigned kc) {
   const unsigned hi2 = __builtin_amdgcn_perm(__float_as_uint(r1), __float_as_uint(r0), 0x07060302u);
   const unsigned eb = __builtin_bit_cast(unsigned, __builtin_bit_cast(v2u16, hi2) + (v2u16){0x40, 0x40}) & 0x7F807F80u;      // E << 7, twice
   unsigned out;
-  asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(out) : "s"(0x47804780u), "v"(eb));                                          // sat((143 - E) << 7)
+  asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(out) : "s"(kc), "v"(eb));                                                   // sat((127 + klim - E) << 7)
   return out;
 }
 
@@ -155,7 +158,9 @@ __global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 :
   // s_q1^2 / s_attn is a power of two (checked by the launcher), so ((acc * qk_scale) * 2^e) == acc * (qk_scale * 2^e)
   // with the same single rounding; the NEGATED code is produced (round-half-even and the clamp are symmetric).
   const float nmm = -(a.at.qk_scale * (a.at.s_qkv_sq * a.at.inv_s_attn));
-  const float avm = a.at.av_mul * P2V_PROB_SCALE;        // the probabilities enter the P.V product scaled by 2^-111 (lis_prob_pair); exact, checked by the launcher
+  const int klim = a.klim;                               // 2^softmax_bits: probability 0 from k = klim on
+  const unsigned kc = lis_prob_const(klim);
+  const float avm = a.at.av_mul * lis_prob_scale(klim);  // the probabilities enter the P.V product scaled by 2^-(127 - klim) (lis_prob_pair); exact, checked by the C entry layer
   const int nqb = ((a.nq > 0 && a.nq < N ? a.nq : N) + 15) >> 4;        // a.nq: only the first query rows are wanted (whole 16-row blocks)
   const int nwaves = (int)(blockDim.x >> 6);
   // the Q fragment of a wave's first query block is requested before the barrier and the one of its next block a block ahead: its
@@ -315,13 +320,13 @@ __global__ __launch_bounds__(512, HD > 64 ? 2 : (NKP <= 7 ? 4 : (NKP <= 10 ? 3 :
             int k = (int)((__float_as_uint(ratio[e]) + 0x00400000u) >> 23) - 127;   // log_round, layers.py:323-329
             const int key = kb * 16 + 4 * g + r;
             const long long trow = ((long long)b * a.H + head) * N + qrow;
-            if (a.probs_k) a.probs_k[trow * N + key] = (int8_t)(k > 16 ? 16 : k);
-            if (a.probs_kp) a.probs_kp[trow * a.pitch + key] = (int8_t)(k > 16 ? 16 : k);
+            if (a.probs_k) a.probs_k[trow * N + key] = (int8_t)(k >= klim ? 16 : k);
+            if (a.probs_kp) a.probs_kp[trow * a.pitch + key] = (int8_t)(k >= klim ? 16 : k);
             // the qact_attn1 code back from its table offset: code = rowmax - d, nothing is recomputed
             if (a.score_codes) a.score_codes[trow * a.pitch + key] = (int8_t)(rowmax - ((s[kb][r] - ebase) >> 3));
           }
         }
-        pk[e2] = lis_prob_pair(ratio[0], ratio[1]);              // 2^-k * 2^-111 as bf16, 0 from k = 16 on
+        pk[e2] = lis_prob_pair(ratio[0], ratio[1], kc);          // 2^-k * 2^-(127 - klim) as bf16, 0 from k = klim on
       }
       v4i pb = {(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
       const v8bf fb = __builtin_bit_cast(v8bf, pb);
@@ -390,6 +395,7 @@ static int launch_attn_hd(const AttnArgs& a_, int nkp, hipStream_t st) {
   static constexpr auto table = p2v_table<AttnLauncher, AttnAt<HD, ISH_OK>, (MAXP + 1) * 4>();
   if (nkp < 1 || nkp > MAXP) return -1;
   AttnArgs a = a_;
+  if ((a.klim = p2v_attn_klim(a.klim)) < 0) return -1;
   {   // score multiplier 2^-p with p >= 1: the integer round-half-even path (|score| <= 64 * 128 * 128 < 2^21, p <= 24)
     int ex;
     const float m = a.at.qk_scale * (a.at.s_qkv_sq * a.at.inv_s_attn);

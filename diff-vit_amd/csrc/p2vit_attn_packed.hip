@@ -37,12 +37,16 @@
 // uniform over a read (one channel tile), and it spreads the staging stores (ds_write_b32, bank = dword mod 32) of the four channel chunks
 // that share a wave over 16 banks (2-way = no extra cycles) instead of 8.
 //
+// Softmax width (KLIM = 2^softmax_bits, 16 or 8): a template dimension here, because the clamp is part of the per-score shift.  At KLIM = 8 the
+// probability is 0 from k = 8 on, so plane B is zero everywhere and its MFMAs and byte permutes are not issued; KLIM = 16 is the code it was.
+//
 // Not here: the probs_k tap (those launches keep the streaming kernel) and every other head_dim.
 #include "p2vit_attn_lis.h"
 
-template <int NG>
+template <int NG, int KLIM>
 __global__ __launch_bounds__(512, 2) void k_lis_attention_packed(AttnKArgs a) {
   static_assert(NG >= 1 && NG * 64 <= P2V_MAX_TOKENS_PACKED, "key groups");
+  static_assert(KLIM == 8 || KLIM == 16, "2^softmax_bits");
   constexpr int HD = 64, KROWS = NG * 64, NDT = HD / 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int8_t* sK = reinterpret_cast<int8_t*>(smem);                  // [KROWS][64] swizzled
@@ -192,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void k_lis_attention_packed(AttnKArgs a) {
     for (int dt = 0; dt < NDT; ++dt) oA[dt] = oB[dt] = (v4i){0, 0, 0, 0};
 #pragma unroll
     for (int grp = 0; grp < NG; ++grp) {
-      v4i pa, pb;
+      v4i pa, pb = {0, 0, 0, 0};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         unsigned h[4];
@@ -207,19 +211,20 @@ __global__ __launch_bounds__(512, 2) void k_lis_attention_packed(AttnKArgs a) {
           const double rd = ((lds_f64p)(uintptr_t)(unsigned)d8)[258];
           const float ratio = rintf((float)(Sd * rd));
           const unsigned E = (__float_as_uint(ratio) + 0x00400000u) >> 23;        // log_round, layers.py:323-329: 127 + k, k >= 0 (ratio >= 1)
-          h[r] = 0x8000u >> ((E < 143u ? E : 143u) - 127u);                       // p 2^15; 0 from k = 16 on (layers.py:372-375)
+          if constexpr (KLIM == 16) h[r] = 0x8000u >> ((E < 143u ? E : 143u) - 127u);      // p 2^15; 0 from k = 16 on (layers.py:372-375)
+          else h[r] = (0x80u >> ((E < 143u ? E : 143u) - 127u)) << 8;                        // uint3: 0 from k = 8 on
         }
         const v2u16 n01 = (v2u16){0, 0} - __builtin_bit_cast(v2u16, h[0] | (h[1] << 16));      // -h, 16-bit
         const v2u16 n23 = (v2u16){0, 0} - __builtin_bit_cast(v2u16, h[2] | (h[3] << 16));
         const v2u16 a01 = n01 + (v2u16){0x80, 0x80}, a23 = n23 + (v2u16){0x80, 0x80};
         pa[j] = (int)__builtin_amdgcn_perm(__builtin_bit_cast(unsigned, a23), __builtin_bit_cast(unsigned, a01), 0x07050301u);   // the high bytes
-        pb[j] = (int)__builtin_amdgcn_perm(__builtin_bit_cast(unsigned, n23), __builtin_bit_cast(unsigned, n01), 0x06040200u);   // the low bytes
+        if constexpr (KLIM == 16) pb[j] = (int)__builtin_amdgcn_perm(__builtin_bit_cast(unsigned, n23), __builtin_bit_cast(unsigned, n01), 0x06040200u);   // the low bytes
       }
 #pragma unroll
       for (int dt = 0; dt < NDT; ++dt) {
         const v4i va = *reinterpret_cast<const v4i*>(sVt + grp * 4096 + (dt * 16 + l15) * 64 + ((g ^ ksw ^ dt) << 4));
         oA[dt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(va, pa, oA[dt], 0, 0, 0);
-        oB[dt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(va, pb, oB[dt], 0, 0, 0);
+        if constexpr (KLIM == 16) oB[dt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(va, pb, oB[dt], 0, 0, 0);      // (KLIM = 8: plane B is zero)
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -240,32 +245,38 @@ __global__ __launch_bounds__(512, 2) void k_lis_attention_packed(AttnKArgs a) {
   }
 }
 
-template <int NG>
+template <int NG, int KLIM>
 static int launch_packed_t(const AttnArgs& a, hipStream_t st) {
   constexpr size_t smem = (size_t)NG * 64 * 128 + 2 * 258 * 8;
   static_assert(smem <= 160 * 1024, "LDS of a CU");
   static P2vLdsGrant grant = {};                   // always beyond the default dynamic LDS limit
-  const hipError_t e = grant.ensure(reinterpret_cast<const void*>(&k_lis_attention_packed<NG>), (int)smem);
+  const hipError_t e = grant.ensure(reinterpret_cast<const void*>(&k_lis_attention_packed<NG, KLIM>), (int)smem);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((k_lis_attention_packed<NG>), dim3((unsigned)(a.B * a.H)), dim3(64 * g_attn_waves), smem, st, a);
+  hipLaunchKernelGGL((k_lis_attention_packed<NG, KLIM>), dim3((unsigned)(a.B * a.H)), dim3(64 * g_attn_waves), smem, st, a);
   CHECK_LAUNCH();
   return 0;
 }
 
-// the launchers by ceil(tokens / 64): 10 .. 19 are instantiated
+// the launchers, in the order the code object holds their kernels (p2vit_launch.h): flat index ceil(tokens / 64) * 2 + (uint3); groups
+// 10 .. 19 are instantiated
 typedef int (*PackedLauncher)(const AttnArgs&, hipStream_t);
+constexpr int packed_index(int ng, int klim) { return ng * 2 + (klim == 8 ? 1 : 0); }
 struct PackedAt {
   template <int I> static constexpr PackedLauncher at() {
-    if constexpr (I >= 10) return launch_packed_t<I>;
+    constexpr int NG = I >> 1, KLIM = (I & 1) ? 8 : 16;
+    static_assert(packed_index(NG, KLIM) == I, "decoded as the launcher encodes");
+    if constexpr (NG >= 10) return launch_packed_t<NG, KLIM>;
     else return nullptr;
   }
 };
-static const auto packed_table = p2v_table<PackedLauncher, PackedAt, 20>();
+static const auto packed_table = p2v_table<PackedLauncher, PackedAt, 40>();
 
 // head_dim 64, no tap, tokens beyond the resident kernel's up to P2V_MAX_TOKENS_PACKED: one instantiation per ceil(tokens / 64)
-int p2v_launch_attention_packed(const AttnArgs& a, hipStream_t st) {
+int p2v_launch_attention_packed(const AttnArgs& a_, hipStream_t st) {
+  AttnArgs a = a_;
   if (a.probs_k || a.B * a.H <= 0 || a.N > P2V_MAX_TOKENS_PACKED) return -1;
-  const int ng = (a.N + 63) / 64;
-  const PackedLauncher launch = (ng >= 0 && ng < (int)packed_table.size()) ? packed_table[ng] : nullptr;
+  if ((a.klim = p2v_attn_klim(a.klim)) < 0) return -1;
+  const int ng = (a.N + 63) / 64, idx = packed_index(ng, a.klim);
+  const PackedLauncher launch = (ng >= 0 && idx < (int)packed_table.size()) ? packed_table[idx] : nullptr;
   return launch ? launch(a, st) : -1;
 }

@@ -58,7 +58,9 @@ __global__ __launch_bounds__(64) void k_lis_attention_stream(std::conditional_t<
     if (4 * j + g < CH) fq[j] = *reinterpret_cast<const v4i*>(base + (long long)qload * ld + (4 * j + g) * 16);
   }
   const float nmm = -(a.at.qk_scale * (a.at.s_qkv_sq * a.at.inv_s_attn));            // the NEGATED code is produced, as in k_lis_attention
-  const float avm = a.at.av_mul * P2V_PROB_SCALE;
+  const int klim = a.klim;                                                            // 2^softmax_bits, see lis_prob_pair
+  const unsigned kc = lis_prob_const(klim);
+  const float avm = a.at.av_mul * lis_prob_scale(klim);
 
   // ---- pass 1: scores -> negated qact_attn1 codes nc in [-127, 128], stored as nc + 127 in a byte; row minimum of nc over the real keys
   int mn = 1000;
@@ -138,12 +140,12 @@ __global__ __launch_bounds__(64) void k_lis_attention_stream(std::conditional_t<
         if constexpr (TAP) if (key < N && qrow < N) {
           const int k = (int)((__float_as_uint(ratio[e]) + 0x00400000u) >> 23) - 127; // log_round, layers.py:323-329
           const long long trow = ((long long)b * a.H + head) * N + qrow;
-          if (a.probs_k) a.probs_k[trow * N + key] = (int8_t)(k > 16 ? 16 : k);
-          if (a.probs_kp) a.probs_kp[trow * a.pitch + key] = (int8_t)(k > 16 ? 16 : k);
+          if (a.probs_k) a.probs_k[trow * N + key] = (int8_t)(k >= klim ? 16 : k);
+          if (a.probs_kp) a.probs_kp[trow * a.pitch + key] = (int8_t)(k >= klim ? 16 : k);
           if (a.score_codes) a.score_codes[trow * a.pitch + key] = (int8_t)(-nc);       // the qact_attn1 code (pass 1 keeps its negation)
         }
       }
-      pk[e2] = lis_prob_pair(ratio[0], ratio[1]);
+      pk[e2] = lis_prob_pair(ratio[0], ratio[1], kc);
     }
     const v4i pb = {(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
     const v8bf fb = __builtin_bit_cast(v8bf, pb);
@@ -193,8 +195,9 @@ struct StreamAt {
 static const auto stream_table = p2v_table<StreamLauncher, StreamAt, 18>();
 
 // tokens beyond p2v_max_tokens(head_dim), up to P2V_MAX_TOKENS_STREAMED
-int p2v_launch_attention_stream(const AttnArgs& a, int head_dim, hipStream_t st) {
-  if (a.N > P2V_MAX_TOKENS_STREAMED || a.B * a.H <= 0) return -1;
+int p2v_launch_attention_stream(const AttnArgs& a_, int head_dim, hipStream_t st) {
+  AttnArgs a = a_;
+  if (a.N > P2V_MAX_TOKENS_STREAMED || a.B * a.H <= 0 || (a.klim = p2v_attn_klim(a.klim)) < 0) return -1;
   const StreamLauncher launch = (head_dim >= 0 && head_dim <= 128 && head_dim % 16 == 0) ? stream_table[stream_index(head_dim, a.tapped())] : nullptr;
   return launch ? launch(a, st) : -1;
 }

@@ -64,16 +64,24 @@ static int check_gelu_tab(const char* who, const p2v_gelu_tab& t) {
   if (t.table && (t.cells <= 0 || t.cells > 4096)) return fail(P2V_E_ARG, "%s: GELU table with %d cells", who, t.cells);
   return P2V_OK;
 }
-static int check_attn(const char* who, const p2v_attn& at) {
+// width of the log-int-softmax (the module's bit type, layers.py:372-375): uint4 or uint3
+static int check_softmax_bits(const char* who, int bits) {
+  if (bits != 3 && bits != 4) return fail(P2V_E_UNSUPPORTED, "%s: softmax_bits %d (the log-int-softmax runs at 3 or 4 bits)", who, bits);
+  return P2V_OK;
+}
+// the probabilities enter the P.V product scaled by 2^-(127 - 2^bits) and av_mul carries the inverse (lis_prob_pair): the product stays a
+// finite power of two up to 2^126, i.e. av_mul up to 2^15 at 4 bits and 2^7 at 3 bits
+static float av_mul_max(int bits) { return bits == 3 ? 0x1p7f : 0x1p15f; }
+static int check_attn(const char* who, const p2v_attn& at, int bits = 4) {
+  if (const int rb = check_softmax_bits(who, bits)) return rb;
   const int rc = check_lis_consts(who, at.x0_int, at.b_int, at.c_int);
   if (rc != P2V_OK) return rc;
   // the kernel folds s_q1^2 / s_attn into qk_scale: exact only for a power of two (both are PoT scales in the reference)
   if (!is_pot(at.s_qkv_sq * at.inv_s_attn)) return fail(P2V_E_UNSUPPORTED, "%s: s_qkv_sq * inv_s_attn must be a power of two", who);
   if (!(at.qk_scale > 0.f) || !(at.av_mul > 0.f)) return fail(P2V_E_ARG, "%s: qk_scale and av_mul must be positive", who);
-  // the probabilities enter the P.V product scaled by 2^-111 and av_mul carries the 2^111 (p2vit_attn.hip, lis_prob_pair): exact for a
-  // power of two in this range (s_q1 / qact2 scale of two PoT activation scales)
-  if (!is_pot(at.av_mul) || at.av_mul > 0x1p15f || at.av_mul < 0x1p-40f)
-    return fail(P2V_E_UNSUPPORTED, "%s: av_mul %g must be a power of two in [2^-40, 2^15]", who, at.av_mul);
+  // exact for a power of two in this range (s_q1 / qact2 scale of two PoT activation scales)
+  if (!is_pot(at.av_mul) || at.av_mul > av_mul_max(bits) || at.av_mul < 0x1p-40f)
+    return fail(P2V_E_UNSUPPORTED, "%s: av_mul %g must be a power of two in [2^-40, 2^%d] at softmax_bits %d", who, at.av_mul, bits == 3 ? 7 : 15, bits);
   return P2V_OK;
 }
 
@@ -107,6 +115,7 @@ struct p2v_plan {
   std::vector<p2v_float_block> fblocks;
   std::vector<char> fblock_set;
   p2v_float_ln final_fln = {};
+  std::vector<char> softmax_bits;   // [block] width of the block's log-int-softmax (p2v_plan_set_softmax_bits): 4 unless set
   ~p2v_plan() {
     int prev = -1;
     const bool sw = device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device && hipSetDevice(device) == hipSuccess;
@@ -243,6 +252,7 @@ int p2v_plan_create(const p2v_model_desc* desc, p2v_plan** out) {
   p->cls_codes = nullptr;
   p->fblocks.resize(d.depth);
   p->fblock_set.assign(d.depth, 0);
+  p->softmax_bits.assign(d.depth, 4);
   *out = p;
   return P2V_OK;
 }
@@ -425,7 +435,7 @@ int p2v_plan_set_block(p2v_plan* plan, int block, const p2v_block* blk) {
   if (!plan || !blk) return fail(P2V_E_ARG, "p2v_plan_set_block: null argument");
   if (block < 0 || block >= plan->d.depth) return fail(P2V_E_ARG, "block %d out of range", block);
   // p2v_forward launches the kernels directly: everything the per-operator entry points check is checked here, once
-  int rc = check_attn("p2v_plan_set_block: attn", blk->attn);
+  int rc = check_attn("p2v_plan_set_block: attn", blk->attn, plan->softmax_bits[block]);
   if (rc == P2V_OK) rc = check_gelu_tab("p2v_plan_set_block: gelu_fc1", blk->gelu_fc1);
   for (int b = 0; b < 2 && rc == P2V_OK; ++b) rc = check_requant_scale("p2v_plan_set_block: inv_s_qkv", blk->inv_s_qkv[b]);
   if (rc == P2V_OK && !(is_pot(blk->inv_s_fc1) && blk->inv_s_fc1 >= 0x1p-40f && blk->inv_s_fc1 <= 0x1p40f))
@@ -753,6 +763,7 @@ struct Fwd {
     } else {
       AttnArgs at{{QKV, batch, T, p->d.num_heads, b.attn, ATT, nullptr}};
       at.nq = rs.nq;
+      at.klim = 1 << p->softmax_bits[i];
       int8_t* planes = (!done && o.ddv) ? o.ddv->attn : nullptr;              // P2V_DDV_STAGES_ATTN: the tapped launch, both planes of this block
       const int pitch = round_up(T, 16), HT = p->d.num_heads * T;
       if (planes) {
@@ -1187,35 +1198,49 @@ static int check_tap_planes(const char* who, int row, int pitch, std::initialize
   return P2V_OK;
 }
 
-static int lis_attention(const char* who, const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int min_rows,
+static int lis_attention(const char* who, int bits, const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int min_rows,
                          int query_rows, int8_t* out, int8_t* probs_k, void* stream, int8_t* score_codes = nullptr, int8_t* probs_kp = nullptr,
                          int pitch = 0) {
   if (!qkv || !at || !out) return fail(P2V_E_ARG, "%s: null argument", who);
   if (batch <= 0 || tokens <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad attention shape");
   if (query_rows < min_rows || query_rows > tokens) return fail(P2V_E_SHAPE, "%s: query_rows %d outside 1 .. %d", who, query_rows, tokens);
-  const int rc = check_attn(who, *at);
+  const int rc = check_attn(who, *at, bits);
   if (rc != P2V_OK) return rc;
   const int rp = check_tap_planes(who, tokens, pitch, {score_codes, probs_kp});
   if (rp != P2V_OK) return rp;
   AttnArgs a{{qkv, batch, tokens, heads, *at, out, probs_k}};
   a.nq = query_rows;
+  a.klim = 1 << bits;
   a.score_codes = score_codes; a.probs_kp = probs_kp; a.pitch = pitch;
   return launch_rc(p2v_launch_attention(a, head_dim, (hipStream_t)stream), "lis_attention");
 }
 
 int p2v_lis_attention_taps(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int8_t* out,
                            int8_t* score_codes, int8_t* probs_k, int pitch, void* stream) {
-  return lis_attention("p2v_lis_attention_taps", qkv, batch, tokens, heads, head_dim, at, 0, 0, out, nullptr, stream, score_codes, probs_k, pitch);
+  return lis_attention("p2v_lis_attention_taps", 4, qkv, batch, tokens, heads, head_dim, at, 0, 0, out, nullptr, stream, score_codes, probs_k, pitch);
+}
+int p2v_lis_attention_taps_bits(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int softmax_bits,
+                                int8_t* out, int8_t* score_codes, int8_t* probs_k, int pitch, void* stream) {
+  return lis_attention("p2v_lis_attention_taps_bits", softmax_bits, qkv, batch, tokens, heads, head_dim, at, 0, 0, out, nullptr, stream, score_codes,
+                       probs_k, pitch);
 }
 
 int p2v_lis_attention(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int8_t* out,
                       int8_t* probs_k, void* stream) {
-  return lis_attention("p2v_lis_attention", qkv, batch, tokens, heads, head_dim, at, 0, 0, out, probs_k, stream);
+  return lis_attention("p2v_lis_attention", 4, qkv, batch, tokens, heads, head_dim, at, 0, 0, out, probs_k, stream);
+}
+int p2v_lis_attention_bits(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int softmax_bits,
+                           int8_t* out, int8_t* probs_k, void* stream) {
+  return lis_attention("p2v_lis_attention_bits", softmax_bits, qkv, batch, tokens, heads, head_dim, at, 0, 0, out, probs_k, stream);
 }
 
 int p2v_lis_attention_rows(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int query_rows,
                            int8_t* out, void* stream) {
-  return lis_attention("p2v_lis_attention_rows", qkv, batch, tokens, heads, head_dim, at, 1, query_rows, out, nullptr, stream);
+  return lis_attention("p2v_lis_attention_rows", 4, qkv, batch, tokens, heads, head_dim, at, 1, query_rows, out, nullptr, stream);
+}
+int p2v_lis_attention_rows_bits(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int softmax_bits,
+                                int query_rows, int8_t* out, void* stream) {
+  return lis_attention("p2v_lis_attention_rows_bits", softmax_bits, qkv, batch, tokens, heads, head_dim, at, 1, query_rows, out, nullptr, stream);
 }
 
 // ---- float LayerNorm / table softmax (Config(ptf=False) / Config(lis=False)) -------------------------------------------------------------
@@ -1282,6 +1307,18 @@ int p2v_plan_set_float_ops(p2v_plan* plan, int float_norm, int float_softmax) {
   return P2V_OK;
 }
 
+int p2v_plan_set_softmax_bits(p2v_plan* plan, int block, int bits) {
+  const char* who = "p2v_plan_set_softmax_bits";
+  if (!plan) return fail(P2V_E_ARG, "%s: null plan", who);
+  if (block < 0 || block >= plan->d.depth) return fail(P2V_E_ARG, "%s: block %d out of range", who, block);
+  if (plan->float_softmax) return fail(P2V_E_UNSUPPORTED, "%s: the plan's softmax is the table one, it has no width", who);
+  if (const int rc = check_softmax_bits(who, bits)) return rc;
+  if (plan->block_set[block] && plan->blocks[block].attn.av_mul > av_mul_max(bits))
+    return fail(P2V_E_UNSUPPORTED, "%s: av_mul %g of block %d is above 2^7, the range of a 3-bit softmax", who, plan->blocks[block].attn.av_mul, block);
+  plan->softmax_bits[block] = (char)bits;
+  return P2V_OK;
+}
+
 int p2v_plan_set_float_block(p2v_plan* plan, int block, const p2v_float_block* blk) {
   if (!plan || !blk) return fail(P2V_E_ARG, "p2v_plan_set_float_block: null argument");
   if (block < 0 || block >= plan->d.depth) return fail(P2V_E_ARG, "block %d out of range", block);
@@ -1328,11 +1365,12 @@ int p2v_avgpool_quant(const int8_t* x, int batch, int tokens, int C, float s_in,
   return launch_rc(p2v_launch_avgpool_quant(x, batch, tokens, C, s_in, inv_s_out, out, (hipStream_t)stream), "avgpool_quant");
 }
 
-static int window_attention(const char* who, const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+static int window_attention(const char* who, int bits, const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
                             int8_t* out, int8_t* probs_k, void* stream, int8_t* attn1_codes, int8_t* qact2_codes, int8_t* probs_kp, int pitch) {
   if (!qkv || !wa || !out || !wa->table_codes || !wa->win_index) return fail(P2V_E_ARG, "p2v_window_attention: null argument");
   if (batch <= 0 || tokens_per_image <= 0 || heads <= 0) return fail(P2V_E_SHAPE, "bad window attention shape");
   if (head_dim != 32) return fail(P2V_E_UNSUPPORTED, "window attention: head_dim must be 32");
+  if (const int rb = check_softmax_bits(who, bits)) return rb;
   if (wa->ws < 1 || wa->ws > 12 || wa->n_windows < 1 || wa->ws * wa->ws * wa->n_windows > tokens_per_image)
     return fail(P2V_E_SHAPE, "window attention: window size must be 1..12 and windows must fit the token count");
   {
@@ -1348,24 +1386,35 @@ static int window_attention(const char* who, const int8_t* qkv, int batch, int t
       (wa->out_stride && wa->out_stride < heads * head_dim))
     return fail(P2V_E_SHAPE, "window attention: row strides must cover a row and be 16 / 4 byte aligned");
   if (wa->s_q2 > 1.0f) return fail(P2V_E_UNSUPPORTED, "window attention: qact2 scale above 1 (the -100 mask would not be an integer)");
-  if (wa->s_q1 / wa->s_q3 > 0x1p15f || wa->s_q1 / wa->s_q3 < 0x1p-40f)
-    return fail(P2V_E_UNSUPPORTED, "window attention: qact1 scale / qact3 scale must lie in [2^-40, 2^15]");
+  if (wa->s_q1 / wa->s_q3 > av_mul_max(bits) || wa->s_q1 / wa->s_q3 < 0x1p-40f)
+    return fail(P2V_E_UNSUPPORTED, "window attention: qact1 scale / qact3 scale must lie in [2^-40, 2^%d] at softmax_bits %d", bits == 3 ? 7 : 15, bits);
   const int rp = check_tap_planes(who, wa->ws * wa->ws, pitch, {attn1_codes, qact2_codes, probs_kp});
   if (rp != P2V_OK) return rp;
-  WinAttnArgs a{{qkv, batch, tokens_per_image, heads, *wa, out, probs_k}};
+  WinAttnArgs a{{qkv, batch, tokens_per_image, heads, *wa, out, probs_k, 1 << bits}};
   a.attn1_codes = attn1_codes; a.qact2_codes = qact2_codes; a.probs_kp = probs_kp; a.pitch = pitch;
   return launch_rc(p2v_launch_window_attention(a, (hipStream_t)stream), "window_attention");
 }
 
 int p2v_window_attention(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
                          int8_t* out, int8_t* probs_k, void* stream) {
-  return window_attention("p2v_window_attention", qkv, batch, tokens_per_image, heads, head_dim, wa, out, probs_k, stream, nullptr, nullptr, nullptr, 0);
+  return window_attention("p2v_window_attention", 4, qkv, batch, tokens_per_image, heads, head_dim, wa, out, probs_k, stream, nullptr, nullptr, nullptr, 0);
+}
+int p2v_window_attention_bits(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                              int softmax_bits, int8_t* out, int8_t* probs_k, void* stream) {
+  return window_attention("p2v_window_attention_bits", softmax_bits, qkv, batch, tokens_per_image, heads, head_dim, wa, out, probs_k, stream, nullptr,
+                          nullptr, nullptr, 0);
 }
 
 int p2v_window_attention_taps(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
                               int8_t* out, int8_t* attn1_codes, int8_t* qact2_codes, int8_t* probs_k, int pitch, void* stream) {
-  return window_attention("p2v_window_attention_taps", qkv, batch, tokens_per_image, heads, head_dim, wa, out, nullptr, stream, attn1_codes,
+  return window_attention("p2v_window_attention_taps", 4, qkv, batch, tokens_per_image, heads, head_dim, wa, out, nullptr, stream, attn1_codes,
                           qact2_codes, probs_k, pitch);
+}
+int p2v_window_attention_taps_bits(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                                   int softmax_bits, int8_t* out, int8_t* attn1_codes, int8_t* qact2_codes, int8_t* probs_k, int pitch,
+                                   void* stream) {
+  return window_attention("p2v_window_attention_taps_bits", softmax_bits, qkv, batch, tokens_per_image, heads, head_dim, wa, out, nullptr, stream,
+                          attn1_codes, qact2_codes, probs_k, pitch);
 }
 
 // Config(lis=False) of a Swin plan: the table softmax behind the qact2 codes.  Every refusal comes before the launch
@@ -1451,8 +1500,10 @@ static int run_one_op(const p2v_op& o, void* stream) {
       return p2v_int_layernorm((const int8_t*)o.in, o.lda, o.M, o.N, &o.ln, (int8_t*)o.out, o.ldo, stream);
     case P2V_OP_WINATTN:
       // (additive) the planes of p2v_window_attention_taps in members this kind did not read before: all NULL = the untapped launch
-      return p2v_window_attention_taps((const int8_t*)o.in, o.i0, o.i1, o.i2, o.i3, &o.wa, (int8_t*)o.out, const_cast<int8_t*>(o.lin.w_codes),
-                                       const_cast<int8_t*>(o.lin.w_frag), reinterpret_cast<int8_t*>(o.ep.tap_out), o.ldo, stream);
+      // (additive) i4: the softmax width, 0 = 4 (an earlier record)
+      return p2v_window_attention_taps_bits((const int8_t*)o.in, o.i0, o.i1, o.i2, o.i3, &o.wa, o.i4 ? o.i4 : 4, (int8_t*)o.out,
+                                            const_cast<int8_t*>(o.lin.w_codes), const_cast<int8_t*>(o.lin.w_frag),
+                                            reinterpret_cast<int8_t*>(o.ep.tap_out), o.ldo, stream);
     case P2V_OP_MERGE:
       return p2v_patch_merge_gather((const int8_t*)o.in, o.i0, o.i1, o.i2, o.i3, (int8_t*)o.out, stream);
     case P2V_OP_AVGPOOL:

@@ -55,6 +55,8 @@ struct AttnKArgs {
   int8_t* probs_k;
   int pshift;           // filled by the launcher: score multiplier = 2^-pshift (>= 1) -> integer requant path; 0 = fp32 path
   int nq;               // query rows to compute, in whole 16-row blocks (0 = all): the resident and the packed kernel; the streaming kernel computes all rows
+  int klim;             // 2^softmax_bits (8 or 16): the probability is 0 from k = klim on.  0 (an argument built without it) = 16: every launcher
+                        // that takes AttnArgs from outside its file fills it in (p2v_attn_klim) and refuses any other value
 #ifdef P2V_DIAG
   unsigned long long* stamps;   // diagnostic build only: 16 cycle stamps per workgroup (wave 0) or null
 #endif
@@ -68,12 +70,16 @@ struct AttnArgs : AttnKArgs {
   bool tapped() const { return probs_k || score_codes || probs_kp; }
 };
 
+// klim as the kernels read it: 0 -> 16; -1 for anything but 8 and 16
+inline int p2v_attn_klim(int klim) { return klim == 0 ? 16 : ((klim == 8 || klim == 16) ? klim : -1); }
+
 struct WinAttnKArgs {      // the untapped instantiations' argument, as AttnKArgs
   const int8_t* qkv;
   int B, T, H;          // images, tokens per image, heads
   p2v_winattn wa;
   int8_t* out;
   int8_t* probs_k;
+  int klim;             // 2^softmax_bits (8 or 16), as AttnKArgs.klim.  0 = 16: p2v_launch_window_attention (the one way in) fills it in
 };
 struct WinAttnArgs : WinAttnKArgs {
   // pitched taps (p2v_window_attention_taps; each optional): [B][n_windows][H][N][pitch] int8, pitch >= N a multiple of 16; only the

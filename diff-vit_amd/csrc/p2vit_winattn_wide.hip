@@ -152,7 +152,9 @@ __global__ __launch_bounds__(256, 2) void k_window_attention_wide(std::condition
   const double sig_int = (double)sig_m;
   const float x_mul = ((1.0f / inv_u) * a.wa.s_q1) * inv_sa;                   // u / s_attn: a power of two
   const float m100 = (float)(int)(100.0f * inv_s2);                            // 100 / sf as an integer
-  const float av_mul = (a.wa.s_q1 / a.wa.s_q3) * P2V_PROB_SCALE;               // the probabilities are scaled by 2^-111 (lis_prob_pair)
+  const int klim = a.klim;                                                        // 2^softmax_bits: probability 0 from k = klim on
+  const unsigned kc = lis_prob_const(klim);
+  const float av_mul = (a.wa.s_q1 / a.wa.s_q3) * lis_prob_scale(klim);            // the probabilities are scaled by 2^-(127 - klim) (lis_prob_pair)
   constexpr int c0 = (WS - 1) * (2 * WS - 1) + (WS - 1);
   // per score slot of this lane: relative-position term and region of its key (the same for every query block), as staged: two
   // slots to a register (keys 4g + r and 4g + r + 1 are neighbours in sMeta)
@@ -303,11 +305,11 @@ __global__ __launch_bounds__(256, 2) void k_window_attention_wide(std::condition
           if constexpr (TAP) if (qi < N && kb * 16 + 4 * g + r < N) {
             const int k = (int)((__float_as_uint(ratio[e]) + 0x00400000u) >> 23) - 127;
             const long long trow = (((long long)b * nW + w) * a.H + head) * N + qi;
-            if (a.probs_k) a.probs_k[trow * N + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
-            if (a.probs_kp) a.probs_kp[trow * a.pitch + kb * 16 + 4 * g + r] = (int8_t)(k > 16 ? 16 : k);
+            if (a.probs_k) a.probs_k[trow * N + kb * 16 + 4 * g + r] = (int8_t)(k >= klim ? 16 : k);
+            if (a.probs_kp) a.probs_kp[trow * a.pitch + kb * 16 + 4 * g + r] = (int8_t)(k >= klim ? 16 : k);
           }
         }
-        pk[e2] = lis_prob_pair(ratio[0], ratio[1]);              // 2^-k * 2^-111 as bf16, 0 from k = 16 on (see k_lis_attention)
+        pk[e2] = lis_prob_pair(ratio[0], ratio[1], kc);          // 2^-k * 2^-(127 - klim) as bf16, 0 from k = klim on (see k_lis_attention)
       }
       const v4i pb = {(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]};
       const v8bf fb = __builtin_bit_cast(v8bf, pb);

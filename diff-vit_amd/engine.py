@@ -234,6 +234,13 @@ def lib():
         L.p2v_plan_set_float_head.argtypes = [_p, C.POINTER(FloatLn)]
     if hasattr(L, 'p2v_window_softmax_attention'):      # Swin Config(lis=False), additive
         L.p2v_window_softmax_attention.argtypes = [_p, _i, _i, _i, _i, C.POINTER(WinAttn), _p, _p, _p]
+    if hasattr(L, 'p2v_plan_set_softmax_bits'):   # the width of the log-int-softmax (Config.BIT_TYPE_S: uint3 / uint4), additive
+        L.p2v_plan_set_softmax_bits.argtypes = [_p, _i, _i]
+        L.p2v_lis_attention_bits.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Attn), _i, _p, _p, _p]
+        L.p2v_lis_attention_rows_bits.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Attn), _i, _i, _p, _p]
+        L.p2v_lis_attention_taps_bits.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Attn), _i, _p, _p, _p, _i, _p]
+        L.p2v_window_attention_bits.argtypes = [_p, _i, _i, _i, _i, C.POINTER(WinAttn), _i, _p, _p, _p]
+        L.p2v_window_attention_taps_bits.argtypes = [_p, _i, _i, _i, _i, C.POINTER(WinAttn), _i, _p, _p, _p, _p, _i, _p]
     if hasattr(L, 'p2v_freeze_weights'):          # the weight freeze is additive, found by its symbols
         L.p2v_freeze_bytes.argtypes = [_i, _i, _i]
         L.p2v_freeze_bytes.restype = C.c_size_t

@@ -34,6 +34,7 @@ def build_parser():
     p.add_argument('--no-ptf', dest='ptf', action='store_false', help='Config(ptf=False): layer-wise QActs around a float LayerNorm (ViT / DeiT; a Swin model needs ptf)')
     p.add_argument('--no-lis', dest='lis', action='store_false',
                    help='Config(lis=False): float softmax instead of the log-int-softmax (ViT / DeiT and Swin)')
+    p.add_argument('--softmax-bits', default=None, type=int, choices=[3, 4], help='width of the log-int-softmax (Config.BIT_TYPE_S: uint3 / uint4; default 4)')
     p.add_argument('--quant-method', default='minmax', choices=['minmax', 'ema', 'omse', 'percentile'])
     p.add_argument('--mixed', default=False, action='store_true')
     p.add_argument('--calib-batchsize', default=50, type=int, help='batchsize of calibration set')
@@ -355,7 +356,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     seed(args.seed)
     device = torch.device(args.device)
-    cfg = Config(args.ptf, args.lis, args.quant_method)
+    cfg = Config(args.ptf, args.lis, args.quant_method).set_softmax_bits(args.softmax_bits)
     model = str2model(args.model)(pretrained=args.pretrained, cfg=cfg)
     arch = model.arch
     if args.pretrained:

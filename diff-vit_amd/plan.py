@@ -65,6 +65,59 @@ def softmax_table(s_attn):
     return np.minimum(e, float((1 << SOFTMAX_FRAC_BITS) - 1)).astype(np.uint32)
 
 
+SOFTMAX_BITS = (3, 4)                            # the widths of the log-int-softmax on the engine (uint3 / uint4 of Config.BIT_TYPE_S)
+
+
+def softmax_bits_list(softmax_bits, n, who='softmax_bits'):
+    """``softmax_bits`` of a plan as one width per attention module: None (4 everywhere), an int, or ``n`` entries"""
+    if softmax_bits is None:
+        return [4] * n
+    if isinstance(softmax_bits, (int, np.integer)) and not isinstance(softmax_bits, bool):
+        vals = [int(softmax_bits)] * n
+    else:
+        vals = [int(b) for b in softmax_bits]
+        if len(vals) != n:
+            raise ValueError('%s has %d entries, the model has %d attention modules' % (who, len(vals), n))
+    for i, b in enumerate(vals):
+        if b not in SOFTMAX_BITS:
+            raise NotImplementedError('%s[%d] = %d: the log-int-softmax runs at 3 or 4 bits on the engine' % (who, i, b))
+    return vals
+
+
+def module_softmax_bits(model, int_softmax=True):
+    """What ``freeze`` reads off the module graph: the width of every QIntSoftmax in module order (its own ``bit_type``, as
+    QIntSoftmax.forward reads it), and a refusal - ``NotImplementedError`` naming the module path - of what the engine would otherwise
+    ignore: a log-int-softmax that is neither uint3 nor uint4, a QAct that is not int8 (Config.BIT_TYPE_A = uint8).  Under
+    ``int_softmax=False`` the softmax bit type (uint8) is unused, as in the reference."""
+    from .ptq.layers import QAct, QIntSoftmax
+    widths = []
+    for name, m in model.named_modules():
+        if type(m) is QAct and m.bit_type.name != 'int8':
+            raise NotImplementedError('%s: QAct bit type %s: the HIP engine runs int8 activations only' % (name, m.bit_type.name))
+        if type(m) is QIntSoftmax:
+            if int_softmax and m.bit_type.name not in ('uint3', 'uint4'):
+                raise NotImplementedError('%s: log-int-softmax bit type %s: the HIP engine runs uint3 and uint4' % (name, m.bit_type.name))
+            widths.append(m.bit_type.bits if int_softmax else 4)
+    return widths
+
+
+def calib_softmax_bits(calib, paths, softmax_bits=None):
+    """the width of the attention modules ``paths``, in order, from a plan's ``softmax_bits`` argument and the calibration state.
+    ``export_calib`` writes the key ``<path>.log_int_softmax.bits`` only where the width is not 4, so a missing key says nothing:
+    with ``softmax_bits`` None a named width is taken and the rest are 4 (files and dicts without the key read as 4); with an argument
+    (an int or one entry per module) a named width that disagrees with it is refused - ``ValueError`` naming the module - instead of
+    one of the two being ignored."""
+    named = [int(round(float(torch.as_tensor(calib[p + '.log_int_softmax.bits']).reshape(-1)[0]))) if (p + '.log_int_softmax.bits') in calib else None
+             for p in paths]
+    if softmax_bits is None:
+        return softmax_bits_list([4 if b is None else b for b in named], len(paths), 'log_int_softmax.bits')
+    vals = softmax_bits_list(softmax_bits, len(paths))
+    for p, b, v in zip(paths, named, vals):
+        if b is not None and b != v:
+            raise ValueError('%s.log_int_softmax.bits = %d in the calibration state, softmax_bits says %d' % (p, b, v))
+    return vals
+
+
 def _per_channel(t, D):
     """a QAct scale as D per-channel values: the PTF vector, or the one layer-wise scale of Config(ptf=False) repeated"""
     t = t.detach().float().reshape(-1)
@@ -74,8 +127,13 @@ def _per_channel(t, D):
 class FrozenPlan:
     """Device-resident integer plan + handle of the C plan object."""
 
-    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, input_quant=True, int_norm=True, int_softmax=True, ln_eps=1e-6):
+    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, input_quant=True, int_norm=True, int_softmax=True, ln_eps=1e-6,
+                 softmax_bits=None):
         self.arch = dict(arch)
+        # width of every block's log-int-softmax (the bit type of its QIntSoftmax: p = 2^-k for k < 2^bits, else 0): None = what the
+        # calibration state names (export_calib of a uint3 model), else 4; an int, or one entry per block, which a named width must
+        # agree with.  Unused (as in the reference) under int_softmax=False
+        self.softmax_bits = calib_softmax_bits(calib, ['blocks.%d.attn' % i for i in range(self.arch['depth'])], softmax_bits)
         # Config(ptf, lis): False selects the float LayerNorm (F.layer_norm -> QAct) / the float softmax as the engine's fp64 / table operators
         self.int_norm, self.int_softmax, self.ln_eps = bool(int_norm), bool(int_softmax), float(ln_eps)
         self.input_quant = bool(input_quant)      # False: the fp32 image feeds the patch-embed convolution (vit_fquant.py:705, :925)
@@ -285,6 +343,10 @@ class FrozenPlan:
             fe.s_res = E.ptr(self._dev(s_b2))
             fe.s_next = E.ptr(self._dev(s_b4))
             blk.fc2_epi = fe
+            if self.int_softmax and self.softmax_bits[i] != 4:
+                if not hasattr(L, 'p2v_plan_set_softmax_bits'):
+                    raise RuntimeError('libp2vit_hip.so lacks p2v_plan_set_softmax_bits (a %d-bit log-int-softmax): rebuild' % self.softmax_bits[i])
+                E.check(L.p2v_plan_set_softmax_bits(self._handle, i, self.softmax_bits[i]))
             E.check(L.p2v_plan_set_block(self._handle, i, C.byref(blk)))
             if not (self.int_norm and self.int_softmax):
                 E.check(L.p2v_plan_set_float_block(self._handle, i, C.byref(fblk)))
@@ -470,7 +532,7 @@ class FrozenPlan:
         ``stages='full'`` (``P2V_DDV_STAGES_FULL``): also the stages behind the reference's remaining hook points - the stem's codes, the
         LayerNorm values, the mid codes of proj / fc2 - in the same one call; the tap buffer is then needed either way.
         ``attention`` (``P2V_DDV_STAGES_ATTN``, with either set): per block also ``attn.qact_attn1`` (the score codes) and
-        ``attn.log_int_softmax`` (the 4-bit log2 probabilities), both exact, from the tapped attention launch through one scratch of
+        ``attn.log_int_softmax`` (the log2 probabilities at the block's softmax width), both exact, from the tapped attention launch through one scratch of
         ``ddv_attn_bytes(n)`` that the next block reuses."""
         images, cfg = self._check(images_2n, bit_config)
         B = images.shape[0]

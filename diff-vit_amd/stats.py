@@ -334,12 +334,13 @@ def main(argv=None):
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--device', default='cuda')
     p.add_argument('--result-name', default='stats_result')
+    p.add_argument('--softmax-bits', default=None, type=int, choices=[3, 4], help='width of the log-int-softmax (Config.BIT_TYPE_S: uint3 / uint4; default 4)')
     args = p.parse_args(argv)
     _check_cli(args)
     from . import harness, synth
     from .config import Config
     device = torch.device(args.device)
-    q = harness.str2model(args.model)(cfg=Config(not args.no_ptf, not args.no_lis, 'minmax'))
+    q = harness.str2model(args.model)(cfg=Config(not args.no_ptf, not args.no_lis, 'minmax').set_softmax_bits(args.softmax_bits))
     is_swin = harness._is_swin(q)
     if not hasattr(q, 'arch') or not (is_swin or hasattr(q, 'depth')):
         raise NotImplementedError('the statistics tool covers the ViT / DeiT and the Swin models')

@@ -329,18 +329,26 @@ class SwinTransformer(nn.Module):
                 c[name] = m.quantizer.scale.detach().float().cpu().reshape(-1)
             elif type(m) in (QLinear, QConv2d):
                 c[name] = {k: v.detach().float().cpu().reshape(-1) for k, v in m.quantizer.dic_scale.items()}
+            elif type(m) is QIntSoftmax and self.cfg.INT_SOFTMAX and m.bit_type.bits != 4:
+                # the width of the log-int-softmax, only where it is not the default 4 (dicts and files without the key read as 4)
+                c[name + '.bits'] = torch.tensor([float(m.bit_type.bits)])
         return c
 
     def freeze(self, device=None, bits=8, pack4=True):
+        """the plan is a snapshot: it holds the width of every window attention's ``log_int_softmax.bit_type`` (uint3 / uint4) as read
+        here - changing a module's bit type afterwards needs a new ``freeze`` (``model_open_calibrate`` drops the plan).  A
+        log-int-softmax of another width and a QAct that is not int8 are refused (``NotImplementedError`` naming the module)."""
         from .swin_plan import SwinPlan
+        from .plan import module_softmax_bits
         if not self.input_quant:
             raise NotImplementedError('the HIP engine fuses qact_input into the patch gather: input_quant=True models only')
         if not self.cfg.INT_NORM:
             raise NotImplementedError('the HIP engine runs a Swin model with ptf=True only (lis=True or False): Config(ptf=False) needs a '
                                       'float LayerNorm the Swin engine does not have')
+        widths = module_softmax_bits(self, bool(self.cfg.INT_SOFTMAX))
         dev = device or self.head.weight.device
         self._plan = SwinPlan(self.arch, dict(self.state_dict()), self.export_calib(), device=dev, in_chans=self.in_chans, bits=bits, pack4=pack4,
-                              int_softmax=bool(self.cfg.INT_SOFTMAX))
+                              int_softmax=bool(self.cfg.INT_SOFTMAX), softmax_bits=widths)
         return self._plan
 
     # ---- per-layer widths -----------------------------------------------------------------------------------------------

@@ -40,13 +40,20 @@ class SwinPlan:
     one per byte (A/B comparison).  The tapped / model-diff sequences always read int8-stored codes.
     ``int_softmax=False`` (Config(lis=False)): every window-attention record of every sequence is ``P2V_OP_WINATTN_SOFTMAX`` - the float
     softmax behind the qact2 codes as a 256-entry fixed-point table per block (``plan.softmax_table`` of the block's qact2 scale), which
-    needs that scale to be at most 2^-2 (``NotImplementedError`` here otherwise, naming the layer)."""
+    needs that scale to be at most 2^-2 (``NotImplementedError`` here otherwise, naming the layer).
+    ``softmax_bits``: the width of every window attention's log-int-softmax (p = 2^-k for k < 2^bits, else 0): None = the widths the
+    calibration state names (``<path>.log_int_softmax.bits``, else 4), an int, or one entry per attention module in model order (a named
+    width that disagrees is refused); kept as ``plan.softmax_bits`` and written into every ``P2V_OP_WINATTN``
+    record.  Unused (as in the reference) under ``int_softmax=False``."""
 
-    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, bits=8, pack4=True, int_softmax=True):
+    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, bits=8, pack4=True, int_softmax=True, softmax_bits=None):
         if bits not in (4, 8):
             raise KeyError('int%s' % (bits,))          # (the weight scale a width has none of: what the lookup below raised)
         self.arch, self.device, self.in_chans, self.bits, self.pack4 = dict(arch), torch.device(device), in_chans, bits, bool(pack4)
         self.int_softmax = bool(int_softmax)
+        from .plan import calib_softmax_bits
+        self.softmax_bits = calib_softmax_bits(calib, ['layers.%d.blocks.%d.attn' % (li, bi) for li, d in enumerate(self.arch['depths'])
+                                                       for bi in range(d)], softmax_bits)
         if self.device.type != 'cuda':
             raise RuntimeError('SwinPlan needs a GPU device: the quantized forward has no CPU path')
         if self.device.index is None:
@@ -227,7 +234,7 @@ class SwinPlan:
                 p = 'layers.%d.blocks.%d.' % (li, bi)
                 shift = 0 if (bi % 2 == 0 or H <= ws) else ws // 2
                 s1 = self._pot(p + 'qact1')
-                b = dict(C=Cc, heads=heads, H=H, ws=wsz, shift=shift)
+                b = dict(C=Cc, heads=heads, H=H, ws=wsz, shift=shift, softmax_bits=self.softmax_bits[sum(a['depths'][:li]) + bi])
                 b['ln1'] = self._ln(p + 'norm1', s_res, s1, Cc)
                 s_q1 = self._pot(p + 'attn.qact1')
                 b['qkv'] = self._linear(p + 'attn.qkv', s1, frag=Cc <= 384)
@@ -490,6 +497,7 @@ class SwinPlan:
                 o.i0, o.i1, o.i2, o.i3 = B, T, b['heads'], 32
                 o.wa = b['wa']
                 o.wa.out_stride = att.shape[1]
+                o.i4 = b['softmax_bits']     # the width of the log-int-softmax (0, an earlier record, = 4); the table softmax reads none
                 if b['sm_tab'] is not None:  # Config(lis=False): the table softmax behind the same qact2 codes; the table in lin.w_codes
                     o.kind, o.lin.w_codes = E.OP_WINATTN_SOFTMAX, E.ptr(b['sm_tab'])
                 if planes is not None:       # the tapped launch (op table of include/p2vit.h: members the record did not use before)
@@ -673,7 +681,7 @@ class SwinPlan:
         stream: every stage is reduced from the live buffer right behind the launch that completes it (the LayerNorm outputs exist in HBM
         because the unfused sequence is recorded; attn.qact4 / mlp.qact2 come from the mid-code output of the RESID epilogue), one combine
         launch closes it.  ``attention``: also the QActs inside the window kernel - attn.qact_attn1, attn.qact2 (codes) and
-        attn.log_int_softmax (the 4-bit log2 probabilities), exact sums from the tapped window launch; stage names =
+        attn.log_int_softmax (the log2 probabilities at the block's softmax width), exact sums from the tapped window launch; stage names =
         ``ddv.swin_stage_names(depths, with_linear, attention=True)``.  qact_table does not depend on the input and is not a stage."""
         images_2n = self._check_images(images_2n)
         if images_2n.shape[0] < 2 or images_2n.shape[0] % 2:

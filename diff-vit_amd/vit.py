@@ -413,15 +413,24 @@ class VisionTransformer(nn.Module):
             c[p + 'mlp.fc2'] = dic(blk.mlp.fc2)
             c[p + 'mlp.qact2'] = sc(blk.mlp.qact2)
             c[p + 'qact4'] = sc(blk.qact4)
+            # the width of the log-int-softmax, only where it is not the default 4 (dicts and files without the key read as 4)
+            if self.cfg.INT_SOFTMAX and blk.attn.log_int_softmax.bit_type.bits != 4:
+                c[p + 'attn.log_int_softmax.bits'] = torch.tensor(float(blk.attn.log_int_softmax.bit_type.bits))
         return c
 
     def freeze(self, device=None):
-        """build (once) the integer plan the HIP engine executes; called lazily by the first quantized forward."""
-        from .plan import FrozenPlan
+        """build (once) the integer plan the HIP engine executes; called lazily by the first quantized forward.
+        The plan is a snapshot: among the rest it holds the width of every block's ``log_int_softmax.bit_type`` (uint3 / uint4) as read
+        here, so changing a module's bit type afterwards needs a new ``freeze`` (``model_open_calibrate`` drops the plan).  What the
+        engine cannot honour is refused here (``NotImplementedError`` naming the module): a log-int-softmax of another width, a QAct
+        that is not int8."""
+        from .plan import FrozenPlan, module_softmax_bits
         dev = device or self.cls_token.device
+        widths = module_softmax_bits(self, bool(self.cfg.INT_SOFTMAX))
         sd = {k: v for k, v in self.state_dict().items()}
         self._plan = FrozenPlan(self.arch, sd, self.export_calib(), device=dev, in_chans=self.in_chans, input_quant=self.input_quant,
-                                int_norm=bool(self.cfg.INT_NORM), int_softmax=bool(self.cfg.INT_SOFTMAX), ln_eps=float(self.norm.eps))
+                                int_norm=bool(self.cfg.INT_NORM), int_softmax=bool(self.cfg.INT_SOFTMAX), ln_eps=float(self.norm.eps),
+                                softmax_bits=widths)
         return self._plan
 
     def flops(self):

@@ -480,6 +480,28 @@ int p2v_lis_attention_rows(const int8_t* qkv, int batch, int tokens, int heads, 
 int p2v_lis_attention_taps(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int8_t* out,
                            int8_t* score_codes, int8_t* probs_k, int pitch, void* stream);
 
+/* ---- Width of the log-int-softmax (additive: no structure, existing entry point or P2V_ABI_VERSION changes; found by their symbols) ----
+ * QIntSoftmax clamps at the width of its own bit type (layers.py:372-375; Config.BIT_TYPE_S, config.py:34-36: uint4, or uint3):
+ *     p = 2^-k for k < 2^softmax_bits, else 0,        softmax_bits 3 or 4.
+ * The entry points above run at 4.  The *_bits forms take the width; at 4 they write the bytes of the forms above.  A tap plane holds
+ * k >= 2^softmax_bits ? 16 : k, so "16 = zero" goes on holding for every reader of such a plane (P2V_COS_LOG2K, P2V_STAT_U8).
+ * Any other width: P2V_E_UNSUPPORTED.
+ * Range.  The kernels carry the probabilities scaled by 2^-(127 - 2^softmax_bits) and fold the inverse into av_mul (one multiply per
+ * output): av_mul * 2^(127 - 2^softmax_bits) has to stay finite, so the accepted range of av_mul (p2v_attn), and of s_q1 / s_q3 (p2v_winattn),
+ * is NARROWED at 3 bits: [2^-40, 2^7] instead of [2^-40, 2^15]; beyond it P2V_E_UNSUPPORTED.  (Calibrated models sit many octaves below
+ * either bound.)  Every argument and range refusal comes before any launch.
+ * Plans: p2v_plan_set_softmax_bits(plan, block, bits) sets the width of one block's attention (4 unless set), in either order with
+ * p2v_plan_set_block - both check the block's av_mul against the width's range.  P2V_E_UNSUPPORTED on a plan whose softmax is the table one
+ * (p2v_plan_set_float_ops, float_softmax != 0: that softmax has no width), P2V_E_ARG for a block out of range.  Every forward of the plan
+ * (taps, DDV stages, statistics, profiling, the class-row last block) runs each block at its width.
+ * P2V_OP_WINATTN reads the width from i4, which the kind did not read before: 0 = 4, so earlier records keep their meaning. */
+int p2v_lis_attention_bits(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int softmax_bits,
+                           int8_t* out, int8_t* probs_k, void* stream);
+int p2v_lis_attention_rows_bits(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int softmax_bits,
+                                int query_rows, int8_t* out, void* stream);
+int p2v_lis_attention_taps_bits(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_attn* at, int softmax_bits,
+                                int8_t* out, int8_t* score_codes, int8_t* probs_k, int pitch, void* stream);
+
 /* Swin window attention core (WindowAttention.forward between qact1 and qact3, swin_quant.py:186-217; window partition /
  * cyclic shift / reverse of SwinTransformerBlock.forward, swin_quant.py:366-391, folded into the addressing):
  *   (q*scale) @ k^T -> qact_attn1 -> + qact_table(relative_position_bias_table)[index] -> qact2 -> (+ -100 mask) ->
@@ -519,6 +541,12 @@ int p2v_window_attention(const int8_t* qkv, int batch, int tokens_per_image, int
  * 12 x 12).  P2V_E_ARG for a bad pitch or a misaligned plane when a plane is given. */
 int p2v_window_attention_taps(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
                               int8_t* out, int8_t* attn1_codes, int8_t* qact2_codes, int8_t* probs_k, int pitch, void* stream);
+/* the two entry points above at a softmax width of 3 or 4 bits (see "Width of the log-int-softmax") */
+int p2v_window_attention_bits(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                              int softmax_bits, int8_t* out, int8_t* probs_k, void* stream);
+int p2v_window_attention_taps_bits(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
+                                   int softmax_bits, int8_t* out, int8_t* attn1_codes, int8_t* qact2_codes, int8_t* probs_k, int pitch,
+                                   void* stream);
 
 /* PatchMerging.forward gather (swin_quant.py:446-459): x int8 [batch][H*W][C] -> out int8 [batch][(H/2)*(W/2)][4*C] in the
  * reference's channel order x0 (even row, even col), x1 (odd row, even col), x2 (even row, odd col), x3 (odd, odd). */
@@ -560,7 +588,8 @@ int p2v_avgpool_quant(const int8_t* x, int batch, int tokens, int C, float s_in,
  *                     are not read
  *   P2V_OP_STATS      one stage of the stage statistics (p2v_code_stats below): every sample of the live buffer `in` is reduced into the
  *                     record `out` (initialised by p2v_stats_init, accumulated into).  i0 samples, i1 kind (P2V_STAT_*), M rows, N cols,
- *                     lda row stride, i2 | i3 << 32 sample stride (elements; p2v_stat_layer's rules).  One launch */
+ *                     lda row stride, i2 | i3 << 32 sample stride (elements; p2v_stat_layer's rules).  One launch
+ *   P2V_OP_WINATTN    i4 the softmax width (3 or 4); 0, the value of every earlier record, means 4 */
 enum { P2V_OP_PATCHIFY = 0, P2V_OP_GEMM = 1, P2V_OP_LAYERNORM = 2, P2V_OP_WINATTN = 3, P2V_OP_MERGE = 4, P2V_OP_AVGPOOL = 5, P2V_OP_LN_GEMM = 6,
        P2V_OP_COS = 7, P2V_OP_COS_COMBINE = 8, P2V_OP_GEMM_F32 = 9, P2V_OP_WINATTN_SOFTMAX = 10, P2V_OP_STATS = 11 };
 typedef struct p2v_op {
@@ -901,6 +930,8 @@ typedef struct p2v_float_block {
   const uint32_t* softmax_table;   /* dev [256] */
 } p2v_float_block;
 int p2v_plan_set_float_ops(p2v_plan* plan, int float_norm, int float_softmax);
+/* (additive) the width of one block's log-int-softmax, 3 or 4 bits (4 unless set): see "Width of the log-int-softmax" above */
+int p2v_plan_set_softmax_bits(p2v_plan* plan, int block, int bits);
 int p2v_plan_set_float_block(p2v_plan* plan, int block, const p2v_float_block* blk);
 int p2v_plan_set_float_head(p2v_plan* plan, const p2v_float_ln* final_ln);
 
