@@ -5,6 +5,8 @@ DDV_CKA.py), on the fused engine.
     MinibatchCKA(num_layers, num_layers2=None, across_models=False, dtype=torch.float32)           efficient_CKA.py
     MinibatchAdvCKA(...)                                                                            DDV_CKA.py
     compute_cka(model1, model2, batches, bit_config1, bit_config2, normalize_act=False)           float vs quantized heat map
+    get_stage_grams(images, model, bit_config, device, stages='engine', with_linear=False)         centred Grams over the DDV stage list
+    compute_cka(..., stages='engine' | 'full', with_linear=False)                                 the heat map over the two stage lists
 
 On a fused model (``model_quant()`` state) ``get_activations`` makes ONE ``p2v_forward_linear_taps`` call: its forward hooks on
 QConv2d / QLinear are fed by the engine (``VisionTransformer._forward_hooked``).  A Swin model is called with its own signature
@@ -15,7 +17,15 @@ module graph runs with the hooks, as in the reference.  The CKA classes send GPU
 (``torch.ops.p2vit.cka_grams`` / ``hsic_accumulate``: one grouped Gram launch sequence for all layers of an update) and CPU
 activations through ``gram_matrix``, a plain-torch restatement of the same formula.
 
-``python -m diff_vit_amd.cka --model deit_small --bits 8 --batch 50 --iters 2`` (or ``--model swin_tiny``; ``--bits mixed`` is refused
+With ``stages`` the heat map runs over ``ddv.stage_names`` instead of the linear layers - the QAct stages (block inputs, attention and
+GELU outputs, the residual streams) included, where the quantization happens.  On a fused GPU model ``get_stage_grams`` makes ONE
+``p2v_forward_grams`` call: every int8 stage's Gram is an exact integer contraction of its live codes on the int8 MFMA
+(``p2v_code_grams``; per-channel stages as code * 2^m_c in units of the smallest scale, which CKA does not see), no fp32 tap is written
+for them, and ``torch.ops.p2vit.cka_centre`` applies the centring.  Any other state runs the module graph with hooks on the same names
+(``ddv._hooked_outputs``) and the fp32 Gram path above.  A Swin model and the attention stages are refused with ``stages``.
+
+``python -m diff_vit_amd.cka --model deit_small --bits 8 --batch 50 --iters 2`` (``--stages engine|full`` and ``--with-linear`` for the
+stage lists; then ``_names.pkl`` holds the two name lists) (or ``--model swin_tiny``; ``--bits mixed`` is refused
 for Swin) writes ``<result-name>/_heatmap.pkl`` (float vs
 quantized on the synthetic data of ``harness``)."""
 import argparse
@@ -156,6 +166,22 @@ class MinibatchCKA:
         assert self.hsic_accumulator.size(1) == len(activations2), 'Number of activation vectors does not match num_layers.'
         self._accumulate(_grams(activations1, None, self.dtype), _grams(activations2, None, self.dtype), True)
 
+    def _flat(self, g):
+        """centred Grams as ``_accumulate`` takes them: [L, n, n] on the GPU, [L, n*n] on the CPU"""
+        g = g.to(torch.float32 if g.is_cuda else self.dtype)
+        return g if g.is_cuda else g.reshape(g.shape[0], -1)
+
+    def update_state_grams(self, g):
+        """``update_state`` on centred Grams [L, n, n] (``get_stage_grams``) instead of activations"""
+        g = self._flat(g)
+        self._accumulate(g, g, False)
+
+    def update_state_across_models_grams(self, g1, g2):
+        """``update_state_across_models`` on the centred Grams of the two models"""
+        assert self.hsic_accumulator.size(0) == g1.shape[0], 'Number of Gram matrices does not match num_layers.'
+        assert self.hsic_accumulator.size(1) == g2.shape[0], 'Number of Gram matrices does not match num_layers.'
+        self._accumulate(self._flat(g1), self._flat(g2), True)
+
     def result(self):
         mean_hsic = self.hsic_accumulator
         if self.across_models:
@@ -173,6 +199,14 @@ class MinibatchAdvCKA(MinibatchCKA):
         g2 = _grams(model2_activations, model2_adv_activations, self.dtype)
         self._accumulate(g1, g2, True)
 
+    def update_state_grams(self, g1, g2):
+        """``update_state`` on centred X X_adv^T Grams [L, n, n] of the two models - e.g. ``torch.ops.p2vit.cka_centre`` of the
+        off-diagonal blocks ``raw[:, :n, n:]`` of the raw Grams of a batch [clean; perturbed]"""
+        self._accumulate(self._flat(g1), self._flat(g2), True)
+
+    def update_state_across_models_grams(self, g1, g2):
+        self.update_state_grams(g1, g2)
+
     def result(self):
         mean_hsic = self.hsic_accumulator / torch.sqrt(self.hsic_accumulator_model1).unsqueeze(1)
         return mean_hsic / torch.sqrt(self.hsic_accumulator_model2).unsqueeze(0)
@@ -183,9 +217,75 @@ def _device_of(model):
     return p.device if p is not None else torch.device('cpu')
 
 
-def compute_cka(model1, model2, batches, bit_config1, bit_config2, normalize_act=False, dtype=torch.float32):
+def _check_stages(model, stages):
+    from .swin import SwinTransformer
+    from .vit import VisionTransformer
+    if stages not in ('engine', 'full'):
+        if stages in ('attention', 'attn'):
+            raise NotImplementedError('CKA over the stages inside the attention kernels is not served: the log2 exponent planes are no '
+                                      'byte codes the Gram kernel takes')
+        raise ValueError("stages must be None, 'engine' or 'full', not %r" % (stages,))
+    if isinstance(model, SwinTransformer):
+        raise NotImplementedError('CKA over the DDV stage list covers the ViT / DeiT models: the Swin plan has no Gram entry point yet; '
+                                  'use stages=None (the linear layers)')
+    if not isinstance(model, VisionTransformer):
+        raise NotImplementedError('CKA over the DDV stage list covers the ViT / DeiT models')
+
+
+def get_stage_grams(images, model, bit_config, device, stages='engine', with_linear=False, attention=False, dtype=torch.float32):
+    """(names, centred Grams [S, n, n]) of ``model`` under ``bit_config`` over ``ddv.stage_names(depth, with_linear, stages == 'full')``.
+    A fused model on a GPU makes ONE ``FrozenPlan.forward_grams`` call plus ``cka_centre`` (fp32 Grams); any other state (float model,
+    ``-1`` entries, dequant, CPU) takes the outputs of forward hooks on the same names through ``_grams``."""
+    from .ddv import _hooked_outputs, stage_names
+    if attention:
+        raise NotImplementedError('CKA over the stages inside the attention kernels is not served: the log2 exponent planes are no byte '
+                                  'codes the Gram kernel takes')
+    _check_stages(model, stages)
+    device = torch.device(device)
+    model = model.to(device)
+    x = images.to(device).float()
+    full = stages == 'full'
+    has_fp = bit_config is not None and any(int(b) == -1 for b in bit_config)
+    fused_state = model._fused()
+    if fused_state and bit_config is not None and not has_fp and device.type == 'cuda':
+        if model._plan is None:
+            model.freeze(device)
+        _, names, raw, _ = model._plan.forward_grams(x, [int(b) for b in bit_config], with_linear, stages=stages)
+        return names, torch.ops.p2vit.cka_centre(raw)
+    if full and not getattr(model, 'input_quant', True):
+        raise AttributeError("get_stage_grams(stages='full'): the model has no qact_input (input_quant=False)")
+    names = stage_names(model.depth, with_linear, full, False)
+    acts = [a.reshape(x.shape[0], -1) for a in _hooked_outputs(model, x, bit_config, names, fused_state)]
+    g = _grams(acts, None, dtype)
+    return names, g.reshape(len(names), x.shape[0], x.shape[0])
+
+
+def _compute_cka_stages(model1, model2, batches, bit_config1, bit_config2, stages, with_linear, dtype):
+    cka = None
+    for images in batches:
+        if isinstance(images, (tuple, list)):
+            images = images[0]
+        _, g1 = get_stage_grams(images, model1, bit_config1, _device_of(model1), stages, with_linear, dtype=dtype)
+        _, g2 = get_stage_grams(images, model2, bit_config2, _device_of(model2), stages, with_linear, dtype=dtype)
+        if cka is None:
+            cka = MinibatchCKA(g1.shape[0], g2.shape[0], across_models=True, dtype=dtype)
+        cka.update_state_across_models_grams(g1, g2.to(g1.device))
+    if cka is None:
+        raise ValueError('compute_cka: no batches')
+    return cka.result()
+
+
+def compute_cka(model1, model2, batches, bit_config1, bit_config2, normalize_act=False, dtype=torch.float32, stages=None, with_linear=False):
     """the CKA heat map [layers of model1, layers of model2] between two models over ``batches`` (image tensors, or (images, labels)
-    pairs), one update_state_across_models per batch."""
+    pairs), one update_state_across_models per batch.  ``stages='engine' | 'full'``: over the DDV stage lists of the two models
+    (``get_stage_grams``; ``with_linear`` adds the linear outputs) instead of the linear layers."""
+    if stages is not None:
+        if normalize_act:
+            raise NotImplementedError('compute_cka(stages=...): normalize_act rescales every image by its own norm, which the integer Grams '
+                                      'of the codes do not carry')
+        _check_stages(model1, stages)
+        _check_stages(model2, stages)
+        return _compute_cka_stages(model1, model2, batches, bit_config1, bit_config2, stages, with_linear, dtype)
     cka = None
     for images in batches:
         if isinstance(images, (tuple, list)):
@@ -214,7 +314,12 @@ def main(argv=None):
     p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT; a Swin model needs ptf)')
     p.add_argument('--no-lis', action='store_true', help='Config(lis=False): float softmax (ViT / DeiT and Swin)')
     p.add_argument('--softmax-bits', default=None, type=int, choices=[3, 4], help='width of the log-int-softmax (Config.BIT_TYPE_S: uint3 / uint4; default 4)')
+    p.add_argument('--stages', default='linear', choices=['linear', 'engine', 'full'],
+                   help='linear: the QConv2d / QLinear outputs; engine / full: the DDV stage lists (ViT / DeiT), from one engine call per batch')
+    p.add_argument('--with-linear', action='store_true', help='with --stages engine / full: the linear outputs as stages too')
     args = p.parse_args(argv)
+    if args.stages != 'linear' and args.model.startswith('swin'):      # refused before anything is built
+        raise NotImplementedError('--stages %s: CKA over the DDV stage list covers the ViT / DeiT models' % args.stages)
     device = torch.device(args.device)
     fp = harness.str2model(args.model)(cfg=Config(not args.no_ptf, not args.no_lis, 'minmax').set_softmax_bits(args.softmax_bits))
     is_swin = harness._is_swin(fp)
@@ -233,8 +338,14 @@ def main(argv=None):
         L = 4 * fp.depth + 2
         bits = {'8': [8] * L, '4': [4] * L, 'mixed': [8 if (i * 7 + 3) % 5 < 3 else 4 for i in range(L)]}[args.bits]
     loader = harness.SyntheticLoader(args.batch * args.iters, args.batch, fp.arch['img_size'], fp.arch['num_classes'], args.seed + 2, device)
-    heatmap = compute_cka(fp, q, loader, None, bits).cpu().numpy()
+    stages = None if args.stages == 'linear' else args.stages
+    heatmap = compute_cka(fp, q, loader, None, bits, stages=stages, with_linear=args.with_linear).cpu().numpy()
     os.makedirs(args.result_name, exist_ok=True)
+    if stages is not None:
+        from .ddv import stage_names
+        names = stage_names(fp.depth, args.with_linear, stages == 'full')
+        with open(os.path.join(args.result_name, '_names.pkl'), 'wb') as f:
+            pickle.dump({'model1': names, 'model2': names}, f)
     path = os.path.join(args.result_name, '_heatmap.pkl')
     with open(path, 'wb') as f:
         pickle.dump(heatmap, f)

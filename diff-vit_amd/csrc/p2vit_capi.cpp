@@ -116,6 +116,11 @@ struct p2v_plan {
   std::vector<char> fblock_set;
   p2v_float_ln final_fln = {};
   std::vector<char> softmax_bits;   // [block] width of the block's log-int-softmax (p2v_plan_set_softmax_bits): 4 unless set
+  // p2v_plan_prepare_grams: of every per-channel stage scale vector its exponent bytes (one device buffer, owned by the plan) and its unit
+  struct GramScale { const float* scale; const uint8_t* shift; double unit; };
+  std::vector<GramScale> gram_scales;
+  uint8_t* gram_shift_buf = nullptr;
+  bool grams_ready = false;
   ~p2v_plan() {
     int prev = -1;
     const bool sw = device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device && hipSetDevice(device) == hipSuccess;
@@ -124,6 +129,7 @@ struct p2v_plan {
     for (float* b : resid_buf)
       if (b) (void)hipFree(b);
     if (final_pre_buf) (void)hipFree(final_pre_buf);
+    if (gram_shift_buf) (void)hipFree(gram_shift_buf);
     if (sw) (void)hipSetDevice(prev);
   }
 };
@@ -588,6 +594,7 @@ struct DdvCtx {
   float* scratch = nullptr;       // P2V_DDV_STAGES_FULL: the same buffer, for the fp32 LayerNorm values (set whatever with_linear says); null = the engine stages
   int8_t* attn = nullptr;         // P2V_DDV_STAGES_ATTN: the two planes of one block's attention taps (p2v_ddv_attn_scratch_bytes); null = no such stages
   struct StatsCtx* stats = nullptr;   // p2v_forward_stats: the stage sites reduce all n samples into records instead of pairs into cosines
+  struct GramsCtx* grams = nullptr;   // p2v_forward_grams: the stage sites take the n x n Gram of all n samples
 };
 // p2v_forward_stats: stage k's record lies at the running offset in the arena; a layout pass (no launches) lists the records instead
 struct StatsStage { size_t off; int cols, kind; const float* scale; };
@@ -613,6 +620,47 @@ static int stats_reduce(DdvCtx* c, const void* base, int rows, int cols, int dty
   const int rc = stats_check(l, s->arena + off, false, "p2v_forward_stats", c->stage - 1);
   return rc != P2V_OK ? rc : launch_rc(p2v_launch_stats(p2v_stats_desc(l, s->arena + off), st), "stage_stats");
 }
+// p2v_forward_grams: stage k's Gram goes to grams[k][n][n], its unit to units[k]; a layout pass (no launches) lists the stages instead
+struct GramStage { int rows, cols, kind; const float* scale; };
+struct GramsCtx {
+  const p2v_plan* plan;
+  double *grams, *units;
+  void* ws;                           // the partials of one stage, reused by every stage (one stream)
+  size_t ws_bytes;
+  std::vector<GramStage>* layout;     // non-null: the layout pass
+  std::vector<double> host_units;     // uploaded once behind the last stage
+};
+static int gram_check(const p2v_gram_layer& a, int n, bool aligned, const char* what, int l);
+static size_t gram_ws_bytes(const p2v_gram_layer& a, int n);
+static int gram_launch(const p2v_gram_layer& a, int n, double* G, void* ws, hipStream_t st);
+static int grams_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st, long long sample_stride,
+                        long long row_stride) {
+  GramsCtx* g = c->grams;
+  const int k = c->stage++;
+  const int kind = dtype == P2V_COS_F32 ? P2V_GRAM_F32 : P2V_GRAM_I8;
+  if (dtype == P2V_COS_LOG2K) return fail(P2V_E_UNSUPPORTED, "p2v_forward_grams: the exponent planes of the attention stages are no byte codes");
+  if (g->layout) {
+    g->layout->push_back(GramStage{rows, cols, kind, scale});
+    return P2V_OK;
+  }
+  const uint8_t* shift = nullptr;
+  double unit = kind == P2V_GRAM_F32 ? 1.0 : 0.0;
+  if (scale) {
+    const p2v_plan::GramScale* hit = nullptr;
+    for (const p2v_plan::GramScale& s : g->plan->gram_scales)
+      if (s.scale == scale) { hit = &s; break; }
+    if (!hit) return fail(P2V_E_STATE, "p2v_forward_grams: stage %d has per-channel scales p2v_plan_prepare_grams has not seen", k);
+    shift = hit->shift;
+    unit = hit->unit;
+  }
+  const p2v_gram_layer l{base, shift, sample_stride, row_stride, rows, cols, kind};
+  int rc = gram_check(l, c->n, false, "p2v_forward_grams", k);
+  if (rc != P2V_OK) return rc;
+  if (gram_ws_bytes(l, c->n) > g->ws_bytes)
+    return fail(P2V_E_WORKSPACE, "p2v_forward_grams: stage %d needs %zu bytes of partials, the workspace holds %zu", k, gram_ws_bytes(l, c->n), g->ws_bytes);
+  g->host_units.push_back(unit);
+  return launch_rc(gram_launch(l, c->n, g->grams + (size_t)k * c->n * c->n, g->ws, st), "stage_gram");
+}
 // sample_stride (elements): 0 = the samples are dense, rows * cols apart; else e.g. the patch rows of a [T][cols] token layout
 // row_stride (elements): 0 = dense rows; else the pitch of the attention planes
 static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype, const float* scale, hipStream_t st, long long sample_stride = 0,
@@ -621,6 +669,7 @@ static int ddv_reduce(DdvCtx* c, const void* base, int rows, int cols, int dtype
   if (!row_stride) row_stride = cols;
   if (!sample_stride) sample_stride = (long long)rows * row_stride;
   if (c->stats) return stats_reduce(c, base, rows, cols, dtype, scale, st, sample_stride, row_stride);
+  if (c->grams) return grams_reduce(c, base, rows, cols, dtype, scale, st, sample_stride, row_stride);
   const p2v_cos_layer l{base, reinterpret_cast<const char*>(base) + (size_t)c->n * sample_stride * esz, scale, sample_stride, row_stride, rows, cols, dtype};
   const CosDesc d = p2v_cos_desc(l, c->n, 0);        // (logits / head rows of a class count that is no multiple of 4: d.vec = 0, scalar loads)
   if ((long long)c->n * d.nsplit > c->slots)
@@ -2062,4 +2111,240 @@ int p2v_forward_stats(p2v_plan* plan, const float* images, int batch, const int8
   FwdOpts o;
   o.images = images; o.ddv = &ctx; o.lin_tap = with_linear ? taps.data() : nullptr;
   return forward_impl(plan, batch, bit_config, n_cfg, logits, ws, ws_bytes, stream, o);
+}
+
+// ---- stage Grams (p2vit_gram.hip; fp32 stages: the partial and reduce launches of p2vit_cka.hip) ------------------------------------------
+// aligned: the public rule (base and shift 16-byte aligned); the forward's own stages pass false and the kernels read what is unaligned with
+// scalar loads
+static int gram_check(const p2v_gram_layer& a, int n, bool aligned, const char* what, int l) {
+  if (n < 1 || n > P2V_GRAM_MAX_N) return fail(P2V_E_SHAPE, "%s: n = %d images, the kernels take 1 ... %d", what, n, P2V_GRAM_MAX_N);
+  if (!a.base) return fail(P2V_E_ARG, "%s: layer %d has a null base", what, l);
+  if (a.dtype != P2V_GRAM_I8 && a.dtype != P2V_GRAM_F32) return fail(P2V_E_ARG, "%s: layer %d: dtype %d (0 = int8, 1 = fp32)", what, l, a.dtype);
+  if (a.rows < 1 || a.cols < 1) return fail(P2V_E_SHAPE, "%s: layer %d: %d rows x %d cols", what, l, a.rows, a.cols);
+  if (a.row_stride < a.cols) return fail(P2V_E_ARG, "%s: layer %d: row_stride %lld < cols %d", what, l, a.row_stride, a.cols);
+  if (a.sample_stride < 0) return fail(P2V_E_ARG, "%s: layer %d: negative sample_stride %lld", what, l, a.sample_stride);
+  if (a.shift && a.dtype != P2V_GRAM_I8) return fail(P2V_E_ARG, "%s: layer %d: the shift bytes go with int8 codes", what, l);
+  if (aligned && ((uintptr_t)a.base % 16 || (uintptr_t)a.shift % 16))
+    return fail(P2V_E_ARG, "%s: layer %d: base and shift must be 16-byte aligned", what, l);
+  if (a.dtype == P2V_GRAM_F32 && (uintptr_t)a.base % 4) return fail(P2V_E_ARG, "%s: layer %d: the plane is not aligned to its element", what, l);
+  if ((long long)a.rows * a.cols >= (1LL << 31))
+    return fail(P2V_E_UNSUPPORTED, "%s: layer %d: %d x %d elements per sample (at most 2^31 - 1)", what, l, a.rows, a.cols);
+  if (a.dtype == P2V_GRAM_F32 && a.rows > 1 && a.row_stride != a.cols)
+    return fail(P2V_E_UNSUPPORTED, "%s: layer %d: an fp32 stage needs dense rows (row_stride %lld, cols %d)", what, l, a.row_stride, a.cols);
+  if (a.dtype == P2V_GRAM_F32 && a.sample_stride < (long long)a.rows * a.cols && n > 1)
+    return fail(P2V_E_ARG, "%s: layer %d: sample_stride %lld < rows * cols", what, l, a.sample_stride);
+  if (p2v_gram_items(p2v_gram_desc(a), n) >= (1LL << 31)) return fail(P2V_E_UNSUPPORTED, "%s: layer %d: too many partial tiles", what, l);
+  return P2V_OK;
+}
+static p2v_cka_layer gram_as_cka(const p2v_gram_layer& a) {
+  return p2v_cka_layer{reinterpret_cast<const float*>(a.base), nullptr, (long long)a.rows * a.cols, a.sample_stride, 0};
+}
+// the partials of one layer, a multiple of 256 bytes (the layers of one call run one after the other on one stream and share them)
+static size_t gram_ws_bytes(const p2v_gram_layer& a, int n) {
+  if (a.dtype == P2V_GRAM_F32) {
+    const p2v_cka_layer c = gram_as_cka(a);
+    return (p2v_cka_layout(&c, 1, n, nullptr).g64_off + 255) / 256 * 256;       // descriptor and chunk partials; the fp64 Gram goes to the output
+  }
+  return (size_t)p2v_gram_items(p2v_gram_desc(a), n) * 1024 * sizeof(long long);
+}
+static int gram_launch(const p2v_gram_layer& a, int n, double* G, void* ws, hipStream_t st) {
+  if (a.dtype == P2V_GRAM_F32) {
+    const p2v_cka_layer c = gram_as_cka(a);
+    std::vector<CkaDesc> descs;
+    const CkaLayout w = p2v_cka_layout(&c, 1, n, &descs);
+    return p2v_launch_cka_raw(descs[0], w, n, G, ws, st);
+  }
+  return p2v_launch_gram_i8(p2v_gram_desc(a), n, reinterpret_cast<long long*>(ws), G, st);
+}
+
+size_t p2v_code_grams_workspace_bytes(const p2v_gram_layer* layers, int n_layers, int n) {
+  if (!layers || n_layers <= 0) return 0;
+  size_t need = 0;
+  for (int l = 0; l < n_layers; ++l) {
+    if (gram_check(layers[l], n, true, "p2v_code_grams_workspace_bytes", l) != P2V_OK) return 0;
+    const size_t b = gram_ws_bytes(layers[l], n);
+    need = b > need ? b : need;
+  }
+  return need;
+}
+
+int p2v_code_grams(const p2v_gram_layer* layers, int n_layers, int n, double* grams, void* ws, size_t ws_bytes, void* stream) {
+  if (!layers || n_layers <= 0) return fail(P2V_E_ARG, "p2v_code_grams: no layers");
+  if (!grams || !ws) return fail(P2V_E_ARG, "p2v_code_grams: null grams / workspace");
+  if ((uintptr_t)grams % 8) return fail(P2V_E_ARG, "p2v_code_grams: grams must be 8-byte aligned");
+  if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_code_grams: the workspace must be 256-byte aligned");
+  size_t need = 0;
+  for (int l = 0; l < n_layers; ++l) {
+    const int rc = gram_check(layers[l], n, true, "p2v_code_grams", l);
+    if (rc != P2V_OK) return rc;
+    const size_t b = gram_ws_bytes(layers[l], n);
+    need = b > need ? b : need;
+  }
+  if (ws_bytes < need) return fail(P2V_E_WORKSPACE, "p2v_code_grams: workspace %zu < %zu bytes", ws_bytes, need);
+  for (int l = 0; l < n_layers; ++l) {
+    const int rc = launch_rc(gram_launch(layers[l], n, grams + (size_t)l * n * n, ws, (hipStream_t)stream), "code_grams");
+    if (rc != P2V_OK) return rc;
+  }
+  return P2V_OK;
+}
+
+int p2v_cka_centre(const double* raw, long long pitch, long long layer_stride, int n_layers, int n, float* grams, void* stream) {
+  if (!raw || !grams || n_layers <= 0) return fail(P2V_E_ARG, "p2v_cka_centre: null gram or no layers");
+  if (n < P2V_CKA_MIN_N || n > P2V_GRAM_MAX_N) return fail(P2V_E_SHAPE, "p2v_cka_centre: n = %d images, the kernel takes %d ... %d", n, P2V_CKA_MIN_N, P2V_GRAM_MAX_N);
+  if (pitch < n || layer_stride < 0) return fail(P2V_E_ARG, "p2v_cka_centre: pitch %lld < n = %d, or a negative layer stride", pitch, n);
+  if ((uintptr_t)raw % 8 || (uintptr_t)grams % 4) return fail(P2V_E_ARG, "p2v_cka_centre: misaligned gram");
+  return launch_rc(p2v_launch_gram_centre(raw, pitch, layer_stride, n_layers, n, grams, (hipStream_t)stream), "cka_centre");
+}
+
+int p2v_plan_prepare_grams(p2v_plan* plan) {
+  if (!plan) return fail(P2V_E_ARG, "p2v_plan_prepare_grams: null plan");
+  if (!plan->embed_set) return fail(P2V_E_STATE, "p2v_plan_prepare_grams: plan incomplete (embed)");
+  for (int i = 0; i < plan->d.depth; ++i)
+    if (!plan->block_set[i]) return fail(P2V_E_STATE, "p2v_plan_prepare_grams: plan incomplete (block %d)", i);
+  const int D = plan->d.embed_dim, Dp = round_up(D, 16);
+  std::vector<const float*> vecs{plan->embed_epi.s_next};
+  for (const p2v_block& b : plan->blocks) {
+    vecs.push_back(b.proj_epi.s_mid); vecs.push_back(b.proj_epi.s_next);
+    vecs.push_back(b.fc2_epi.s_mid); vecs.push_back(b.fc2_epi.s_next);
+  }
+  for (const float* v : vecs)
+    if (!v) return fail(P2V_E_STATE, "p2v_plan_prepare_grams: a stage of the plan has no per-channel scales");
+  OwnerDevice dev(vecs[0]);
+  if (!dev.ok()) return fail(P2V_E_ARG, "p2v_plan_prepare_grams: cannot locate the device of the plan's scales");
+  if (hipDeviceSynchronize() != hipSuccess) return fail(P2V_E_LAUNCH, "p2v_plan_prepare_grams: %s", hipGetErrorString(hipGetLastError()));
+  std::vector<float> host(D);
+  std::vector<uint8_t> bytes(vecs.size() * (size_t)Dp, 0);
+  std::vector<p2v_plan::GramScale> found;
+  for (size_t v = 0; v < vecs.size(); ++v) {
+    if (hipMemcpy(host.data(), vecs[v], (size_t)D * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(P2V_E_LAUNCH, "p2v_plan_prepare_grams: %s", hipGetErrorString(hipGetLastError()));
+    float lo = host[0];
+    for (int c = 1; c < D; ++c) lo = host[c] < lo ? host[c] : lo;
+    if (!(lo > 0.f) || !(lo < INFINITY)) return fail(P2V_E_UNSUPPORTED, "p2v_plan_prepare_grams: scale vector %zu holds %g", v, lo);
+    for (int c = 0; c < D; ++c) {
+      const float q = host[c] / lo;
+      const int m = q == 1.f ? 0 : q == 2.f ? 1 : q == 4.f ? 2 : q == 8.f ? 3 : -1;
+      if (m < 0 || lo * q != host[c])
+        return fail(P2V_E_UNSUPPORTED, "p2v_plan_prepare_grams: scale vector %zu: s[%d] / min s = %g is not 1, 2, 4 or 8", v, c, (double)host[c] / lo);
+      bytes[v * Dp + c] = (uint8_t)m;
+    }
+    found.push_back(p2v_plan::GramScale{vecs[v], nullptr, (double)lo});
+  }
+  uint8_t* buf = plan->gram_shift_buf;
+  if (!buf && hipMalloc(&buf, bytes.size()) != hipSuccess) return fail(P2V_E_LAUNCH, "p2v_plan_prepare_grams: %s", hipGetErrorString(hipGetLastError()));
+  plan->gram_shift_buf = buf;
+  if (plan->device < 0) plan->device = dev.own;
+  if (hipMemcpy(buf, bytes.data(), bytes.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(P2V_E_LAUNCH, "p2v_plan_prepare_grams: %s", hipGetErrorString(hipGetLastError()));
+  for (size_t v = 0; v < found.size(); ++v) found[v].shift = buf + v * Dp;
+  plan->gram_scales = found;
+  plan->grams_ready = true;
+  return P2V_OK;
+}
+
+static int grams_stage_set_check(const p2v_plan* plan, int stage_set, const char* who) {
+  if (!plan) return fail(P2V_E_ARG, "%s: null argument", who);
+  if (stage_set >= 0 && stage_set <= (P2V_DDV_STAGES_FULL | P2V_DDV_STAGES_ATTN) && (stage_set & P2V_DDV_STAGES_ATTN))
+    return fail(P2V_E_UNSUPPORTED, "%s: P2V_DDV_STAGES_ATTN: the exponent planes of the attention stages are no byte codes", who);
+  return stats_stage_set_check(plan, stage_set, who);
+}
+
+// the layout pass: forward_impl's own sequence with no launch made, every stage site listing itself
+static int grams_layout(const p2v_plan* plan, int with_linear, int stage_set, std::vector<GramStage>* out) {
+  int rc = grams_stage_set_check(plan, stage_set, "p2v_forward_grams_layout");
+  if (rc != P2V_OK) return rc;
+  void* const some = reinterpret_cast<void*>(256);      // never dereferenced: nothing is launched
+  std::vector<int8_t> cfg(plan->n_layers);
+  for (int i = 0; i < plan->n_layers; ++i) cfg[i] = plan->lin_set[bit_index(8)][i] ? 8 : 4;
+  GramsCtx gc{plan, nullptr, nullptr, nullptr, 0, out, {}};
+  DdvCtx ctx{1, nullptr, 0, nullptr, with_linear ? reinterpret_cast<float*>(some) : nullptr, 0};
+  ctx.scratch = (stage_set & P2V_DDV_STAGES_FULL) ? reinterpret_cast<float*>(some) : nullptr;
+  ctx.grams = &gc;
+  FwdOpts o;
+  o.images = reinterpret_cast<const float*>(some); o.ddv = &ctx; o.dry = true;
+  return forward_impl(const_cast<p2v_plan*>(plan), 1, cfg.data(), plan->n_layers, reinterpret_cast<float*>(some), some, (size_t)-1, nullptr, o);
+}
+
+int p2v_forward_grams_stage_count(const p2v_plan* plan, int with_linear, int stage_set) {
+  const int rc = grams_stage_set_check(plan, stage_set, "p2v_forward_grams_stage_count");
+  return rc != P2V_OK ? rc : p2v_ddv_stage_count_ex(plan, with_linear, stage_set);
+}
+
+// the partials of the largest stage at `batch` samples (the forward's stages are dense or pitched planes of its own buffers)
+static size_t grams_partial_bytes(const std::vector<GramStage>& st, int batch) {
+  size_t need = 0;
+  for (const GramStage& s : st) {
+    const p2v_gram_layer l{reinterpret_cast<const void*>(256), nullptr, (long long)s.rows * s.cols, s.cols, s.rows, s.cols, s.kind};
+    const size_t b = gram_ws_bytes(l, batch);
+    need = b > need ? b : need;
+  }
+  return need;
+}
+
+size_t p2v_forward_grams_bytes(const p2v_plan* plan, int batch, int with_linear, int stage_set) {
+  std::vector<GramStage> st;
+  if (batch < 1 || batch > P2V_GRAM_MAX_N || grams_layout(plan, with_linear, stage_set, &st) != P2V_OK) return 0;
+  return ws_layout(plan, batch).total + grams_partial_bytes(st, batch);        // (the forward's part is a multiple of 256 bytes)
+}
+
+int p2v_forward_grams_layout(const p2v_plan* plan, int with_linear, int stage_set, int max_stages, int32_t* rows, int32_t* cols,
+                             int32_t* kinds, const float** scales) {
+  std::vector<GramStage> st;
+  const int rc = grams_layout(plan, with_linear, stage_set, &st);
+  if (rc != P2V_OK) return rc;
+  for (int k = 0; k < (int)st.size() && k < max_stages; ++k) {
+    if (rows) rows[k] = st[k].rows;
+    if (cols) cols[k] = st[k].cols;
+    if (kinds) kinds[k] = st[k].kind;
+    if (scales) scales[k] = st[k].scale;
+  }
+  return (int)st.size();
+}
+
+int p2v_forward_grams(p2v_plan* plan, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                      size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, double* grams,
+                      size_t grams_bytes, double* units, size_t units_bytes, void* stream) {
+  if (!plan || !grams || !units || !ws) return fail(P2V_E_ARG, "p2v_forward_grams: null argument");
+  std::vector<GramStage> stages;
+  int rc = grams_layout(plan, with_linear, stage_set, &stages);
+  if (rc != P2V_OK) return rc;
+  if (!plan->grams_ready) return fail(P2V_E_STATE, "p2v_forward_grams: call p2v_plan_prepare_grams on the finished plan first");
+  const bool full = stage_set & P2V_DDV_STAGES_FULL;
+  if (batch < 1 || batch > P2V_GRAM_MAX_N) return fail(P2V_E_SHAPE, "p2v_forward_grams: batch = %d images, the kernels take 1 ... %d", batch, P2V_GRAM_MAX_N);
+  if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_forward_grams: the workspace must be 256-byte aligned");
+  if ((uintptr_t)grams % 8 || (uintptr_t)units % 8) return fail(P2V_E_ARG, "p2v_forward_grams: grams and units must be 8-byte aligned");
+  const size_t K = stages.size();
+  if (grams_bytes < K * batch * batch * sizeof(double))
+    return fail(P2V_E_WORKSPACE, "p2v_forward_grams: grams %zu < %zu bytes", grams_bytes, K * batch * batch * sizeof(double));
+  if (units_bytes < K * sizeof(double)) return fail(P2V_E_WORKSPACE, "p2v_forward_grams: units %zu < %zu bytes", units_bytes, K * sizeof(double));
+  const size_t fwd = ws_layout(plan, batch).total, part = grams_partial_bytes(stages, batch);
+  if (ws_bytes < fwd + part) return fail(P2V_E_WORKSPACE, "p2v_forward_grams: workspace %zu < %zu bytes", ws_bytes, fwd + part);
+  const int n = (batch + 1) / 2;                        // the scratch size is the DDV call's, which counts pairs of images
+  if (full && !tap_scratch)
+    return fail(P2V_E_WORKSPACE, "p2v_forward_grams: the FULL stage set needs tap_scratch (%zu bytes) whatever with_linear says", p2v_ddv_tap_scratch_bytes(plan, n));
+  if (with_linear || full) {
+    if (!tap_scratch) return fail(P2V_E_ARG, "p2v_forward_grams: with_linear needs tap_scratch");
+    if ((uintptr_t)tap_scratch % 16) return fail(P2V_E_ARG, "p2v_forward_grams: tap_scratch must be 16-byte aligned");
+    if (tap_scratch_bytes < p2v_ddv_tap_scratch_bytes(plan, n))
+      return fail(P2V_E_WORKSPACE, "p2v_forward_grams: tap_scratch %zu < %zu bytes", tap_scratch_bytes, p2v_ddv_tap_scratch_bytes(plan, n));
+  }
+  GramsCtx gc{plan, grams, units, reinterpret_cast<char*>(ws) + fwd, part, nullptr, {}};
+  gc.host_units.reserve(K);
+  DdvCtx ctx{batch, nullptr, 0, nullptr, with_linear ? tap_scratch : nullptr, 0};
+  ctx.scratch = full ? tap_scratch : nullptr;
+  ctx.grams = &gc;
+  std::vector<float*> taps;
+  if (with_linear) {
+    taps.assign(plan->n_layers, tap_scratch);      // every linear output goes through the one buffer; the patch embedding is no stage
+    taps[0] = nullptr;
+  }
+  FwdOpts o;
+  o.images = images; o.ddv = &ctx; o.lin_tap = with_linear ? taps.data() : nullptr;
+  rc = forward_impl(plan, batch, bit_config, n_cfg, logits, ws, fwd, stream, o);
+  if (rc != P2V_OK) return rc;
+  if (gc.host_units.size() != K) return fail(P2V_E_STATE, "p2v_forward_grams: %zu stages ran, the layout lists %zu", gc.host_units.size(), K);
+  // pageable source: the runtime stages it before returning, so the host vector may go away afterwards
+  if (hipMemcpyAsync(units, gc.host_units.data(), K * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
+    return fail(P2V_E_LAUNCH, "p2v_forward_grams: %s", hipGetErrorString(hipGetLastError()));
+  return P2V_OK;
 }

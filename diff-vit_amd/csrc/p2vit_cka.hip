@@ -230,6 +230,21 @@ int p2v_launch_cka_grams(const std::vector<CkaDesc>& descs, const CkaLayout& w, 
   return 0;
 }
 
+int p2v_launch_cka_raw(const CkaDesc& desc, const CkaLayout& w, int n, double* g64, void* ws, hipStream_t st) {
+  char* base = reinterpret_cast<char*>(ws);
+  CkaDesc* dd = reinterpret_cast<CkaDesc*>(base + w.desc_off);
+  float* parts = reinterpret_cast<float*>(base + w.part_off);
+  if (w.items >= (1LL << 31)) return -1;
+  hipError_t e = hipMemcpyAsync(dd, &desc, sizeof(CkaDesc), hipMemcpyHostToDevice, st);      // (pageable source: staged before the call returns)
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(k_cka_partial, dim3((unsigned)w.items), dim3(256), 0, st, dd, 1, n, parts);
+  CHECK_LAUNCH();
+  const long long total = (long long)n * n;
+  hipLaunchKernelGGL(k_cka_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dd, n, parts, g64, total);
+  CHECK_LAUNCH();
+  return 0;
+}
+
 int p2v_launch_hsic(const float* g1, int l1, const float* g2, int l2, int n, void* acc, void* self1, void* self2, int dtype, hipStream_t st) {
   const unsigned blocks = (unsigned)(l1 * l2 + (self1 ? l1 : 0) + (self2 ? l2 : 0));
   const long long nn = (long long)n * n;

@@ -150,6 +150,8 @@ struct CkaLayout {
 };
 CkaLayout p2v_cka_layout(const p2v_cka_layer* layers, int L, int n, std::vector<CkaDesc>* descs);
 int p2v_launch_cka_grams(const std::vector<CkaDesc>& descs, const CkaLayout& w, int n, float* grams, void* ws, hipStream_t st);
+// the raw form p2v_code_grams takes for an fp32 stage: k_cka_partial and k_cka_reduce of ONE layer, the uncentred fp64 Gram (zero diagonal) to g64
+int p2v_launch_cka_raw(const CkaDesc& desc, const CkaLayout& w, int n, double* g64, void* ws, hipStream_t st);
 int p2v_launch_hsic(const float* g1, int l1, const float* g2, int l2, int n, void* acc, void* self1, void* self2, int dtype, hipStream_t st);
 
 // pair-cosine sums of the DDV model diff (p2vit_ddv.hip): one record per stage
@@ -194,6 +196,22 @@ struct StatsDesc {
 StatsDesc p2v_stats_desc(const p2v_stat_layer& l, void* rec);
 int p2v_launch_stats(const StatsDesc& d, hipStream_t st);
 int p2v_launch_stats_init(void* rec, size_t bytes, int kind, int cols, hipStream_t st);
+
+// integer Grams of a stage's codes (p2vit_gram.hip): one record per stage, passed to the launches by value
+struct GramDesc {
+  const int8_t* base;
+  const uint8_t* shift;  // per-column exponents m_c [cols] or null
+  long long sample_stride, row_stride;   // in elements
+  long long groups;      // rows * cg: the 16-byte column groups of a sample (its features, rows padded to whole groups)
+  int rows, cols;
+  int cg;                // column groups per row
+  int nchunks;           // chunks of P2V_GRAM_CHUNK / 16 groups
+  int vec;               // base and strides are 16-byte aligned: whole column groups are read with one 16-byte load
+};
+GramDesc p2v_gram_desc(const p2v_gram_layer& l);
+long long p2v_gram_items(const GramDesc& d, int n);    // workgroups of k_gram_partial = int64 [32][32] partial tiles
+int p2v_launch_gram_i8(const GramDesc& d, int n, long long* partials, double* G, hipStream_t st);
+int p2v_launch_gram_centre(const double* raw, long long pitch, long long layer_stride, int L, int n, float* grams, hipStream_t st);
 
 // scoring of the logits (p2vit_score.hip): one record per row, then the fold into a totals slot (p2v_score_logits / p2v_score_accumulate)
 int p2v_launch_score_rows(const float* logits, long long ld, int rows, int classes, const long long* labels, int* ranks, double* loss,

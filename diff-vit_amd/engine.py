@@ -121,6 +121,16 @@ class StatLayer(C.Structure):
     _fields_ = [('base', _p), ('sample_stride', _ll), ('row_stride', _ll), ('samples', _i), ('rows', _i), ('cols', _i), ('dtype', _i)]
 
 
+GRAM_I8, GRAM_F32 = 0, 1                      # P2V_GRAM_*: the element kinds of the stage Grams
+GRAM_MAX_N, GRAM_CHUNK = 512, 8192            # P2V_GRAM_MAX_N, P2V_GRAM_CHUNK
+
+
+class GramLayer(C.Structure):
+    """``p2v_gram_layer``: one stage of ``p2v_code_grams`` (n samples of rows x cols int8 codes or fp32 values; strides in elements; shift
+    None or the per-column exponent bytes [cols])."""
+    _fields_ = [('base', _p), ('shift', _p), ('sample_stride', _ll), ('row_stride', _ll), ('rows', _i), ('cols', _i), ('dtype', _i)]
+
+
 class P2VError(RuntimeError):
     pass
 
@@ -212,6 +222,18 @@ def lib():
         L.p2v_forward_stats_bytes.restype = C.c_size_t
         L.p2v_forward_stats_layout.argtypes = [_p, _i, _i, _i, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), C.POINTER(_p)]
         L.p2v_forward_stats.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _i, _p, C.c_size_t, _p, C.c_size_t, _p,
+                                        C.c_size_t, _p]
+    if hasattr(L, 'p2v_code_grams'):              # the stage Grams are additive, found by their symbols
+        L.p2v_code_grams_workspace_bytes.argtypes = [C.POINTER(GramLayer), _i, _i]
+        L.p2v_code_grams_workspace_bytes.restype = C.c_size_t
+        L.p2v_code_grams.argtypes = [C.POINTER(GramLayer), _i, _i, _p, _p, C.c_size_t, _p]
+        L.p2v_cka_centre.argtypes = [_p, _ll, _ll, _i, _i, _p, _p]
+        L.p2v_plan_prepare_grams.argtypes = [_p]
+        L.p2v_forward_grams_stage_count.argtypes = [_p, _i, _i]
+        L.p2v_forward_grams_bytes.argtypes = [_p, _i, _i, _i]
+        L.p2v_forward_grams_bytes.restype = C.c_size_t
+        L.p2v_forward_grams_layout.argtypes = [_p, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_p)]
+        L.p2v_forward_grams.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _i, _p, C.c_size_t, _p, C.c_size_t, _p,
                                         C.c_size_t, _p]
     if hasattr(L, 'p2v_score_logits'):            # the scoring entry points are additive, found by their symbols
         L.p2v_score_logits.argtypes = [_p, _ll, _i, _i, _p, _p, _p, _p]

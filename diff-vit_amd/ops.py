@@ -17,6 +17,8 @@ one without the built library raises ``RuntimeError`` from ``engine.lib()``.
     torch.ops.p2vit.score_logits(logits, labels)                                tie-aware ranks + fp64 loss  test_quant.py:430-436, 488-501
     torch.ops.p2vit.score_accumulate(ranks, loss, ks, totals)                   running totals of a pass   test_quant.py:437-439
     torch.ops.p2vit.code_stats(tensors)                                         per-channel ranges, histogram, sums   plot_distrib.py:30-61
+    torch.ops.p2vit.code_grams(tensors, shifts)                                 raw fp64 Grams X X^T of codes / values   DDV_CKA.py (MinibatchAdvCKA)
+    torch.ops.p2vit.cka_centre(raw)                                             the centring of _generate_gram_matrix   efficient_CKA.py:28-39
 """
 import ctypes as C
 
@@ -40,6 +42,8 @@ _LIB.define('pair_cosine(Tensor[] a, Tensor[] b, Tensor?[] scales) -> Tensor')
 _LIB.define('score_logits(Tensor logits, Tensor labels) -> (Tensor ranks, Tensor loss)')
 _LIB.define('score_accumulate(Tensor ranks, Tensor loss, int[] ks, Tensor(a!) totals) -> ()')
 _LIB.define('code_stats(Tensor[] tensors) -> Tensor[]')
+_LIB.define('code_grams(Tensor[] tensors, Tensor?[] shifts) -> Tensor')
+_LIB.define('cka_centre(Tensor raw) -> Tensor')
 
 
 def _f32(t):
@@ -367,6 +371,74 @@ def _code_stats(tensors, records=None):
     return out
 
 
+def _gram_view(t, n):
+    """(tensor kept alive, kind, rows, cols, sample stride, row stride) of ``t`` = [n, ..., cols] int8 codes or floats for
+    ``p2v_code_grams``.  A [n, rows, cols] int8 view (last stride 1, any row and sample stride) on a 16-byte aligned base is read in place;
+    anything else is made contiguous (fp32 stages need dense rows)."""
+    if t.dim() < 2 or t.shape[0] != n or t[0].numel() < 1:
+        raise AssertionError('code_grams: every tensor is [%d, ..., cols] (got shape %s)' % (n, tuple(t.shape)))
+    if t.dtype != torch.int8:
+        x = _f32(t).reshape(n, -1)
+        if x.data_ptr() % 16:
+            x = x.clone()
+        return x, E.GRAM_F32, 1, x.shape[1], x.shape[1], x.shape[1]
+    if t.dim() == 3 and t.stride(2) == 1 and t.stride(1) >= t.shape[2] and t.stride(0) >= 0 and t.data_ptr() % 16 == 0:
+        return t, E.GRAM_I8, t.shape[1], t.shape[2], t.stride(0), t.stride(1)
+    x = t.reshape(n, -1, t.shape[-1]).contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    return x, E.GRAM_I8, x.shape[1], x.shape[2], x.shape[1] * x.shape[2], x.shape[2]
+
+
+def _code_grams(tensors, shifts):
+    """raw Grams fp64 [stages, n, n] (p2v_code_grams): tensors[k] holds n samples, int8 codes (shifts[k]: None or the uint8 exponents m_c of
+    the LAST dimension, the values are code * 2^m_c) or floats (fp32 Gram with a zero diagonal)."""
+    if not tensors or len(shifts) != len(tensors):
+        raise AssertionError('code_grams: %d tensors, %d shifts' % (len(tensors), len(shifts)))
+    n, dev = tensors[0].shape[0] if tensors[0].dim() else 0, tensors[0].device
+    keep, lays = [], (E.GramLayer * len(tensors))()
+    for k, (t, sh) in enumerate(zip(tensors, shifts)):
+        if t.device != dev:
+            raise AssertionError('code_grams: every tensor must be on %s' % dev)
+        x, kind, rows, cols, ss, rs = _gram_view(t, n)
+        keep.append(x)
+        d = lays[k]
+        d.base, d.sample_stride, d.row_stride, d.rows, d.cols, d.dtype = x.data_ptr(), ss, rs, rows, cols, kind
+        if sh is not None:
+            if kind != E.GRAM_I8 or sh.numel() != cols or sh.device != dev:
+                raise AssertionError('code_grams: stage %d: shifts go with int8 codes, one byte per element of the last dimension, on %s' % (k, dev))
+            sh = sh.reshape(-1).to(torch.uint8).contiguous()
+            if sh.data_ptr() % 16:
+                sh = sh.clone()
+            keep.append(sh)
+            d.shift = sh.data_ptr()
+    L = E.lib()
+    with torch.cuda.device(dev):
+        nbytes = L.p2v_code_grams_workspace_bytes(lays, len(tensors), n)
+        if nbytes == 0:
+            E.check(L.p2v_code_grams(lays, len(tensors), n, None, None, 0, None))       # raises with the validation message
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(len(tensors), n, n, dtype=torch.float64, device=dev)
+        E.check(L.p2v_code_grams(lays, len(tensors), n, E.ptr(out), E.ptr(ws), nbytes, E.stream_ptr(dev)))
+    return out
+
+
+def _cka_centre(raw):
+    """centred fp32 Grams [layers, n, n] of raw fp64 Grams [layers, n, n] (p2v_cka_centre); a view with a row pitch and a layer stride -
+    the off-diagonal block ``big[:, :n, n:]`` of [layers, 2n, 2n] Grams, which centres as the X Y^T form - is read in place."""
+    if raw.dim() == 2:
+        raw = raw.unsqueeze(0)
+    if raw.dim() != 3 or raw.shape[1] != raw.shape[2]:
+        raise AssertionError('cka_centre: raw Grams are [layers, n, n] (got shape %s)' % (tuple(raw.shape),))
+    if raw.dtype != torch.float64 or raw.stride(2) != 1 or raw.stride(1) < raw.shape[2] or raw.stride(0) < 0:
+        raw = raw.double().contiguous()
+    Ln, n = raw.shape[0], raw.shape[1]
+    out = torch.empty(Ln, n, n, dtype=torch.float32, device=raw.device)
+    with torch.cuda.device(raw.device):
+        E.check(E.lib().p2v_cka_centre(raw.data_ptr(), raw.stride(1), raw.stride(0), Ln, n, E.ptr(out), E.stream_ptr(raw.device)))
+    return out
+
+
 _LIB.impl('fake_quant', _fake_quant, 'CUDA')
 _LIB.impl('quantize_patchify', _quantize_patchify, 'CUDA')
 _LIB.impl('linear_requant', lambda x, w, cs, b, inv: _linear(E.EPI_REQUANT, x, w, cs, b, inv), 'CUDA')
@@ -381,6 +453,8 @@ _LIB.impl('pair_cosine', _pair_cosine, 'CUDA')
 _LIB.impl('score_logits', _score_logits, 'CUDA')
 _LIB.impl('score_accumulate', _score_accumulate, 'CUDA')
 _LIB.impl('code_stats', lambda tensors: _code_stats(tensors), 'CUDA')
+_LIB.impl('code_grams', _code_grams, 'CUDA')
+_LIB.impl('cka_centre', _cka_centre, 'CUDA')
 
 OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'lis_attention_rows', 'forward', 'cka_grams',
-       'hsic_accumulate', 'pair_cosine', 'score_logits', 'score_accumulate', 'code_stats')
+       'hsic_accumulate', 'pair_cosine', 'score_logits', 'score_accumulate', 'code_stats', 'code_grams', 'cka_centre')

@@ -602,6 +602,50 @@ class FrozenPlan:
                                         E.ptr(into.arena), into.arena.numel(), E.stream_ptr(self.device)))
         return out, into
 
+    def forward_grams(self, images, bit_config, with_linear=False, stages='engine'):
+        """p2v_forward_grams: the logits of ``images`` (1 ... 512 images) and the raw Gram of every ``forward_ddv`` stage over the
+        batch, taken from the live codes right behind the launch that completes the stage.  Returns (logits, names, grams, units):
+        names = ``ddv_stage_names(with_linear, stages)``, grams fp64 [stages, B, B] - the exact integer sums of the stage values
+        code * 2^m_c for the int8 stages, the fp32 Gram with a zero diagonal for the fp32 ones - and units fp64 [stages], the value of
+        one integer step (values = integers * unit; CKA does not depend on it).  ``ops.cka_centre`` turns the Grams into the centred
+        ones of ``cka._grams``.  Stage sets and refusals are ``forward_ddv``'s; the attention stages are not served."""
+        images, cfg = self._check(images, bit_config)
+        B = images.shape[0]
+        L = E.lib()
+        names = self.ddv_stage_names(with_linear, stages, False)
+        full = stages == 'full'
+        if full and not self.input_quant:
+            raise NotImplementedError("forward_grams(stages='full'): no qact_input stage on an input_quant=False plan")
+        stage_set = E.DDV_STAGES_FULL if full else E.DDV_STAGES_ENGINE
+        n = (B + 1) // 2
+        with torch.cuda.device(self.device):
+            if not getattr(self, '_grams_ready', False):       # once per plan: the exponent bytes and units of the per-channel scale vectors
+                E.check(L.p2v_plan_prepare_grams(self._handle))
+                self._grams_ready = True
+            K = len(names)
+            assert K == L.p2v_forward_grams_stage_count(self._handle, int(with_linear), stage_set)
+            need = int(L.p2v_forward_grams_bytes(self._handle, B, int(with_linear), stage_set))
+            if need == 0:
+                E.check(L.p2v_forward_grams(self._handle, None, B, cfg, len(bit_config), None, None, 0, int(with_linear), stage_set, None, 0,
+                                            None, 0, None, 0, None))     # raises with the validation message
+            ws, out = self.workspace(B, need), self._out(None, B)
+            grams = torch.empty(K, B, B, dtype=torch.float64, device=self.device)
+            units = torch.empty(K, dtype=torch.float64, device=self.device)
+            tap = torch.empty(self.ddv_tap_bytes(n), dtype=torch.uint8, device=self.device) if (with_linear or full) else None
+            E.check(L.p2v_forward_grams(self._handle, E.ptr(images), B, cfg, len(bit_config), E.ptr(out), E.ptr(ws), ws.numel(), int(with_linear),
+                                        stage_set, E.ptr(tap), 0 if tap is None else tap.numel(), E.ptr(grams), grams.numel() * 8, E.ptr(units),
+                                        units.numel() * 8, E.stream_ptr(self.device)))
+            # a one-scale stage's unit is the scale the plan was frozen with (the stage sites of the C layer do not carry it)
+            one = [k for k, nm in enumerate(names) if nm in self.stage_scales]
+            kinds = (C.c_int32 * K)()
+            scales = (C.c_void_p * K)()
+            L.p2v_forward_grams_layout(self._handle, int(with_linear), stage_set, K, None, None, kinds, scales)
+            one = [k for k in one if kinds[k] == E.GRAM_I8 and not scales[k]]
+            if one:
+                units[torch.tensor(one, device=self.device)] = torch.tensor([self.stage_scales[names[k]] for k in one], dtype=torch.float64,
+                                                                            device=self.device)
+        return out, names, grams, units
+
     def slice_sizes(self, batch, n_streams=3):
         """Batch slices of ``forward_streams`` for up to ``n_streams`` side streams plus the caller's own stream (256 -> 68 + 68 + 68 + 52).
         Four kernels in flight on four hardware queues is what the device sustains - a fourth SIDE stream (five streams with the caller's)

@@ -1008,6 +1008,76 @@ int p2v_forward_stats(p2v_plan* plan, const float* images, int batch, const int8
                       size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, int8_t* attn_scratch,
                       size_t attn_scratch_bytes, void* stats, size_t stats_bytes, void* stream);
 
+/* ---- Stage Grams: CKA over the DDV stage list (additive: no structure, existing entry point or P2V_ABI_VERSION changes) ---------------
+ * efficient_CKA.MinibatchCKA / DDV_CKA.MinibatchAdvCKA take Gram matrices over hooked activations.  A STAGE is n samples (images) of
+ * rows x cols elements in the addressing of p2v_cos_layer: sample i at + i * sample_stride, row r at + r * row_stride (both in ELEMENTS,
+ * row_stride >= cols; only columns [0, cols) of a row are read).  The raw Gram of a stage is G[i][j] = sum_{r,c} v_i[r][c] * v_j[r][c],
+ * fp64 [n][n], with a `unit` such that the stage's values are v * unit:
+ *   P2V_GRAM_I8, shift == NULL   v = code.  G is the exact integer sum, returned as an (integer-valued) fp64.  unit = the stage's one scale.
+ *   P2V_GRAM_I8, shift != NULL   per-channel scales s_c = unit * 2^m_c with unit = min_c s_c (the PTF streams qact1 / qact2 / qact4 and the
+ *                                mid codes attn.qact3 / mlp.qact2: m_c in {0, 1, 2, 3}; a ptf = False plan repeats one scale, m_c = 0).
+ *                                v = code * 2^m_c with m_c = shift[c] (dev bytes [cols], 16-byte aligned; the low two bits are used).  G is
+ *                                again the exact integer sum.  The fp32 value a hook on the QAct sees is RN(code * s_c): it differs from
+ *                                v * unit by at most one fp32 rounding per element, and CKA does not depend on unit at all.
+ *   P2V_GRAM_F32                 v = the fp32 value, unit = 1, shift must be NULL: the chunked exact-product fp32 MFMA partials and the
+ *                                fixed-order fp64 combination of p2v_cka_grams (the same two launches), stored uncentred.  As there, the
+ *                                DIAGONAL IS ZERO (the Gram rule discards it before anything reads it).  Rows must be dense
+ *                                (row_stride == cols, or rows == 1): P2V_E_UNSUPPORTED otherwise.
+ * G is exactly symmetric: the 32 x 32 tiles ti <= tj are computed, the rest is their mirror.  Integer stages are exact while |G| < 2^53
+ * (always for one-scale codes: rows * cols * 2^14 < 2^45); rows * cols >= 2^31 is refused before any launch.  Integer kernel: one workgroup
+ * per (tile, chunk of P2V_GRAM_CHUNK features) on v_mfma_i32_32x32x32_i8, int32 within a chunk (at most 2^13 features * 2^14 = 2^27;
+ * shifted stages split code * 4^m into two byte planes, products at most 2^13), int64 partials, a second launch adds them in chunk order and
+ * converts once.  No atomics, fixed order: bitwise repeatable; the splitting depends on (n, rows, cols, dtype) only.
+ * p2v_code_grams: layers is a HOST array (used before the call returns), grams dev fp64 [n_layers][n][n] (8-byte aligned), 1 <= n <=
+ * P2V_GRAM_MAX_N (any n: edge tiles read and write nothing outside the stage and G); base pointers and shift 16-byte aligned (strides are
+ * free: 16-byte loads where base and strides allow them, a scalar tail otherwise); ws 256-byte aligned, p2v_code_grams_workspace_bytes
+ * (0: refused).  Two launches per layer on `stream` (fp32: a descriptor copy and two).  Refusals, all before the first HIP call: P2V_E_ARG
+ * (null / misaligned pointer, unknown dtype, row_stride < cols, negative sample_stride, shift on an fp32 stage), P2V_E_SHAPE (n, rows,
+ * cols < 1, n > P2V_GRAM_MAX_N), P2V_E_UNSUPPORTED (rows * cols >= 2^31, strided fp32 rows), P2V_E_WORKSPACE. */
+enum { P2V_GRAM_I8 = 0, P2V_GRAM_F32 = 1 };
+typedef struct p2v_gram_layer {
+  const void* base;      /* dev, n samples */
+  const uint8_t* shift;  /* dev bytes [cols] (int8 only) or NULL */
+  long long sample_stride, row_stride;   /* elements; row_stride >= cols */
+  int32_t rows, cols;    /* >= 1 each */
+  int32_t dtype;         /* P2V_GRAM_* */
+} p2v_gram_layer;
+#define P2V_GRAM_MAX_N 512
+#define P2V_GRAM_CHUNK 8192   /* features per int32 partial sum: 2^13 * 2^14 = 2^27 < 2^31 */
+size_t p2v_code_grams_workspace_bytes(const p2v_gram_layer* layers, int n_layers, int n);
+int p2v_code_grams(const p2v_gram_layer* layers, int n_layers, int n, double* grams, void* ws, size_t ws_bytes, void* stream);
+/* The centring rule of p2v_cka_grams (fp64 centring, fp32 store) on given raw Grams: entry (i, j) of layer l is raw[l * layer_stride +
+ * i * pitch + j] (fp64, strides in elements, pitch >= n); grams dev fp32 [n_layers][n][n].  The diagonal of raw is not read (it counts as
+ * zero).  With pitch = 2n and raw + n, the off-diagonal n x n block of a 2n x 2n Gram is centred as the X Y^T form - MinibatchAdvCKA's
+ * X X_adv^T.  P2V_CKA_MIN_N <= n <= P2V_GRAM_MAX_N.  One launch. */
+int p2v_cka_centre(const double* raw, long long pitch, long long layer_stride, int n_layers, int n, float* grams, void* stream);
+/* Once per plan, after every block and the embed stage are set (it synchronises, like the other plan setters): derives shift[c] and unit
+ * of every per-channel stage scale vector of the plan - the embed s_next, per block proj_epi.s_mid / s_next and fc2_epi.s_mid / s_next -
+ * into device bytes the plan owns.  P2V_E_UNSUPPORTED: a vector whose ratios s_c / min_c s_c are not all in {1, 2, 4, 8}; P2V_E_STATE: an
+ * incomplete plan. */
+int p2v_plan_prepare_grams(p2v_plan* plan);
+/* The raw Grams of every stage inside the fused forward: p2v_forward_stats's launch sequence, stage order and scratch rules, with `batch`
+ * images (1 ... P2V_GRAM_MAX_N, no pairs) and with_linear / stage_set in {P2V_DDV_STAGES_ENGINE, P2V_DDV_STAGES_FULL} as in
+ * p2v_forward_ddv_ex; right after the launch that completes a stage its Gram over all `batch` samples is taken from the live buffer.
+ * grams: dev fp64 [stages][batch][batch]; units: dev fp64 [stages] - min_c s_c of a per-channel stage, 1 of an fp32 stage, and 0 for a
+ * one-scale int8 stage, whose scale the stage sites do not carry (the layout reports scales == NULL for it; the caller holds the scale).
+ * Every row of the last block is computed, as in the tap entry points, and the logits are byte-equal to p2v_forward's.
+ *   p2v_forward_grams_stage_count   = p2v_ddv_stage_count_ex
+ *   p2v_forward_grams_bytes         the workspace: the forward's of `batch` images plus the partials of the largest stage (0: refused)
+ *   p2v_forward_grams_layout        per stage k < max_stages its rows, cols, kind (P2V_GRAM_*) and per-channel scales (dev fp32 [cols] or
+ *                                   NULL); any array may be NULL.  Returns the number of stages or a negative status.  It runs the
+ *                                   forward's own sequence with no launch made.
+ * Refusals before any launch: P2V_DDV_STAGES_ATTN (P2V_E_UNSUPPORTED: the exponent planes are no byte codes), a plan without
+ * p2v_plan_prepare_grams (P2V_E_STATE), those of p2v_forward_stats, a short ws or tap_scratch (P2V_E_WORKSPACE), grams_bytes < stages *
+ * batch^2 * 8 or units_bytes < stages * 8 (P2V_E_WORKSPACE). */
+int p2v_forward_grams_stage_count(const p2v_plan* plan, int with_linear, int stage_set);
+size_t p2v_forward_grams_bytes(const p2v_plan* plan, int batch, int with_linear, int stage_set);
+int p2v_forward_grams_layout(const p2v_plan* plan, int with_linear, int stage_set, int max_stages, int32_t* rows, int32_t* cols,
+                             int32_t* kinds, const float** scales);
+int p2v_forward_grams(p2v_plan* plan, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* ws,
+                      size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, double* grams,
+                      size_t grams_bytes, double* units, size_t units_bytes, void* stream);
+
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
 
