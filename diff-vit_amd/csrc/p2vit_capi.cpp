@@ -555,7 +555,14 @@ static int run_gemm(int epi, const int8_t* A, int lda, int M, int K, int N, cons
                     int ldo, int8_t* out_codes, hipStream_t st, bool few_rows = false) {
   const GemmArgs g = gemm_args(A, lda, M, lin.w_codes, K, N, lin, ep, out, ldo, out_codes);
   if (few_rows && g_gemm_rows != 2 && g_gemm_tile == 0 && !(epi == P2V_EPI_RESID && out_codes)) return launch_rc(p2v_launch_gemm_rows(epi, g, st), "gemm_rows");
-  return launch_rc(p2v_launch_gemm(epi, g, st), "gemm_i8");
+  const int rc = p2v_launch_gemm(epi, g, st);
+  if (rc == -4) {      // the tiled kernel's 32-bit lane offsets: name the bound that is passed, as p2v_gemm_resid_tap does for M * ldo
+    const long long a_bytes = (long long)M * lda + K, w_bytes = (long long)((N + 127) / 128) * 128 * K;
+    if (a_bytes >= (1LL << 32))
+      return fail(P2V_E_UNSUPPORTED, "gemm_i8: M * lda + K = %lld must stay below 2^32 = 4294967296, the 32-bit lane offsets of the tiled kernel", a_bytes);
+    return fail(P2V_E_UNSUPPORTED, "gemm_i8: round_up(N, 128) * K = %lld must stay below 2^32 = 4294967296, the 32-bit lane offsets of the tiled kernel", w_bytes);
+  }
+  return launch_rc(rc, "gemm_i8");
 }
 
 // QIntLayerNorm -> /cs -> qact0 -> QLinear -> (GELU) -> QAct in one launch (k_ln_gemm); a.out may be null

@@ -598,7 +598,7 @@ int p2v_launch_gemm(int epi, const GemmArgs& g0, hipStream_t st) {
     // "gemm_rows" = 1: the few-rows kernel wherever it applies (parity runs against this kernel); an explicit tile height means this kernel
     if (g_gemm_rows == 1 && g_gemm_tile == 0 && !(epi == P2V_EPI_RESID && g.out_codes)) return p2v_launch_gemm_rows(epi, g0, st);
     // the tiled kernel addresses both matrices with 32-bit lane offsets
-    if ((long long)g.M * g.lda + g.K >= (1LL << 32) || (long long)g.tiles_n * GBN * g.K >= (1LL << 32)) return -1;
+    if ((long long)g.M * g.lda + g.K >= (1LL << 32) || (long long)g.tiles_n * GBN * g.K >= (1LL << 32)) return -4;      // (named by run_gemm)
     // 256-row tiles (8 waves, two workgroups per CU) when the grid still gives every CU its two workgroups; else 128-row tiles
     const long long tiles256 = (long long)((g.M + 255) / 256) * g.tiles_n;
     // (packed int4 weights keep 128 rows: the 8-wave form moves a 4 KB W tile as eight half-wave pieces and measured 3 % slower on DeiT-B W4)

@@ -103,7 +103,7 @@ int p2v_launch_embed_fp32(const float* img, int B, int C, int H, int W, int P, c
 int p2v_launch_u8_patchify(const uint8_t* img, int B, int C, int H, int W, int P, int nhwc, const int8_t* lut, int8_t* out, int k_pad,
                            hipStream_t st);
 int p2v_launch_embed_u8(const uint8_t* img, int nhwc, const float* lut, int B, int C, int H, int W, int P, const GemmArgs& g, hipStream_t st);
-int p2v_launch_gemm(int epi, const GemmArgs& g, hipStream_t st);
+int p2v_launch_gemm(int epi, const GemmArgs& g, hipStream_t st);     // -4: M * lda + K or the padded weight matrix reaches 2^32 bytes (tiled kernel)
 // the few-rows kernel (p2vit_gemm_rows.hip): REQUANT / GELU / RESID at any M, parallel over N and K; -3: not one of its epilogues
 int p2v_launch_gemm_rows(int epi, const GemmArgs& g, hipStream_t st);
 // table of the pre-folded RESID epilogue (p2v_epilogue.resid_tab): [ceil(N/128)][6][128] floats; flags: dev [2] preset to {1, 0}

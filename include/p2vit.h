@@ -406,6 +406,8 @@ int p2v_u8_patchify(const uint8_t* img, int layout, const void* lut_i8, int batc
  * aligned, int8-stored weights (P2V_E_UNSUPPORTED for packed4: p2v_gemm_resid_tap below takes both).  Other epilogues ignore out_codes.
  * K is a multiple of 64 and MAY exceed lda (a width that is not a multiple of 64: the weight columns [width, K) are zero): the
  * contraction then walks into the next row, so (M-1)*lda + K bytes of A must be readable.  ldo >= N.  P2V_E_SHAPE otherwise.
+ * REQUANT / GELU / RESID run the tiled kernel, which addresses A and W with 32-bit lane offsets: M*lda + K < 2^32 and
+ * round_up(N, 128)*K < 2^32, P2V_E_UNSUPPORTED beyond (the message names the sums); `out` has no such bound.
  * Written: columns [0, N) of rows [0, M) of `out` (and of out_codes, same ldo) - never the columns [N, ldo) - and tap_out as a dense
  * [M][N]; P2V_EPI_EMBED: columns [0, N) of the rows b*(patches+1) + 1 + p, never a class-token row b*(patches+1). */
 int p2v_gemm_i8(int epilogue_kind, const int8_t* A, int lda, int M, int K, int N, const p2v_linear* lin,
