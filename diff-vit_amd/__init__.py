@@ -48,6 +48,8 @@ from . import stats  # noqa: F401
 from .stats import StageStats, code_stats_cpu, compute_stats  # noqa: F401
 from . import profiling  # noqa: F401
 from .profiling import gen_profiling_inputs_in_blackbox, metrics_output_diversity  # noqa: F401
+from . import psaq  # noqa: F401
+from .psaq import generate_data, patch_similarity_entropy  # noqa: F401
 
 __all__ = ['BIT_TYPE_DICT', 'QAct', 'QConv2d', 'QIntLayerNorm', 'QIntSoftmax', 'QLinear', 'Config', 'VisionTransformer',
            'deit_tiny_patch16_224', 'deit_small_patch16_224', 'deit_base_patch16_224', 'vit_base_patch16_224',
@@ -55,4 +57,5 @@ __all__ = ['BIT_TYPE_DICT', 'QAct', 'QConv2d', 'QIntLayerNorm', 'QIntSoftmax', '
            'swin_small_patch4_window7_224', 'swin_base_patch4_window7_224', 'swin_base_patch4_window12_384',
            'swin_large_patch4_window12_384', 'SwinPlan', 'get_activations', 'MinibatchCKA',
            'MinibatchAdvCKA', 'compute_cka', 'compute_ddv', 'gen_adv_inputs', 'AttackPGD', 'DeviceMeter', 'score_rows_reference',
-           'gen_profiling_inputs_in_blackbox', 'metrics_output_diversity', 'compute_stats', 'StageStats', 'code_stats_cpu']
+           'gen_profiling_inputs_in_blackbox', 'metrics_output_diversity', 'compute_stats', 'StageStats', 'code_stats_cpu',
+           'generate_data', 'patch_similarity_entropy']

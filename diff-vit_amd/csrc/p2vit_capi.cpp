@@ -1179,6 +1179,33 @@ int p2v_freeze_weights(const float* w, long long ldw, int N, int K, const float*
   return launch_rc(p2v_launch_freeze_weights(w, ldw, N, K, scale, n_scale, bits, layout, out, (hipStream_t)stream), "freeze_weights");
 }
 
+// ---- patch-similarity entropy (p2vit_psaq.hip)
+static int psaq_check(const char* who, int images, int groups, int heads, int tokens, int head_dim) {
+  if (images < 1 || groups < 1 || heads < 1) return fail(P2V_E_SHAPE, "%s: images %d, groups %d, heads %d must be positive", who, images, groups, heads);
+  if (tokens < 3 || tokens > 1025) return fail(P2V_E_SHAPE, "%s: %d tokens (2 ... 1024 patch rows behind the dropped first row)", who, tokens);
+  if (head_dim < 4 || head_dim > 128 || head_dim % 4) return fail(P2V_E_SHAPE, "%s: head_dim %d (a multiple of 4 up to 128)", who, head_dim);
+  const long long T = tokens - 1;
+  if ((long long)images * groups >= (1LL << 31) / (T * ((T + 31) / 32)))
+    return fail(P2V_E_SHAPE, "%s: %d x %d groups of %d tokens pass the grid of one launch", who, images, groups, tokens);
+  return P2V_OK;
+}
+
+size_t p2v_psaq_workspace_bytes(int images, int groups, int heads, int tokens, int head_dim) {
+  if (psaq_check("p2v_psaq_workspace_bytes", images, groups, heads, tokens, head_dim) != P2V_OK) return 0;
+  return (size_t)p2v_psaq_layout(images, groups, tokens, head_dim).bytes;
+}
+
+int p2v_patch_similarity_entropy(const float* av, int images, int groups, int heads, int tokens, int head_dim, void* workspace,
+                                 double* value_out, float* grad_out, void* stream) {
+  const int rc = psaq_check("p2v_patch_similarity_entropy", images, groups, heads, tokens, head_dim);
+  if (rc != P2V_OK) return rc;
+  if (!av || !workspace || !value_out || !grad_out) return fail(P2V_E_ARG, "p2v_patch_similarity_entropy: null argument");
+  if ((uintptr_t)av % 16 || (uintptr_t)grad_out % 16 || (uintptr_t)value_out % 8 || (uintptr_t)workspace % 256)
+    return fail(P2V_E_ARG, "p2v_patch_similarity_entropy: av / grad_out must be 16-byte, value_out 8-byte, workspace 256-byte aligned");
+  const PsaqArgs a = {av, images, groups, heads, tokens, head_dim};
+  return launch_rc(p2v_launch_psaq(a, workspace, value_out, grad_out, (hipStream_t)stream), "patch_similarity_entropy");
+}
+
 size_t p2v_resid_prefold_bytes(int N) { return N > 0 ? resid_tab_floats(N) * sizeof(float) : 0; }
 
 int p2v_resid_prefold(const p2v_linear* lin, const p2v_epilogue* epi, int N, float* tab, size_t tab_bytes, int* usable, void* stream) {

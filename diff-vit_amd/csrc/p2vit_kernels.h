@@ -274,3 +274,19 @@ struct WinSmArgs {
 };
 // head_dim 32, windows of 1 x 1 ... 12 x 12; -1: no instantiation
 int p2v_launch_window_softmax_attention(const WinSmArgs& a, hipStream_t st);
+
+// patch-similarity entropy and its gradient (p2vit_psaq.hip): the workspace sections in bytes from its 256-byte aligned start
+#define PSAQ_POINTS 10      // points of the density (generate_data.py:110)
+#define PSAQ_CHUNK 4096     // similarities per fp64 partial of the point sums
+struct PsaqLayout {
+  long long sims, ahat, norms, mm, range, psums, coef;   // S [B*G][T][T], A^ [B*G][T][hd], |a| [B*G][T], min / max partials, lo / hi, point-sum partials, coefficients
+  int sim_blocks, chunks;                                // workgroups of S per group, chunks per image
+  long long bytes;
+};
+struct PsaqArgs {
+  const float* av;
+  int B, G, H, N, hd;
+};
+PsaqLayout p2v_psaq_layout(int B, int G, int N, int hd);
+// -1: a launch grid beyond 2^31 workgroups
+int p2v_launch_psaq(const PsaqArgs& a, void* ws, double* value, float* grad, hipStream_t st);

@@ -267,6 +267,10 @@ def lib():
         L.p2v_freeze_bytes.argtypes = [_i, _i, _i]
         L.p2v_freeze_bytes.restype = C.c_size_t
         L.p2v_freeze_weights.argtypes = [_p, _ll, _i, _i, _p, _i, _i, _i, _p, C.c_size_t, _p]
+    if hasattr(L, 'p2v_patch_similarity_entropy'):      # the entropy term of the data-free calibration images, additive
+        L.p2v_psaq_workspace_bytes.argtypes = [_i, _i, _i, _i, _i]
+        L.p2v_psaq_workspace_bytes.restype = C.c_size_t
+        L.p2v_patch_similarity_entropy.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p]
     L.p2v_forward_profile.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_int32), _i]
     L.p2v_forward_profile_begin.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(_p)]

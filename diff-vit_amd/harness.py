@@ -38,7 +38,9 @@ def build_parser():
     p.add_argument('--quant-method', default='minmax', choices=['minmax', 'ema', 'omse', 'percentile'])
     p.add_argument('--mixed', default=False, action='store_true')
     p.add_argument('--calib-batchsize', default=50, type=int, help='batchsize of calibration set')
-    p.add_argument('--mode', default=1, type=int, help='calibration data: 1 Gaussian noise (offline default), 0/2 need real data')
+    p.add_argument('--mode', default=1, type=int, help='calibration data: 1 Gaussian noise (offline default), 0 real data (--real-data), '
+                   '2 images generated from the float model (psaq.generate_data)')
+    p.add_argument('--psaq-iters', default=500, type=int, help='--mode 2: Adam steps per epoch of the data generation (generate_data.py:66)')
     p.add_argument('--calib-iter', default=6, type=int)
     p.add_argument('--val-batchsize', default=50, type=int, help='batchsize of validation set')
     p.add_argument('--num-workers', default=16, type=int)
@@ -391,6 +393,12 @@ def main(argv=None):
             if calib_data.dtype == torch.uint8:                          # --uint8-input: the normalised batch, through the fp32 table
                 from .data import expand_uint8, uint8_lut
                 calib_data = expand_uint8(calib_data, uint8_lut(*uint8_stats(args)), 'NHWC')
+        elif args.mode == 2:
+            print('Generating data...')                                  # test_quant.py:205-208, mode 2: PSAQ-ViT images from the float model
+            from .data import model_family
+            from .psaq import generate_data
+            calib_data = generate_data(model, args.calib_batchsize, iterations=args.psaq_iters, family=model_family(args.model))
+            print('Calibrating with generated data...')
         else:
             print('Calibrating with Gaussian noise...')
             calib_data = synth.images(args.seed + 1, args.calib_batchsize, arch['img_size']).to(device)

@@ -19,6 +19,7 @@ one without the built library raises ``RuntimeError`` from ``engine.lib()``.
     torch.ops.p2vit.code_stats(tensors)                                         per-channel ranges, histogram, sums   plot_distrib.py:30-61
     torch.ops.p2vit.code_grams(tensors, shifts)                                 raw fp64 Grams X X^T of codes / values   DDV_CKA.py (MinibatchAdvCKA)
     torch.ops.p2vit.cka_centre(raw)                                             the centring of _generate_gram_matrix   efficient_CKA.py:28-39
+    torch.ops.p2vit.patch_similarity_entropy(av, groups)                        entropy term and its gradient   generate_data.py:102-113, 128-134
 """
 import ctypes as C
 
@@ -44,6 +45,7 @@ _LIB.define('score_accumulate(Tensor ranks, Tensor loss, int[] ks, Tensor(a!) to
 _LIB.define('code_stats(Tensor[] tensors) -> Tensor[]')
 _LIB.define('code_grams(Tensor[] tensors, Tensor?[] shifts) -> Tensor')
 _LIB.define('cka_centre(Tensor raw) -> Tensor')
+_LIB.define('patch_similarity_entropy(Tensor av, int groups) -> (Tensor value, Tensor grad)')
 
 
 def _f32(t):
@@ -439,6 +441,29 @@ def _cka_centre(raw):
     return out
 
 
+def _patch_similarity_entropy(av, groups):
+    """(value fp64 [], grad fp32 like av) of the patch-similarity entropy (p2v_patch_similarity_entropy): av [images * groups, heads,
+    tokens, head_dim], one block's attn @ v; the workspace is allocated here, nothing synchronises."""
+    if av.dim() != 4 or groups < 1 or av.shape[0] % max(groups, 1):
+        raise AssertionError('patch_similarity_entropy: av is [images * groups, heads, tokens, head_dim] (got shape %s, groups %d)'
+                             % (tuple(av.shape), groups))
+    av = _f32(av)
+    if av.data_ptr() % 16:
+        av = av.clone()
+    BG, H, N, hd = av.shape
+    L = E.lib()
+    with torch.cuda.device(av.device):
+        nbytes = L.p2v_psaq_workspace_bytes(BG // groups, groups, H, N, hd)
+        if nbytes == 0:
+            E.check(L.p2v_patch_similarity_entropy(None, BG // groups, groups, H, N, hd, None, None, None, None))   # raises with the validation message
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=av.device)
+        value = torch.empty((), dtype=torch.float64, device=av.device)
+        grad = torch.empty_like(av)
+        E.check(L.p2v_patch_similarity_entropy(E.ptr(av), BG // groups, groups, H, N, hd, E.ptr(ws), E.ptr(value), E.ptr(grad),
+                                               E.stream_ptr(av.device)))
+    return value, grad
+
+
 _LIB.impl('fake_quant', _fake_quant, 'CUDA')
 _LIB.impl('quantize_patchify', _quantize_patchify, 'CUDA')
 _LIB.impl('linear_requant', lambda x, w, cs, b, inv: _linear(E.EPI_REQUANT, x, w, cs, b, inv), 'CUDA')
@@ -455,6 +480,8 @@ _LIB.impl('score_accumulate', _score_accumulate, 'CUDA')
 _LIB.impl('code_stats', lambda tensors: _code_stats(tensors), 'CUDA')
 _LIB.impl('code_grams', _code_grams, 'CUDA')
 _LIB.impl('cka_centre', _cka_centre, 'CUDA')
+_LIB.impl('patch_similarity_entropy', _patch_similarity_entropy, 'CUDA')
 
 OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'lis_attention_rows', 'forward', 'cka_grams',
-       'hsic_accumulate', 'pair_cosine', 'score_logits', 'score_accumulate', 'code_stats', 'code_grams', 'cka_centre')
+       'hsic_accumulate', 'pair_cosine', 'score_logits', 'score_accumulate', 'code_stats', 'code_grams', 'cka_centre',
+       'patch_similarity_entropy')

@@ -87,6 +87,7 @@ class WindowAttention(nn.Module):
         self.proj = _qlinear(cfg, dim, dim, quant, calibrate)
         nn.init.trunc_normal_(self.relative_position_bias_table, std=.02)
         self.global_distance = []        # (SwinTransformer shares ONE list with every module that owns a QLinear)
+        self.av_hook = None              # callable(attn @ v [B * windows, heads, N, head_dim]), still attached to the graph (psaq.generate_data)
 
     def forward(self, x, mask=None):
         B_, N, C = x.shape
@@ -101,7 +102,10 @@ class WindowAttention(nn.Module):
             nW = mask.shape[0]
             attn = (attn.view(B_ // nW, nW, self.num_heads, N, N) + mask.unsqueeze(1).unsqueeze(0)).view(-1, self.num_heads, N, N)
         attn = self.log_int_softmax(attn, self.qact2.quantizer.scale)
-        x = (attn @ v).transpose(1, 2).reshape(B_, N, C)
+        x = attn @ v
+        if self.av_hook is not None:
+            self.av_hook(x)
+        x = x.transpose(1, 2).reshape(B_, N, C)
         return self.qact4(self.proj(self.qact3(x), self.global_distance))
 
 

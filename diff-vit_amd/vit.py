@@ -122,6 +122,7 @@ class Attention(nn.Module, _SmoothQuantMixin):
                                            observer_str=cfg.OBSERVER_S, quantizer_str=cfg.QUANTIZER_S)
         self.channel_scale = None
         self.qkv_output = None
+        self.av_hook = None      # callable(attn @ v [B, heads, N, head_dim]), still attached to the graph (psaq.generate_data); a plain attribute
 
     def forward(self, x, FLOPs, global_distance, atten_bit_config, plot=False, quant=False, smoothquant=True,
                 hessian_statistic=False):
@@ -143,7 +144,10 @@ class Attention(nn.Module, _SmoothQuantMixin):
         attn = self.qact_attn1(attn)
         attn = self.log_int_softmax(attn, self.qact_attn1.quantizer.scale)
         attn = self.attn_drop(attn)
-        x = (attn @ v).transpose(1, 2).reshape(B, N, C)
+        x = attn @ v
+        if self.av_hook is not None:
+            self.av_hook(x)
+        x = x.transpose(1, 2).reshape(B, N, C)
         x = self.qact2(x)
         bit_config = atten_bit_config[1] if atten_bit_config else None
         x = self.proj(x, global_distance, bit_config)

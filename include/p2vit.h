@@ -1080,6 +1080,22 @@ int p2v_forward_grams(p2v_plan* plan, const float* images, int batch, const int8
                       size_t ws_bytes, int with_linear, int stage_set, float* tap_scratch, size_t tap_scratch_bytes, double* grams,
                       size_t grams_bytes, double* units, size_t units_bytes, void* stream);
 
+/* ---- Patch-similarity entropy of PSAQ-ViT's data generator and its gradient (generate_data.py:102-113, 128-134; utils/kde.py:87-96) ----
+ * av: dev fp32, contiguous [images * groups][heads][tokens][head_dim] - one block's attn @ v before the transpose; groups = windows per image
+ * (1 for ViT / DeiT).  Per group: a = mean over heads, row 0 dropped (T = tokens - 1 rows), S = cosine similarity of every pair of rows
+ * (each row divided by max(|row|, 1e-8), diagonal computed).  lo / hi = min / max of S over the WHOLE call (constants of the
+ * differentiation), x_k = linspace(lo, hi, 10).  Per image over its n = groups * T^2 similarities: p_k = (c / n) sum_m exp(-(x_k - s_m)^2 /
+ * (2 h^2)), h = 0.01, c = 1 / sqrt(2 pi h^2); q = p + 1e-4; E_b = trapezoid rule of -q ln q over x.  value_out (dev fp64 [1]) = mean_b E_b;
+ * grad_out (dev fp32, the shape of av) = d value / d av, row 0 of every group exactly zero, every head the same slice.  lo == hi gives 0
+ * and zeros.  The point sums and the trapezoid are fp64, the products run on the exact-fp32 MFMA, nothing is accumulated with atomics and
+ * nothing synchronises: six launches on `stream`, the same bytes on every run.  The workspace (p2v_psaq_workspace_bytes, 256-byte aligned)
+ * holds S - images * groups * T * T floats - plus the normalised rows and the partials.
+ * P2V_E_SHAPE before any launch: images / groups / heads < 1, T outside 2 ... 1024, head_dim no multiple of 4 in 4 ... 128 (the query
+ * returns 0 for these); P2V_E_ARG: a null pointer, av / grad_out not 16-byte, value_out not 8-byte, workspace not 256-byte aligned. */
+size_t p2v_psaq_workspace_bytes(int images, int groups, int heads, int tokens, int head_dim);
+int p2v_patch_similarity_entropy(const float* av, int images, int groups, int heads, int tokens, int head_dim, void* workspace,
+                                 double* value_out, float* grad_out, void* stream);
+
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
 
