@@ -311,7 +311,7 @@ def main(argv=None):
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--device', default='cuda')
     p.add_argument('--result-name', default='cka_result')
-    p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT; a Swin model needs ptf)')
+    p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT and Swin)')
     p.add_argument('--no-lis', action='store_true', help='Config(lis=False): float softmax (ViT / DeiT and Swin)')
     p.add_argument('--softmax-bits', default=None, type=int, choices=[3, 4], help='width of the log-int-softmax (Config.BIT_TYPE_S: uint3 / uint4; default 4)')
     p.add_argument('--stages', default='linear', choices=['linear', 'engine', 'full'],

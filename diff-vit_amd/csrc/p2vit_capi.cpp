@@ -1353,13 +1353,19 @@ int p2v_float_layernorm(const int8_t* x, long long row_stride, int rows, int C, 
   if (!x || !ln || !out) return fail(P2V_E_ARG, "p2v_float_layernorm: null argument");
   if (C % 4 || row_stride % 4 || out_stride % 4) return fail(P2V_E_UNSUPPORTED, "C and strides must be multiples of 4");
   if (rows <= 0) return fail(P2V_E_SHAPE, "rows must be positive");
-  if (C < 16 || C > 2048) return fail(P2V_E_SHAPE, "p2v_float_layernorm: C=%d, the kernel covers 16 .. 2048 channels", C);
+  if (C < 16 || C > P2V_FLOAT_LN_MAX_C) return fail(P2V_E_SHAPE, "p2v_float_layernorm: C=%d, the kernels cover 16 .. %d channels", C, P2V_FLOAT_LN_MAX_C);
   if (row_stride < 0 || out_stride < C) return fail(P2V_E_SHAPE, "p2v_float_layernorm: row_stride non-negative, out_stride >= C");
+  // as p2v_int_layernorm: rows beyond 2048 channels (the row-per-workgroup kernel) are taken only as whole rows.  Up to 2048 channels the
+  // entry point keeps what it accepted before.
+  if (C > 2048 && row_stride < C)
+    return fail(P2V_E_SHAPE, "p2v_float_layernorm: C=%d beyond 2048 channels needs row_stride >= C (got %lld)", C, row_stride);
   if ((uintptr_t)x % 4 || (uintptr_t)out % 4 || (uintptr_t)tap_out % 16) return fail(P2V_E_ARG, "p2v_float_layernorm: x / out 4-byte, tap_out 16-byte aligned");
   if (const int rc = check_float_ln("p2v_float_layernorm", *ln)) return rc;
   const FloatLnArgs a{x, row_stride, rows, C, (double)ln->s_in, (double)ln->eps, ln->gamma, ln->beta, ln->g, out, out_stride, tap_out};
   return launch_rc(p2v_launch_float_layernorm(a, (hipStream_t)stream), "float_layernorm");
 }
+
+int p2v_float_layernorm_max_channels(void) { return P2V_FLOAT_LN_MAX_C; }
 
 int p2v_softmax_attention_taps(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_softmax_attn* at, int8_t* out,
                                int8_t* score_codes, int pitch, void* stream) {
@@ -1605,6 +1611,11 @@ static int run_one_op(const p2v_op& o, void* stream) {
                                           (int8_t*)o.out, stream);
     case P2V_OP_STATS:
       return stats_op(o, stream);
+    case P2V_OP_FLOAT_LAYERNORM: {
+      // P2V_OP_LAYERNORM's shape members; the constants in members no LayerNorm record read before (op table of include/p2vit.h)
+      const p2v_float_ln f{o.f0, o.f1, reinterpret_cast<const float*>(o.lin.w_codes), o.lin.colscale, o.lin.bias};
+      return p2v_float_layernorm((const int8_t*)o.in, o.lda, o.M, o.N, &f, (int8_t*)o.out, o.ldo, o.ep.tap_out, stream);
+    }
     default:
       return fail(P2V_E_ARG, "p2v_run_ops: unknown op kind %d", o.kind);
   }

@@ -71,8 +71,10 @@ __global__ __launch_bounds__(256) void k_float_layernorm(FloatLnArgs a) {
   }
 }
 
+// rows of up to 2048 channels: the kernel above; 2052 ... 4096: a row per workgroup (k_float_layernorm_xwide, p2vit_float_ln_xwide.hip)
 int p2v_launch_float_layernorm(const FloatLnArgs& a, hipStream_t st) {
-  if (a.C < 4 || a.C > FLN_MAX_C || a.C % 4 || a.rows <= 0) return -1;
+  if (a.C > FLN_MAX_C) return p2v_launch_float_layernorm_xwide(a, st);
+  if (a.C < 4 || a.C % 4 || a.rows <= 0) return -1;
   hipLaunchKernelGGL(k_float_layernorm, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, st, a);
   CHECK_LAUNCH();
   return 0;

@@ -261,7 +261,8 @@ struct SmAttnArgs {
   int pitch;
   int nq;               // query rows to compute in whole 16-row blocks (0 = all)
 };
-int p2v_launch_float_layernorm(const FloatLnArgs& a, hipStream_t st);
+int p2v_launch_float_layernorm(const FloatLnArgs& a, hipStream_t st);          // picks the kernel by C; -1: C outside 4 .. 4096
+int p2v_launch_float_layernorm_xwide(const FloatLnArgs& a, hipStream_t st);    // 2052 .. 4096 channels, a row per workgroup
 // head_dim 32 / 64, 1 .. P2V_MAX_TOKENS tokens; -1: no instantiation
 int p2v_launch_softmax_attention(const SmAttnArgs& a, int head_dim, hipStream_t st);
 // Swin window attention with the table softmax (p2vit_winattn_softmax.hip): Config(lis=False) of a Swin plan

@@ -83,6 +83,8 @@ class Block(C.Structure):
 OP_PATCHIFY, OP_GEMM, OP_LAYERNORM, OP_WINATTN, OP_MERGE, OP_AVGPOOL, OP_LN_GEMM = range(7)
 OP_COS, OP_COS_COMBINE, OP_GEMM_F32 = 7, 8, 9      # one DDV stage / the closing combine / a dense fp32 layer output (op table of include/p2vit.h)
 OP_WINATTN_SOFTMAX = 10                           # window attention with the table softmax (Config(lis=False)): lin.w_codes names the table
+OP_FLOAT_LAYERNORM = 12                           # p2v_float_layernorm as a record (Config(ptf=False) of a Swin plan): f0 s_in, f1 eps, lin.w_codes
+                                                  # gamma, lin.colscale beta, lin.bias g, ep.tap_out the optional fp32 tap
 
 
 class Op(C.Structure):
@@ -254,6 +256,8 @@ def lib():
         L.p2v_plan_set_float_ops.argtypes = [_p, _i, _i]
         L.p2v_plan_set_float_block.argtypes = [_p, _i, C.POINTER(FloatBlock)]
         L.p2v_plan_set_float_head.argtypes = [_p, C.POINTER(FloatLn)]
+    if hasattr(L, 'p2v_float_layernorm_max_channels'):  # rows of up to 4096 channels and the P2V_OP_FLOAT_LAYERNORM record (Swin Config(ptf=False)), additive
+        L.p2v_float_layernorm_max_channels.argtypes = []
     if hasattr(L, 'p2v_window_softmax_attention'):      # Swin Config(lis=False), additive
         L.p2v_window_softmax_attention.argtypes = [_p, _i, _i, _i, _i, C.POINTER(WinAttn), _p, _p, _p]
     if hasattr(L, 'p2v_plan_set_softmax_bits'):   # the width of the log-int-softmax (Config.BIT_TYPE_S: uint3 / uint4), additive

@@ -31,7 +31,7 @@ def build_parser():
     p.add_argument('--quant', default=False, action='store_true')
     p.add_argument('--ptf', default=True)
     p.add_argument('--lis', default=True)
-    p.add_argument('--no-ptf', dest='ptf', action='store_false', help='Config(ptf=False): layer-wise QActs around a float LayerNorm (ViT / DeiT; a Swin model needs ptf)')
+    p.add_argument('--no-ptf', dest='ptf', action='store_false', help='Config(ptf=False): layer-wise QActs around a float LayerNorm (ViT / DeiT and Swin)')
     p.add_argument('--no-lis', dest='lis', action='store_false',
                    help='Config(lis=False): float softmax instead of the log-int-softmax (ViT / DeiT and Swin)')
     p.add_argument('--softmax-bits', default=None, type=int, choices=[3, 4], help='width of the log-int-softmax (Config.BIT_TYPE_S: uint3 / uint4; default 4)')

@@ -329,7 +329,7 @@ def main(argv=None):
     p.add_argument('--stages', default='engine', choices=['engine', 'full'])
     p.add_argument('--attention', action='store_true', help='also the QActs inside the attention kernels')
     p.add_argument('--with-linear', action='store_true', help='also the fp32 outputs of the linear layers')
-    p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT)')
+    p.add_argument('--no-ptf', action='store_true', help='Config(ptf=False): float LayerNorm (ViT / DeiT and Swin)')
     p.add_argument('--no-lis', action='store_true', help='Config(lis=False): float softmax (not with --attention)')
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--device', default='cuda')

@@ -341,18 +341,32 @@ class SwinTransformer(nn.Module):
     def freeze(self, device=None, bits=8, pack4=True):
         """the plan is a snapshot: it holds the width of every window attention's ``log_int_softmax.bit_type`` (uint3 / uint4) as read
         here - changing a module's bit type afterwards needs a new ``freeze`` (``model_open_calibrate`` drops the plan).  A
-        log-int-softmax of another width and a QAct that is not int8 are refused (``NotImplementedError`` naming the module)."""
+        log-int-softmax of another width and a QAct that is not int8 are refused (``NotImplementedError`` naming the module).
+        All four ``Config(ptf, lis)`` combinations freeze: ``lis=False`` records the table-softmax window attention, ``ptf=False`` the float
+        LayerNorm at every norm (``SwinPlan(int_softmax=..., int_norm=...)``); under ``ptf=False`` a QAct without its one calibrated layer-wise
+        scale is refused by name, before a device is asked for."""
         from .swin_plan import SwinPlan
         from .plan import module_softmax_bits
         if not self.input_quant:
             raise NotImplementedError('the HIP engine fuses qact_input into the patch gather: input_quant=True models only')
-        if not self.cfg.INT_NORM:
-            raise NotImplementedError('the HIP engine runs a Swin model with ptf=True only (lis=True or False): Config(ptf=False) needs a '
-                                      'float LayerNorm the Swin engine does not have')
+        int_norm = bool(self.cfg.INT_NORM)
+        norms = [(n, m) for n, m in self.named_modules() if type(m) is QIntLayerNorm]
+        if not int_norm:
+            # Config(ptf=False): model_quant() leaves every norm in mode 'ln' and the engine runs its float LayerNorm with the modules' one eps
+            bad = [n for n, m in norms if m.mode != 'ln' or m.eps != norms[0][1].eps]
+            if bad:
+                raise NotImplementedError('%s: under Config(ptf=False) every QIntLayerNorm stays in mode \'ln\' with one eps' % bad[0])
+            # the float LayerNorm reads ONE calibrated scale per QAct (layer-wise minmax): a model that was not calibrated under this
+            # configuration has none, a PTF vector has several - said here, by name, before a device is asked for
+            for n, m in self.named_modules():
+                if type(m) is QAct and (m.quantizer.scale is None or m.quantizer.scale.numel() != 1):
+                    raise NotImplementedError('%s: Config(ptf=False) needs the one calibrated layer-wise scale of every QAct, got %s '
+                                              '(calibrate the model under this configuration first)'
+                                              % (n, 'none' if m.quantizer.scale is None else '%d values' % m.quantizer.scale.numel()))
         widths = module_softmax_bits(self, bool(self.cfg.INT_SOFTMAX))
         dev = device or self.head.weight.device
         self._plan = SwinPlan(self.arch, dict(self.state_dict()), self.export_calib(), device=dev, in_chans=self.in_chans, bits=bits, pack4=pack4,
-                              int_softmax=bool(self.cfg.INT_SOFTMAX), softmax_bits=widths)
+                              int_softmax=bool(self.cfg.INT_SOFTMAX), softmax_bits=widths, int_norm=int_norm, ln_eps=float(norms[0][1].eps))
         return self._plan
 
     # ---- per-layer widths -----------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """Frozen integer plan of a calibrated Swin model: int8 weight codes and per-channel requant constants on the GPU, and a forward
 that is a fixed sequence of HIP kernels called through the C ABI (``p2v_quantize_patchify``, ``p2v_gemm_i8``,
-``p2v_int_layernorm``, ``p2v_window_attention`` - under Config(lis=False) ``p2v_window_softmax_attention`` -, ``p2v_patch_merge_gather``,
-``p2v_avgpool_quant``).  Window partition, cyclic
+``p2v_int_layernorm`` - under Config(ptf=False) ``p2v_float_layernorm`` -, ``p2v_window_attention`` - under Config(lis=False)
+``p2v_window_softmax_attention`` -, ``p2v_patch_merge_gather``, ``p2v_avgpool_quant``).  Window partition, cyclic
 shift and their inverses are index tables consumed by the attention kernel; nothing runs on the CPU and nothing falls back.
 
 Call order = swin_quant.py (forward_features :790-811, SwinTransformerBlock.forward :351-399, PatchMerging.forward :438-461).
@@ -44,13 +44,22 @@ class SwinPlan:
     ``softmax_bits``: the width of every window attention's log-int-softmax (p = 2^-k for k < 2^bits, else 0): None = the widths the
     calibration state names (``<path>.log_int_softmax.bits``, else 4), an int, or one entry per attention module in model order (a named
     width that disagrees is refused); kept as ``plan.softmax_bits`` and written into every ``P2V_OP_WINATTN``
-    record.  Unused (as in the reference) under ``int_softmax=False``."""
+    record.  Unused (as in the reference) under ``int_softmax=False``.
+    ``int_norm=False`` (Config(ptf=False)): every QAct is layer-wise, and every LayerNorm stays ``F.layer_norm`` followed by the next QAct.
+    Every LayerNorm record of every sequence - ``patch_embed.norm``, each block's ``norm1`` / ``norm2``, each ``downsample.norm`` behind the
+    merge gather, the final ``norm`` - is ``P2V_OP_FLOAT_LAYERNORM`` (``p2v_float_layernorm``: s_in the producing QAct's one scale,
+    g = 1 / s_out repeated over the channels, ``ln_eps`` the modules' eps); no fused ``P2V_OP_LN_GEMM`` record runs behind it and no
+    ``p2v_ln_prefold`` buffer is built.  The one scale of ``qact2`` / ``qact4`` / ``downsample.qact2`` is repeated over the channels
+    wherever the plan keeps per-channel vectors, so every other record is the integer arithmetic of the ptf=True plan.  A scale that is
+    no power of two stays refused (``NotImplementedError`` naming the module), as is a library without the record kind."""
 
-    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, bits=8, pack4=True, int_softmax=True, softmax_bits=None):
+    def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, bits=8, pack4=True, int_softmax=True, softmax_bits=None,
+                 int_norm=True, ln_eps=1e-5):
         if bits not in (4, 8):
             raise KeyError('int%s' % (bits,))          # (the weight scale a width has none of: what the lookup below raised)
         self.arch, self.device, self.in_chans, self.bits, self.pack4 = dict(arch), torch.device(device), in_chans, bits, bool(pack4)
         self.int_softmax = bool(int_softmax)
+        self.int_norm, self.ln_eps = bool(int_norm), float(ln_eps)
         from .plan import calib_softmax_bits
         self.softmax_bits = calib_softmax_bits(calib, ['layers.%d.blocks.%d.attn' % (li, bi) for li, d in enumerate(self.arch['depths'])
                                                        for bi in range(d)], softmax_bits)
@@ -58,7 +67,8 @@ class SwinPlan:
             raise RuntimeError('SwinPlan needs a GPU device: the quantized forward has no CPU path')
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
-        E.lib()
+        if not self.int_norm and not hasattr(E.lib(), 'p2v_float_layernorm_max_channels'):
+            raise RuntimeError('libp2vit_hip.so lacks P2V_OP_FLOAT_LAYERNORM (Config(ptf=False) of a Swin model): rebuild')
         self._keep = []
         self.W = {k: v.detach().float().cpu() for k, v in state_dict.items() if v.dtype == torch.float32}
         self.c = calib
@@ -187,7 +197,9 @@ class SwinPlan:
 
     def _ln(self, prefix, s_in_vec, s_out, C_):
         """QIntLayerNorm 'int' constants: mask = round(in_scale / min), inv_out = 1 / out_scale; the following QAct has the LN's
-        own output scale, so post_mul = 1."""
+        own output scale, so post_mul = 1.  ``int_norm=False``: the ``p2v_float_ln`` of the float LayerNorm instead."""
+        if not self.int_norm:
+            return self._float_ln(prefix, s_in_vec, s_out, C_)
         s_in_vec = torch.as_tensor(s_in_vec, dtype=torch.float32).reshape(-1)
         if s_in_vec.numel() == 1:
             s_in_vec = s_in_vec.expand(C_)
@@ -206,6 +218,25 @@ class SwinPlan:
         self._keep.append(buf)
         E.check(L.p2v_ln_prefold(C.byref(ln), C_, E.ptr(buf), nbytes))
         return ln
+
+    def _float_ln(self, prefix, s_in_vec, s_out, C_):
+        """QIntLayerNorm in mode 'ln' and the QAct behind it (Config(ptf=False)): one input scale, g = 1 / s_out over the channels"""
+        s_in_vec = torch.as_tensor(s_in_vec, dtype=torch.float32).reshape(-1)
+        s_in = float(s_in_vec[0])
+        if not bool((s_in_vec == s_in).all()):
+            raise NotImplementedError('%s: the float LayerNorm of Config(ptf=False) needs ONE input scale, got %r' % (prefix, s_in_vec[:4]))
+        if C_ % 4 or not 16 <= C_ <= E.lib().p2v_float_layernorm_max_channels():
+            raise NotImplementedError('%s: %d channels, the float LayerNorm covers multiples of 4 in 16 .. %d'
+                                      % (prefix, C_, E.lib().p2v_float_layernorm_max_channels()))
+        t = [self._dev(self.W[prefix + '.weight']), self._dev(self.W[prefix + '.bias']), self._dev(torch.full((C_,), 1.0 / float(s_out)))]
+        return E.FloatLn(s_in, self.ln_eps, *[E.ptr(x) for x in t])
+
+    def _chan(self, name, n):
+        """the scale of a QAct that is a PTF vector under ptf=True, as n per-channel values: the calibrated vector, or (``int_norm=False``:
+        every QAct is layer-wise) its one power-of-two scale repeated"""
+        if self.int_norm:
+            return self.c[name].reshape(-1)
+        return torch.full((n,), self._pot(name))
 
     # ---- plan ----------------------------------------------------------------------------------------------------------
     def _build(self):
@@ -237,7 +268,7 @@ class SwinPlan:
                 b = dict(C=Cc, heads=heads, H=H, ws=wsz, shift=shift, softmax_bits=self.softmax_bits[sum(a['depths'][:li]) + bi])
                 b['ln1'] = self._ln(p + 'norm1', s_res, s1, Cc)
                 s_q1 = self._pot(p + 'attn.qact1')
-                b['qkv'] = self._linear(p + 'attn.qkv', s1, frag=Cc <= 384)
+                b['qkv'] = self._linear(p + 'attn.qkv', s1, frag=self.int_norm and Cc <= 384)
                 b['inv_s_qkv'] = 1.0 / s_q1
                 s_q2 = self._pot(p + 'attn.qact2')
                 s_q3 = self._pot(p + 'attn.qact3')
@@ -259,15 +290,15 @@ class SwinPlan:
                     from .plan import softmax_table
                     b['sm_tab'] = self._dev(torch.from_numpy(softmax_table(s_q2).astype(np.int32)), torch.int32)
                 b['proj'] = self._linear(p + 'attn.proj', s_q3)
-                s_b2 = c[p + 'qact2'].reshape(-1)
+                s_b2 = self._chan(p + 'qact2', Cc)
                 b['proj_epi'] = self._resid_epi(self._pot(p + 'attn.qact4'), s_res, s_b2, Cc, b['proj'])
                 s3 = self._pot(p + 'qact3')
                 b['ln2'] = self._ln(p + 'norm2', s_b2, s3, Cc)
-                b['fc1'] = self._linear(p + 'mlp.fc1', s3, frag=Cc <= 384)
+                b['fc1'] = self._linear(p + 'mlp.fc1', s3, frag=self.int_norm and Cc <= 384)
                 s_m1 = self._pot(p + 'mlp.qact1')
                 b['inv_s_fc1'] = 1.0 / s_m1
                 b['fc2'] = self._linear(p + 'mlp.fc2', s_m1)
-                s_b4 = c[p + 'qact4'].reshape(-1)
+                s_b4 = self._chan(p + 'qact4', Cc)
                 b['fc2_epi'] = self._resid_epi(self._pot(p + 'mlp.qact2'), s_b2, s_b4, Cc, b['fc2'])
                 s_res = s_b4.clone()
                 blocks.append(b)
@@ -275,7 +306,7 @@ class SwinPlan:
             if li < len(a['depths']) - 1:
                 p = 'layers.%d.downsample.' % li
                 sd1 = self._pot(p + 'qact1')
-                sd2 = c[p + 'qact2'].reshape(-1)
+                sd2 = self._chan(p + 'qact2', 2 * Cc)
                 red = self._linear(p + 'reduction', sd1, bias=False)
                 # single PTF requant through the RESID epilogue: s_mid = s_next and an all-zero residual make it
                 # Q(Q(y; s) * s; s) = Q(y; s)   (|code * eps| << 0.5)
@@ -306,7 +337,8 @@ class SwinPlan:
         """the launch sequence of one forward at batch B as a ``p2v_op`` array with its own activation buffers (built once
         per batch size and stream slot, replayed by ``p2v_run_ops``).  ``fused``: norm1 + qkv and norm2 + fc1 of stages up to 384
         channels run as ONE launch each (``P2V_OP_LN_GEMM``: the LayerNorm output stays in LDS); the tap replay records the
-        unfused sequence, whose LayerNorm outputs exist in HBM.
+        unfused sequence, whose LayerNorm outputs exist in HBM.  Under ``int_norm=False`` nothing is fused behind the float LayerNorm: both
+        sequences hold the same LayerNorm and GEMM records.
         ``ddv_n`` > 0 (B = 2 * ddv_n, unfused): behind the launch that completes a DDV stage a ``P2V_OP_COS`` record reduces samples
         [0, n) of the live buffer against samples [n, 2n); proj / fc2 also store their mid codes (attn.qact4 / mlp.qact2); ``with_linear``
         adds the fp32 layer outputs through ONE scratch buffer; a ``P2V_OP_COS_COMBINE`` closes the sequence.
@@ -430,7 +462,12 @@ class SwinPlan:
         def lnorm(x, ln, Cc, out):
             o = E.Op()
             o.kind, o.inp, o.out = E.OP_LAYERNORM, E.ptr(x), E.ptr(out)
-            o.M, o.N, o.lda, o.ldo, o.ln = x.shape[0], Cc, x.shape[1], out.shape[1], ln
+            o.M, o.N, o.lda, o.ldo = x.shape[0], Cc, x.shape[1], out.shape[1]
+            if isinstance(ln, E.FloatLn):       # Config(ptf=False): the constants in the members of the op table (include/p2vit.h)
+                o.kind, o.f0, o.f1 = E.OP_FLOAT_LAYERNORM, ln.s_in, ln.eps
+                o.lin.w_codes, o.lin.colscale, o.lin.bias = ln.gamma, ln.beta, ln.g
+            else:
+                o.ln = ln
             ops.append(o)
             return out
 
@@ -481,7 +518,7 @@ class SwinPlan:
                 t_qkv, t_fc1 = ftap(p + 'attn.qkv', rows, b['qkv']['N']), None
                 e_fc1 = epi_req(b['inv_s_fc1'])
                 e_fc1.gelu = E.gelu_table(b['inv_s_fc1'], self.device)       # exact GELU -> qact1 threshold table (cached per scale)
-                fuse = (fused and b['qkv']['frag'] and hid_k == fc1_n and E.lib().p2v_ln_gemm_fusable(E.EPI_REQUANT, Cc, b['qkv']['N'], 0) == 1
+                fuse = (fused and self.int_norm and b['qkv']['frag'] and hid_k == fc1_n and E.lib().p2v_ln_gemm_fusable(E.EPI_REQUANT, Cc, b['qkv']['N'], 0) == 1
                         and E.lib().p2v_ln_gemm_fusable(E.EPI_GELU, Cc, b['fc1']['N'], e_fc1.gelu.cells if e_fc1.gelu.table else 0) == 1)
                 if fuse:
                     ln_gemm(E.EPI_REQUANT, x, b['ln1'], Cc, b['qkv'], epi_req(b['inv_s_qkv']), qkv)
@@ -856,5 +893,6 @@ class SwinPlan:
         _, ms = self._replay(images, 0, profile=True)
         r = self._recorded[(images.shape[0], 0, True)]
         names = {E.OP_PATCHIFY: 'patchify', E.OP_GEMM: 'gemm', E.OP_LAYERNORM: 'layernorm', E.OP_WINATTN: 'window_attention',
-                 E.OP_MERGE: 'merge_gather', E.OP_AVGPOOL: 'avgpool', E.OP_LN_GEMM: 'ln_gemm', E.OP_WINATTN_SOFTMAX: 'window_softmax_attention'}
+                 E.OP_MERGE: 'merge_gather', E.OP_AVGPOOL: 'avgpool', E.OP_LN_GEMM: 'ln_gemm', E.OP_WINATTN_SOFTMAX: 'window_softmax_attention',
+                 E.OP_FLOAT_LAYERNORM: 'float_layernorm'}
         return [(names[r['ops'][i].kind], int(r['ops'][i].epi), ms[i]) for i in range(r['n'])]

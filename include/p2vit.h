@@ -67,10 +67,14 @@
  *     scales of this path; for any other scale pass p2v_ln.out_scale too and the kernel divides (exact, ABI 3);
  *   - REQUANT epilogues fold 1/scale into the column constants: it must be a power of two;
  *   - log-int-softmax constants: c_int < 2^24 (qact_attn1 scale >= 2^-11);
- *   - Config(ptf=False) / Config(lis=False) of a ViT / DeiT plan (p2v_plan_set_float_ops, at the end of this header): the float LayerNorm for
- *     16 .. 2048 channels under one power-of-two input scale; the table-softmax attention for head_dim 32 / 64 and up to P2V_MAX_TOKENS
- *     tokens.  Swin plans run ptf = True; lis = False through p2v_window_softmax_attention (head_dim 32, windows up to 12 x 12, qact2
- *     scale <= 2^-2); Config(ptf=False) of a Swin model has no float LayerNorm on the engine and stays refused.
+ *   - Config(ptf=False) / Config(lis=False) of a ViT / DeiT plan (p2v_plan_set_float_ops, at the end of this header): the table-softmax
+ *     attention for head_dim 32 / 64 and up to P2V_MAX_TOKENS tokens; a p2v_plan (ViT) keeps embed_dim <= 2048;
+ *   - float LayerNorm (p2v_float_layernorm, P2V_OP_FLOAT_LAYERNORM): 16 .. P2V_FLOAT_LN_MAX_C = 4096 channels, a multiple of 4, under one
+ *     power-of-two input scale: up to 2048 a row per wave, 2052 .. 4096 a row per workgroup (csrc/p2vit_float_ln_xwide.hip - the 4 * 768 =
+ *     3072-channel PatchMerging norm of Swin-L), whole rows only there (row_stride >= C);
+ *   - Swin plans (recorded p2v_op sequences): lis = False through p2v_window_softmax_attention (head_dim 32, windows up to 12 x 12, qact2
+ *     scale <= 2^-2); ptf = False through P2V_OP_FLOAT_LAYERNORM records at every LayerNorm, every other record unchanged (each PTF
+ *     vector repeats one scale).
  */
 #ifndef P2VIT_H
 #define P2VIT_H
@@ -591,9 +595,14 @@ int p2v_avgpool_quant(const int8_t* x, int batch, int tokens, int C, float s_in,
  *   P2V_OP_STATS      one stage of the stage statistics (p2v_code_stats below): every sample of the live buffer `in` is reduced into the
  *                     record `out` (initialised by p2v_stats_init, accumulated into).  i0 samples, i1 kind (P2V_STAT_*), M rows, N cols,
  *                     lda row stride, i2 | i3 << 32 sample stride (elements; p2v_stat_layer's rules).  One launch
- *   P2V_OP_WINATTN    i4 the softmax width (3 or 4); 0, the value of every earlier record, means 4 */
+ *   P2V_OP_WINATTN    i4 the softmax width (3 or 4); 0, the value of every earlier record, means 4
+ *   P2V_OP_FLOAT_LAYERNORM  p2v_float_layernorm (at the end of this header; a library that has the kind exports
+ *                     p2v_float_layernorm_max_channels): in, out; M rows, N channels, lda / ldo row strides - the members of
+ *                     P2V_OP_LAYERNORM - and the constants in members no LayerNorm record reads: f0 s_in, f1 eps, lin.w_codes gamma
+ *                     (written as const float*), lin.colscale beta, lin.bias g (dev fp32 [N] each, 16-byte aligned), ep.tap_out the
+ *                     optional fp32 tap [M][N] (NULL: none).  `ln` is not read */
 enum { P2V_OP_PATCHIFY = 0, P2V_OP_GEMM = 1, P2V_OP_LAYERNORM = 2, P2V_OP_WINATTN = 3, P2V_OP_MERGE = 4, P2V_OP_AVGPOOL = 5, P2V_OP_LN_GEMM = 6,
-       P2V_OP_COS = 7, P2V_OP_COS_COMBINE = 8, P2V_OP_GEMM_F32 = 9, P2V_OP_WINATTN_SOFTMAX = 10, P2V_OP_STATS = 11 };
+       P2V_OP_COS = 7, P2V_OP_COS_COMBINE = 8, P2V_OP_GEMM_F32 = 9, P2V_OP_WINATTN_SOFTMAX = 10, P2V_OP_STATS = 11, P2V_OP_FLOAT_LAYERNORM = 12 };
 typedef struct p2v_op {
   int32_t kind, epi;
   const void* in;
@@ -891,8 +900,13 @@ int p2v_freeze_weights(const float* w, long long ldw, int N, int K, const float*
  *     out_c = clamp(rne(y_c g_c), -128, 127)
  * gamma, beta, g: dev fp32 [C], 16-byte aligned; g_c = 1 / (channel_scale_c * s_out), a power of two (the caller's to guarantee: the kernel
  * multiplies).  tap_out (optional, NULL): dev fp32 dense [rows][C], 16-byte aligned, receives RN32(y_c) - what a hook on the module sees, up
- * to the distance between this expression and the platform's fp32 F.layer_norm.  C: a multiple of 4 in 16 .. 2048; row_stride / out_stride
- * as p2v_int_layernorm (multiples of 4, out_stride >= C); bytes [C, out_stride) of an output row are not written.
+ * to the distance between this expression and the platform's fp32 F.layer_norm.  C: a multiple of 4 in 16 .. P2V_FLOAT_LN_MAX_C (4096; it was
+ * 2048 before p2v_float_layernorm_max_channels existed); row_stride / out_stride as p2v_int_layernorm (multiples of 4, out_stride >= C,
+ * beyond 2048 channels row_stride >= C: whole rows); bytes [C, out_stride) of an output row are not written.  Everything else is refused
+ * before any launch: P2V_E_UNSUPPORTED for a C or stride that is no multiple of 4, P2V_E_SHAPE for C outside 16 .. 4096.
+ * With |q| <= 128 and C <= 4096: C S2 <= 2^38, S1^2 <= 2^38 and |C q - S1| < 2^32 - 64-bit integers, numerators exact in fp64.
+ * p2v_float_layernorm_max_channels (additive) returns P2V_FLOAT_LN_MAX_C; its presence also tells that p2v_run_ops knows
+ * P2V_OP_FLOAT_LAYERNORM.
  *
  * p2v_softmax_attention: p2v_lis_attention's layouts and score requantisation (the qact_attn1 codes c_ij), then
  *     d_ij = max_j c_ij - c_ij in [0, 255];  E_ij = table[d_ij];  num_ic = sum_j E_ij v_jc;  den_i = sum_j E_ij        (exact integers)
@@ -913,8 +927,10 @@ typedef struct p2v_softmax_attn {
   float s_qkv_sq, qk_scale, inv_s_attn, av_mul;   /* as p2v_attn */
   const uint32_t* table;                          /* dev [256] */
 } p2v_softmax_attn;
+#define P2V_FLOAT_LN_MAX_C 4096
 int p2v_float_layernorm(const int8_t* x, long long row_stride, int rows, int C, const p2v_float_ln* ln, int8_t* out, long long out_stride,
                         float* tap_out, void* stream);
+int p2v_float_layernorm_max_channels(void);
 int p2v_softmax_attention(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_softmax_attn* at, int8_t* out,
                           void* stream);
 int p2v_softmax_attention_taps(const int8_t* qkv, int batch, int tokens, int heads, int head_dim, const p2v_softmax_attn* at, int8_t* out,
@@ -948,8 +964,8 @@ int p2v_plan_set_float_head(p2v_plan* plan, const p2v_float_ln* final_ln);
  * table[0] > 0; the plan builds min(rne(exp(-s_q2 d) 2^21), 2^21 - 1) in fp64 on the host).  wa->x0_int / b_int / c_int are ignored.
  * P2V_E_UNSUPPORTED: head_dim other than 32, s_q2 > 2^-2, s_q1 / s_q3 outside [2^-40, 2^15] or a scale that is no power of two;
  * P2V_E_SHAPE: ws outside 1 .. 12, windows beyond the token count, bad strides; P2V_E_ARG: a null pointer, qkv not 16-byte or out / table /
- * win_index not 4-byte aligned.  All before any launch.  Config(ptf=False) of a Swin model (a float LayerNorm of up to 3072 channels) is
- * not on the engine. */
+ * win_index not 4-byte aligned.  All before any launch.  Config(ptf=False) of a Swin model records P2V_OP_FLOAT_LAYERNORM at every
+ * LayerNorm (up to 3072 channels: the PatchMerging norm of Swin-L); it composes with either window attention. */
 int p2v_window_softmax_attention(const int8_t* qkv, int batch, int tokens_per_image, int heads, int head_dim, const p2v_winattn* wa,
                                  const uint32_t* table, int8_t* out, void* stream);
 
