@@ -27,6 +27,22 @@ static int fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
+// Graph capture (DESIGN "Graph capture of the forwards"): an entry point that copies from host memory of its own, synchronises, times with
+// events or allocates cannot be recorded into a HIP graph - a capture records work, it does not run it.  Such an entry point asks here after
+// its argument checks and before its first runtime call, enqueues nothing and leaves the capture valid.  A query that fails (no device, the
+// null stream beside a capturing one) or reports an invalidated capture is NOT taken as capturing; the sticky error is cleared.
+static bool stream_capturing(void* stream) {
+  hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing((hipStream_t)stream, &status) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return status == hipStreamCaptureStatusActive;
+}
+static int refuse_capture(const char* who, const char* why, void* stream) {
+  if (!stream_capturing(stream)) return P2V_OK;
+  return fail(P2V_E_UNSUPPORTED, "%s: the stream is capturing a HIP graph and this call %s; make it outside the capture", who, why);
+}
 // a best-effort plan-time step (building tables a forward can do without) must not disturb p2v_last_error(): restored on the way out
 struct KeepLastError {
   char keep[sizeof g_err];
@@ -578,6 +594,7 @@ struct Prof {
                                 // interval it opens then measures the host, not the kernel); ev[i] is recorded before launch i, one more after the last
   std::vector<int> kind;        // P2V_K_* of launch i
   int used = 0;
+  hipStream_t st = nullptr;     // the stream of the pass: p2v_forward_profile_end asks it whether it is capturing by then
   bool make_pool(int n) {
     ev.resize(n);
     kind.reserve(n);
@@ -1038,8 +1055,10 @@ int p2v_forward_profile_begin(p2v_plan* p, const float* images, int batch, const
                               size_t workspace_bytes, void* stream, void** token) {
   if (!p || !token) return fail(P2V_E_ARG, "p2v_forward_profile_begin: null argument");
   *token = nullptr;
+  if (const int cap = refuse_capture("p2v_forward_profile_begin", "times every launch with events of its own", stream)) return cap;
   std::unique_ptr<Prof> prof(new Prof());
   if (!prof->make_pool(prof_pool_size(p))) return fail(P2V_E_LAUNCH, "hipEventCreate failed");
+  prof->st = (hipStream_t)stream;
   FwdOpts o;
   o.images = images; o.prof = prof.get();
   const int rc = forward_impl(p, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stream, o);
@@ -1050,6 +1069,8 @@ int p2v_forward_profile_begin(p2v_plan* p, const float* images, int batch, const
 int p2v_forward_profile_end(void* token, float* ms_out, int32_t* kind_out, int max_launches) {
   if (!token) return fail(P2V_E_ARG, "p2v_forward_profile_end: null argument");
   Prof* prof = reinterpret_cast<Prof*>(token);
+  // (the token stays the caller's: it is ended once the capture is over)
+  if (const int cap = refuse_capture("p2v_forward_profile_end", "waits for the last event of the pass; the token stays valid", prof->st)) return cap;
   int n = 0;
   if (ms_out && kind_out && max_launches > 0) n = prof_collect(*prof, ms_out, kind_out, max_launches);
   else hipEventSynchronize(prof->ev[prof->used - 1]);      // ms_out == NULL: just release the token (error paths of the caller)
@@ -1060,6 +1081,7 @@ int p2v_forward_profile_end(void* token, float* ms_out, int32_t* kind_out, int m
 int p2v_forward_profile(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
                         size_t workspace_bytes, void* stream, float* ms_out, int32_t* kind_out, int max_launches) {
   if (!p || !ms_out || !kind_out || max_launches <= 0) return fail(P2V_E_ARG, "p2v_forward_profile: null argument");
+  if (const int cap = refuse_capture("p2v_forward_profile", "times every launch with events and waits for the last one", stream)) return cap;
   void* token;
   const int rc = p2v_forward_profile_begin(p, images, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stream, &token);
   return rc == P2V_OK ? p2v_forward_profile_end(token, ms_out, kind_out, max_launches) : rc;
@@ -1214,6 +1236,7 @@ int p2v_resid_prefold(const p2v_linear* lin, const p2v_epilogue* epi, int N, flo
   if (N <= 0) return fail(P2V_E_SHAPE, "p2v_resid_prefold: N must be positive");
   if (!lin->colscale || !lin->bias || !epi->s_mid || !epi->s_res || !epi->s_next) return fail(P2V_E_ARG, "p2v_resid_prefold: needs colscale / bias / s_mid / s_res / s_next");
   if (tab_bytes < p2v_resid_prefold_bytes(N)) return fail(P2V_E_WORKSPACE, "p2v_resid_prefold: table %zu < %zu bytes", tab_bytes, p2v_resid_prefold_bytes(N));
+  if (const int cap = refuse_capture("p2v_resid_prefold", "allocates its flags and reads them back to the host", stream)) return cap;
   OwnerDevice dev(tab);
   if (!dev.ok()) return fail(P2V_E_ARG, "p2v_resid_prefold: tab is not a device pointer");
   return resid_prefold_impl(*lin, *epi, N, tab, usable, (hipStream_t)stream);
@@ -1632,6 +1655,7 @@ int p2v_run_ops(const p2v_op* ops, int n_ops, void* stream) {
 
 int p2v_run_ops_profile(const p2v_op* ops, int n_ops, void* stream, float* ms) {
   if (!ops || !ms || n_ops < 0) return fail(P2V_E_ARG, "p2v_run_ops_profile: null argument");
+  if (const int cap = refuse_capture("p2v_run_ops_profile", "times every record with events and synchronises the stream", stream)) return cap;
   hipStream_t st = (hipStream_t)stream;
   std::vector<hipEvent_t> ev(n_ops + 1);
   for (auto& e : ev) hipEventCreate(&e);
@@ -1704,6 +1728,7 @@ int p2v_gelu_table_build(float inv_s, const p2v_gelu_tab* t, void* scratch, size
   if (rc != P2V_OK) return rc;
   if (want.k != t->k || want.off != t->off || want.cells != t->cells) return fail(P2V_E_ARG, "p2v_gelu_table_build: descriptor does not come from p2v_gelu_table_plan");
   if (scratch_bytes < p2v_gelu_table_scratch_bytes(t->cells)) return fail(P2V_E_WORKSPACE, "gelu table scratch %zu < %zu bytes", scratch_bytes, p2v_gelu_table_scratch_bytes(t->cells));
+  if (const int cap = refuse_capture("p2v_gelu_table_build", "reads the build status back to the host", stream)) return cap;
   hipStream_t st = (hipStream_t)stream;
   const int lrc = launch_rc(p2v_launch_gelu_table_build(inv_s, *t, (unsigned*)scratch, st), "gelu_table_build");
   if (lrc != P2V_OK) return lrc;
@@ -1755,6 +1780,7 @@ int p2v_cka_grams(const p2v_cka_layer* layers, int n_layers, int n, float* grams
   const CkaLayout w = p2v_cka_layout(layers, n_layers, n, &descs);
   if (ws_bytes < w.total) return fail(P2V_E_WORKSPACE, "p2v_cka_grams: workspace %zu < %zu bytes", ws_bytes, w.total);
   if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_cka_grams: the workspace must be 256-byte aligned");
+  if (const int cap = refuse_capture("p2v_cka_grams", "uploads its layer descriptors from a host array that does not outlive it", stream)) return cap;
   return launch_rc(p2v_launch_cka_grams(descs, w, n, grams, ws, (hipStream_t)stream), "cka_grams");
 }
 
@@ -1805,6 +1831,7 @@ int p2v_pair_cosine(const p2v_cos_layer* layers, int n_layers, int n, double* su
   const CosLayout w = p2v_cos_layout(layers, n_layers, n, &descs);
   if (ws_bytes < w.total) return fail(P2V_E_WORKSPACE, "p2v_pair_cosine: workspace %zu < %zu bytes", ws_bytes, w.total);
   if ((uintptr_t)ws % 256) return fail(P2V_E_ARG, "p2v_pair_cosine: the workspace must be 256-byte aligned");
+  if (const int cap = refuse_capture("p2v_pair_cosine", "uploads its layer descriptors from a host array that does not outlive it", stream)) return cap;
   return launch_rc(p2v_launch_pair_cosine(descs, w, n, sums, ws, (hipStream_t)stream), "pair_cosine");
 }
 
@@ -2226,6 +2253,8 @@ int p2v_code_grams(const p2v_gram_layer* layers, int n_layers, int n, double* gr
     need = b > need ? b : need;
   }
   if (ws_bytes < need) return fail(P2V_E_WORKSPACE, "p2v_code_grams: workspace %zu < %zu bytes", ws_bytes, need);
+  // (only an fp32 layer uploads a descriptor; one rule for the entry point whatever its layers hold)
+  if (const int cap = refuse_capture("p2v_code_grams", "uploads the descriptor of an fp32 layer from host memory that does not outlive it", stream)) return cap;
   for (int l = 0; l < n_layers; ++l) {
     const int rc = launch_rc(gram_launch(layers[l], n, grams + (size_t)l * n * n, ws, (hipStream_t)stream), "code_grams");
     if (rc != P2V_OK) return rc;
@@ -2373,6 +2402,8 @@ int p2v_forward_grams(p2v_plan* plan, const float* images, int batch, const int8
     if (tap_scratch_bytes < p2v_ddv_tap_scratch_bytes(plan, n))
       return fail(P2V_E_WORKSPACE, "p2v_forward_grams: tap_scratch %zu < %zu bytes", tap_scratch_bytes, p2v_ddv_tap_scratch_bytes(plan, n));
   }
+  if (const int cap = refuse_capture("p2v_forward_grams", "uploads the stage units and fp32 descriptors from host memory that does not outlive it", stream))
+    return cap;
   GramsCtx gc{plan, grams, units, reinterpret_cast<char*>(ws) + fwd, part, nullptr, {}};
   gc.host_units.reserve(K);
   DdvCtx ctx{batch, nullptr, 0, nullptr, with_linear ? tap_scratch : nullptr, 0};
@@ -2388,7 +2419,8 @@ int p2v_forward_grams(p2v_plan* plan, const float* images, int batch, const int8
   rc = forward_impl(plan, batch, bit_config, n_cfg, logits, ws, fwd, stream, o);
   if (rc != P2V_OK) return rc;
   if (gc.host_units.size() != K) return fail(P2V_E_STATE, "p2v_forward_grams: %zu stages ran, the layout lists %zu", gc.host_units.size(), K);
-  // pageable source: the runtime stages it before returning, so the host vector may go away afterwards
+  // pageable source on a stream that is NOT capturing (refused above): the runtime stages it before returning, so the host vector may go
+  // away afterwards.  Recorded into a graph the copy node would keep the host pointer and every replay would read freed memory
   if (hipMemcpyAsync(units, gc.host_units.data(), K * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
     return fail(P2V_E_LAUNCH, "p2v_forward_grams: %s", hipGetErrorString(hipGetLastError()));
   return P2V_OK;

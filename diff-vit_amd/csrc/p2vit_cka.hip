@@ -217,7 +217,8 @@ int p2v_launch_cka_grams(const std::vector<CkaDesc>& descs, const CkaLayout& w, 
   float* parts = reinterpret_cast<float*>(base + w.part_off);
   double* g64 = reinterpret_cast<double*>(base + w.g64_off);
   if (w.items >= (1LL << 31)) return -1;
-  // pageable source: the runtime stages it before returning, so the host vector may go away afterwards
+  // pageable source on a stream that is NOT capturing (p2v_cka_grams refuses a capturing one): the runtime stages it before returning, so
+  // the host vector may go away afterwards.  Recorded into a graph the copy node would keep the host pointer: replays would read freed memory
   hipError_t e = hipMemcpyAsync(dd, descs.data(), descs.size() * sizeof(CkaDesc), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(k_cka_partial, dim3((unsigned)w.items), dim3(256), 0, st, dd, L, n, parts);
@@ -235,7 +236,8 @@ int p2v_launch_cka_raw(const CkaDesc& desc, const CkaLayout& w, int n, double* g
   CkaDesc* dd = reinterpret_cast<CkaDesc*>(base + w.desc_off);
   float* parts = reinterpret_cast<float*>(base + w.part_off);
   if (w.items >= (1LL << 31)) return -1;
-  hipError_t e = hipMemcpyAsync(dd, &desc, sizeof(CkaDesc), hipMemcpyHostToDevice, st);      // (pageable source: staged before the call returns)
+  hipError_t e = hipMemcpyAsync(dd, &desc, sizeof(CkaDesc), hipMemcpyHostToDevice, st);      // (pageable source, eager stream only: staged before the
+                                                                                             // call returns; p2v_code_grams / p2v_forward_grams refuse a capturing stream)
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(k_cka_partial, dim3((unsigned)w.items), dim3(256), 0, st, dd, 1, n, parts);
   CHECK_LAUNCH();

@@ -314,7 +314,9 @@ int p2v_launch_pair_cosine(const std::vector<CosDesc>& descs, const CosLayout& w
   CosDesc* dd = reinterpret_cast<CosDesc*>(base + w.desc_off);
   unsigned long long* parts = reinterpret_cast<unsigned long long*>(base + w.part_off);
   if (w.items >= (1LL << 31) || (long long)L * n >= (1LL << 31)) return -1;
-  // pageable source: the runtime stages it before returning, so the host vector may go away afterwards
+  // pageable source on a stream that is NOT capturing (p2v_pair_cosine refuses a capturing one): the runtime stages it before returning, so
+  // the host vector may go away afterwards.  Recorded into a graph the copy node would keep the host pointer - and these descriptors hold
+  // device pointers: a replay would launch on garbage addresses
   hipError_t e = hipMemcpyAsync(dd, descs.data(), descs.size() * sizeof(CosDesc), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(k_cos_partial, dim3((unsigned)w.items), dim3(256), 0, st, dd, L, parts);

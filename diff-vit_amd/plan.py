@@ -129,6 +129,9 @@ class FrozenPlan:
 
     def __init__(self, arch, state_dict, calib, device='cuda', in_chans=3, input_quant=True, int_norm=True, int_softmax=True, ln_eps=1e-6,
                  softmax_bits=None):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FrozenPlan: building a plan uploads and synchronises, which a stream that is capturing a graph cannot do: '
+                               'freeze the model and run one eager forward before the capture')
         self.arch = dict(arch)
         # width of every block's log-int-softmax (the bit type of its QIntSoftmax: p = 2^-k for k < 2^bits, else 0): None = what the
         # calibration state names (export_calib of a uint3 model), else 4; an int, or one entry per block, which a named width must
@@ -620,6 +623,9 @@ class FrozenPlan:
         n = (B + 1) // 2
         with torch.cuda.device(self.device):
             if not getattr(self, '_grams_ready', False):       # once per plan: the exponent bytes and units of the per-channel scale vectors
+                if torch.cuda.is_current_stream_capturing():   # (a plan-time call: it synchronises the device and reads the scales back)
+                    raise RuntimeError('forward_grams: the stream is capturing a graph, and neither p2v_plan_prepare_grams nor '
+                                       'p2v_forward_grams can be captured: call forward_grams outside the capture')
                 E.check(L.p2v_plan_prepare_grams(self._handle))
                 self._grams_ready = True
             K = len(names)
@@ -756,6 +762,9 @@ class FrozenPlan:
         if len(sizes) == 1:
             per = self.profile(images, bit_config)
             return [per], sum(ms for _, ms in per)
+        if torch.cuda.is_current_stream_capturing():       # before the warm-up forward and the device synchronisation below
+            raise NotImplementedError('profile_streams: the stream is capturing a graph and this call times every launch with events and '
+                                      'synchronises the device; make it outside the capture')
         out = self._out(None, B)
         L = E.lib()
         with torch.cuda.device(self.device):

@@ -347,6 +347,9 @@ class SwinTransformer(nn.Module):
         scale is refused by name, before a device is asked for."""
         from .swin_plan import SwinPlan
         from .plan import module_softmax_bits
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():      # (before export_calib reads the scales back)
+            raise RuntimeError('freeze: the stream is capturing a graph and building the plan uploads, reads back and synchronises: '
+                               'run one eager quantized forward (or freeze()) before the capture')
         if not self.input_quant:
             raise NotImplementedError('the HIP engine fuses qact_input into the patch gather: input_quant=True models only')
         int_norm = bool(self.cfg.INT_NORM)

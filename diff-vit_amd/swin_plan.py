@@ -57,6 +57,9 @@ class SwinPlan:
                  int_norm=True, ln_eps=1e-5):
         if bits not in (4, 8):
             raise KeyError('int%s' % (bits,))          # (the weight scale a width has none of: what the lookup below raised)
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('SwinPlan: building a plan uploads and synchronises, which a stream that is capturing a graph cannot do: '
+                               'freeze the model and run one eager forward before the capture')
         self.arch, self.device, self.in_chans, self.bits, self.pack4 = dict(arch), torch.device(device), in_chans, bits, bool(pack4)
         self.int_softmax = bool(int_softmax)
         self.int_norm, self.ln_eps = bool(int_norm), float(ln_eps)
@@ -84,6 +87,14 @@ class SwinPlan:
             self._layers.sort(key=lambda d: d['idx'])
 
     # ---- helpers -------------------------------------------------------------------------------------------------------
+    def _no_capture(self, what):
+        """lazy plan state - freezing codes, building a RESID table, recording a sequence - uploads, allocates and synchronises, and a
+        graph capture would record that work instead of running it while the plan cached it as done: refused before anything is
+        allocated, enqueued or cached, so the plan is as usable afterwards as before (DESIGN, graph capture of the forwards)"""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('SwinPlan: the stream is capturing a graph and %s is not there yet: make the same forward(...) call - this batch size, '
+                               'slicing and bit_config - once eagerly before the capture (freeze_all() ahead of it freezes every width)' % what)
+
     def _dev(self, t, dtype=torch.float32):
         t = t.to(dtype).contiguous().to(self.device)
         self._keep.append(t)
@@ -139,6 +150,7 @@ class SwinPlan:
         f = d['forms'].get((bits, packed))
         if f is not None and (f['wf'] is not None or not frag):
             return f['lin']
+        self._no_capture('the %d-bit codes of %s' % (bits, d['name']))
         with torch.cuda.device(self.device):
             s_w, cs = self._width(d, bits)
             if f is None:
@@ -155,6 +167,7 @@ class SwinPlan:
         lin = self._lin(d, bits, packed)
         f = d['forms'][(bits, packed)]
         if f['tab'] is None:
+            self._no_capture('the %d-bit RESID table of %s' % (bits, d['name']))
             with torch.cuda.device(self.device):
                 e, n, L = d['epi'], d['N'], E.lib()
                 nbytes = L.p2v_resid_prefold_bytes(n)
@@ -353,6 +366,7 @@ class SwinPlan:
         moves the recording to another list.  Every other sequence runs the plan's default width on int8-stored codes (the RESID mid-code
         tap and the records of ``p2v_gemm_i8`` behind it take those)."""
         a = self.arch
+        self._no_capture('the recorded launch sequence of batch %d' % B)
         if attention and not self.int_softmax:
             raise NotImplementedError('the attention stages of the DDV and of the stage statistics need the log-int-softmax: the probabilities of the float softmax '
                                       '(Config(lis=False)) are not codes')
@@ -862,6 +876,11 @@ class SwinPlan:
             slices = [min(step, B - i * step) for i in range(n_streams) if i * step < B]
         if sum(slices) != B or min(slices) < 1:
             raise AssertionError('slices %r do not cover a batch of %d' % (list(slices), B))
+        if torch.cuda.is_current_stream_capturing():      # before the fork: an exception between fork and join would leave the capture unjoined
+            for i, part in enumerate(images.split(list(slices))):
+                slot = i + 1 if i < min(n_streams, len(slices)) else 0
+                if (part.shape[0], slot, True) not in self._recorded:
+                    self._no_capture('the recorded launch sequence of slice %d (batch %d)' % (i, part.shape[0]))
         self._streams = E.side_streams(self.device, n_streams)          # the process's shared side streams of this device (engine.side_streams)
         n_side = min(n_streams, len(slices))
         parts = images.split(list(slices))

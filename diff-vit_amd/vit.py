@@ -429,6 +429,9 @@ class VisionTransformer(nn.Module):
         engine cannot honour is refused here (``NotImplementedError`` naming the module): a log-int-softmax of another width, a QAct
         that is not int8."""
         from .plan import FrozenPlan, module_softmax_bits
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():      # (before export_calib reads the scales back)
+            raise RuntimeError('freeze: the stream is capturing a graph and building the plan uploads, reads back and synchronises: '
+                               'run one eager quantized forward (or freeze()) before the capture')
         dev = device or self.cls_token.device
         widths = module_softmax_bits(self, bool(self.cfg.INT_SOFTMAX))
         sd = {k: v for k, v in self.state_dict().items()}

@@ -15,6 +15,19 @@
  *     failing call on the calling thread.  The Python shim maps P2V_E_BITS -> ValueError/KeyError (as
  *     bit_pool.index / BIT_TYPE_DICT lookups do, vit_fquant.py:282, layers.py:174), P2V_E_SHAPE ->
  *     AssertionError (layers_quant.py:437), P2V_E_UNSUPPORTED -> NotImplementedError (quantizer/base.py:28).
+ *   - HIP graph capture (hipStreamBeginCapture on `stream`, torch.cuda.graph): an entry point that only launches kernels and
+ *     hipMemsetAsync on `stream`, with every argument passed by value or pointing at memory that outlives the call, can be recorded and
+ *     replayed: the whole-model forwards (p2v_forward, _u8, _taps, _linear_taps, p2v_forward_ddv / _ex / _ex2, p2v_forward_stats), p2v_run_ops
+ *     and every per-operator entry point not named below.  HOST arguments (bit_config, the p2v_op table, tap pointer arrays, p2v_* structs)
+ *     are read when the call is made, i.e. baked into the graph.  The entry points that copy from host memory of their own, read results
+ *     back, allocate, or time with events cannot be recorded - a capture records work, it does not run it - and return
+ *     P2V_E_UNSUPPORTED ("... the stream is capturing a HIP graph ...") while `stream` is capturing, after their argument checks, with
+ *     nothing enqueued and the capture left valid: p2v_pair_cosine, p2v_cka_grams, p2v_code_grams, p2v_forward_grams, p2v_forward_profile,
+ *     p2v_forward_profile_begin / _end (the token stays valid), p2v_run_ops_profile, p2v_gelu_table_build, p2v_resid_prefold.  A capture
+ *     status that cannot be read is not taken as capturing.  The plan-time calls that take no stream and synchronise the device
+ *     (p2v_plan_set_block, p2v_plan_set_linear, p2v_plan_set_head, p2v_plan_set_float_block, p2v_ln_prefold, p2v_plan_prepare_grams) and
+ *     p2v_plan_create / _destroy belong in front of any capture; they have no stream to ask.  A new refusal is no ABI change.
+ *     (tests/test_graph_capture_gpu.py; the table of every entry point is in DESIGN.md, "Graph capture of the forwards".)
  *   - activations between kernels are int8 codes, row-major [rows][channels]; "rows" = batch*tokens.
  *   - all scales named *_pot are exact powers of two (the reference's PoT observers, minmax.py:247-251);
  *     per-channel PTF scales (ptf.py:51,133) are arbitrary fp32 and are divided by, as the reference does.
