@@ -166,6 +166,7 @@ extern int g_ln_rows;
 extern int g_attn_waves;
 extern int g_ln_gemm;
 extern int g_ln_gemm_ver;
+extern int g_ln_gemm_lean;
 extern int g_gemm_tile;
 extern int g_resid_pre;
 extern int g_attn_stream;
@@ -199,6 +200,7 @@ static const struct Switch {
     {"cls_rows", "P2V_CLS_ROWS", &g_cls_rows, 0, 1, 1, ANY_ENV},
     {"ln_rows", "P2V_LN_ROWS", &g_ln_rows, 1, 64, 1, 0},
     {"ln_generic", "P2V_LN_GENERIC", &g_ln_generic, 0, 1, 1, ANY_API},
+    {"ln_gemm_lean", "P2V_LN_GEMM_LEAN", &g_ln_gemm_lean, 0, 1, 1, ANY_ENV | ANY_API},
 };
 
 static void read_env_once() {

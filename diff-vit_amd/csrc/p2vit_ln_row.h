@@ -17,6 +17,32 @@ __device__ __forceinline__ int half_wave_sum(int v) {
   return v;
 }
 
+// The four sums of a row pair (S1 and S2 of rows 0 and 1) over the 32 lanes of a half wave, reduced TOGETHER: the first two exchange
+// steps each halve what a lane carries, so 2 + 1 + 3 cross-lane adds replace the 4 x 5 of four half_wave_sum calls (integers: any order
+// is exact).  A DPP move writes only the banks (4 lanes; bit b of the mask = lanes 4b .. 4b+3 of each row of 16) its bank mask names and
+// keeps `old` elsewhere, so x = (partner's p | own q), y = (own p | partner's q) and x + y is p summed in one half of the banks, q in the other:
+//   row_mirror      (lane i <-> 15 - i, bank b <-> 3 - b): banks 0,1 collect row 0, banks 2,3 row 1          4 values -> 2
+//   row_half_mirror (lane i <-> 7 - i, bank 0 <-> 1, 2 <-> 3): banks 0,2 collect S1, banks 1,3 S2             2 values -> 1
+//   xor 1, xor 2 inside the quad (one lane of every bank has been visited: the row of 16 is complete), xor 16
+// Result: S1 / S2 of row r in the lanes of bank 2r (lanes 8r .. 8r+3 and 16 + 8r .. of the half wave); the lanes of banks 1 and 3 hold
+// the two sums exchanged, which nobody reads.
+template <int CTRL, int BANKS_P>
+__device__ __forceinline__ int dpp_halve(int p, int q) {
+  const int x = __builtin_amdgcn_update_dpp(q, p, CTRL, 0xF, BANKS_P, false);
+  const int y = __builtin_amdgcn_update_dpp(p, q, CTRL, 0xF, BANKS_P ^ 0xF, false);
+  return x + y;
+}
+__device__ __forceinline__ void half_wave_sum_pair(const int (&S1)[2], const unsigned (&S2)[2], int& S1k, unsigned& S2k) {
+  const int a = dpp_halve<0x140, 0x3>(S1[0], S1[1]);                 // row_mirror
+  const int b = dpp_halve<0x140, 0x3>((int)S2[0], (int)S2[1]);
+  int v = dpp_halve<0x141, 0x5>(a, b);                               // row_half_mirror
+  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);    // quad_perm [1,0,3,2]
+  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);    // quad_perm [2,3,0,1]
+  v += __builtin_amdgcn_ds_swizzle(v, 0x401F);                      // bitmask mode: lane ^ 16
+  S1k = v;
+  S2k = (unsigned)__builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false);   // the quads agree: the mirror of 8 lanes is the neighbouring bank
+}
+
 // generic per-element chain: every step of get_MN / the 'int' forward as written in the reference
 // os > 0: the output scale itself - the two quotients are IEEE divisions like the reference's; os == 0: multiply by io = 1/scale
 // (identical for powers of two)
