@@ -1230,6 +1230,75 @@ int p2v_patch_similarity_entropy(const float* av, int images, int groups, int he
   return launch_rc(p2v_launch_psaq(a, workspace, value_out, grad_out, (hipStream_t)stream), "patch_similarity_entropy");
 }
 
+// ---- Hutchinson trace bookkeeping (p2vit_hessian.hip)
+static int hs_check_n(const char* who, int n_segs) {
+  if (n_segs < 1 || n_segs > 65536) return fail(P2V_E_ARG, "%s: n_segs = %d (1 ... 65536)", who, n_segs);
+  return P2V_OK;
+}
+static int hs_check_segs(const char* who, const p2v_seg* segs, int n_segs) {
+  if (const int rc = hs_check_n(who, n_segs)) return rc;
+  if (!segs) return fail(P2V_E_ARG, "%s: null argument", who);
+  for (int s = 0; s < n_segs; ++s) {
+    if (!segs[s].ptr || (uintptr_t)segs[s].ptr % 4) return fail(P2V_E_ARG, "%s: segment %d: null or misaligned pointer", who, s);
+    if (segs[s].n < 1 || segs[s].n > 0x7fffffffLL) return fail(P2V_E_ARG, "%s: segment %d: n = %lld (1 ... 2^31 - 1)", who, s, segs[s].n);
+  }
+  return P2V_OK;
+}
+static int hs_check_segs2(const char* who, const p2v_seg2* segs, int n_segs) {
+  if (const int rc = hs_check_n(who, n_segs)) return rc;
+  if (!segs) return fail(P2V_E_ARG, "%s: null argument", who);
+  for (int s = 0; s < n_segs; ++s) {
+    if (!segs[s].a || !segs[s].b || (uintptr_t)segs[s].a % 4 || (uintptr_t)segs[s].b % 4)
+      return fail(P2V_E_ARG, "%s: segment %d: null or misaligned pointer", who, s);
+    if (segs[s].n < 1 || segs[s].n > 0x7fffffffLL) return fail(P2V_E_ARG, "%s: segment %d: n = %lld (1 ... 2^31 - 1)", who, s, segs[s].n);
+  }
+  return P2V_OK;
+}
+
+int p2v_rademacher_fill(const p2v_seg* segs, int n_segs, uint64_t seed, uint64_t probe, void* stream) {
+  if (const int rc = hs_check_segs("p2v_rademacher_fill", segs, n_segs)) return rc;
+  return launch_rc(p2v_launch_rademacher_fill(segs, n_segs, seed, probe, (hipStream_t)stream), "rademacher_fill");
+}
+
+size_t p2v_group_dot_workspace_bytes(const p2v_seg2* segs, int n_segs) {
+  if (hs_check_segs2("p2v_group_dot_workspace_bytes", segs, n_segs) != P2V_OK) return 0;
+  return (size_t)p2v_hs_dot_chunks(segs, n_segs) * sizeof(double);
+}
+
+static int hs_check_dot(const char* who, const p2v_seg2* segs, int n_segs, const void* out, const void* ws, size_t ws_bytes) {
+  if (const int rc = hs_check_segs2(who, segs, n_segs)) return rc;
+  if (!out || !ws) return fail(P2V_E_ARG, "%s: null argument", who);
+  if ((uintptr_t)out % 8 || (uintptr_t)ws % 8) return fail(P2V_E_ARG, "%s: out / record and ws must be 8-byte aligned", who);
+  const size_t need = (size_t)p2v_hs_dot_chunks(segs, n_segs) * sizeof(double);
+  if (ws_bytes < need) return fail(P2V_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+  return P2V_OK;
+}
+
+int p2v_group_dot(const p2v_seg2* segs, int n_segs, double* out, void* ws, size_t ws_bytes, void* stream) {
+  if (const int rc = hs_check_dot("p2v_group_dot", segs, n_segs, out, ws, ws_bytes)) return rc;
+  return launch_rc(p2v_launch_group_dot(segs, n_segs, out, static_cast<double*>(ws), nullptr, 0, 0.0, (hipStream_t)stream), "group_dot");
+}
+
+size_t p2v_hutchinson_state_bytes(int n_segs) { return n_segs < 1 || n_segs > 65536 ? 0 : p2v_hs_state_bytes(n_segs); }
+
+int p2v_hutchinson_init(void* state, size_t state_bytes, int n_segs, void* stream) {
+  if (const int rc = hs_check_n("p2v_hutchinson_init", n_segs)) return rc;
+  if (!state || (uintptr_t)state % 8) return fail(P2V_E_ARG, "p2v_hutchinson_init: null or misaligned state");
+  if (state_bytes < p2v_hs_state_bytes(n_segs)) return fail(P2V_E_WORKSPACE, "p2v_hutchinson_init: state %zu < %zu bytes", state_bytes, p2v_hs_state_bytes(n_segs));
+  return launch_rc(p2v_launch_hutchinson_init(state, n_segs, (hipStream_t)stream), "hutchinson_init");
+}
+
+int p2v_hutchinson_step(const p2v_seg2* segs, int n_segs, int probe, int max_iter, double tol, double* record, void* state,
+                        size_t state_bytes, void* ws, size_t ws_bytes, void* stream) {
+  if (const int rc = hs_check_dot("p2v_hutchinson_step", segs, n_segs, record, ws, ws_bytes)) return rc;
+  if (!state || (uintptr_t)state % 8) return fail(P2V_E_ARG, "p2v_hutchinson_step: null or misaligned state");
+  if (max_iter < 1 || probe < 0 || probe >= max_iter) return fail(P2V_E_ARG, "p2v_hutchinson_step: probe %d outside 0 ... max_iter - 1 = %d", probe, max_iter - 1);
+  if (tol != tol) return fail(P2V_E_ARG, "p2v_hutchinson_step: tol is not a number");
+  if (state_bytes < p2v_hs_state_bytes(n_segs)) return fail(P2V_E_WORKSPACE, "p2v_hutchinson_step: state %zu < %zu bytes", state_bytes, p2v_hs_state_bytes(n_segs));
+  return launch_rc(p2v_launch_group_dot(segs, n_segs, record + (size_t)probe * n_segs, static_cast<double*>(ws), state, probe, tol, (hipStream_t)stream),
+                   "hutchinson_step");
+}
+
 size_t p2v_resid_prefold_bytes(int N) { return N > 0 ? resid_tab_floats(N) * sizeof(float) : 0; }
 
 int p2v_resid_prefold(const p2v_linear* lin, const p2v_epilogue* epi, int N, float* tab, size_t tab_bytes, int* usable, void* stream) {

@@ -291,3 +291,12 @@ struct PsaqArgs {
 PsaqLayout p2v_psaq_layout(int B, int G, int N, int hd);
 // -1: a launch grid beyond 2^31 workgroups
 int p2v_launch_psaq(const PsaqArgs& a, void* ws, double* value, float* grad, hipStream_t st);
+
+// Hutchinson bookkeeping (p2vit_hessian.hip): segments per launch - their table is the launch's kernel argument
+#define HS_MAX_SEGS 64
+size_t p2v_hs_state_bytes(int n_layers);
+long long p2v_hs_dot_chunks(const p2v_seg2* segs, int n_segs);          // fp64 partials p2v_launch_group_dot writes
+int p2v_launch_rademacher_fill(const p2v_seg* segs, int n_segs, unsigned long long seed, unsigned long long probe, hipStream_t st);
+// state == nullptr: the sums alone; else the stopping update of layer s with (probe, tol) behind out[s]
+int p2v_launch_group_dot(const p2v_seg2* segs, int n_segs, double* out, double* partials, void* state, int probe, double tol, hipStream_t st);
+int p2v_launch_hutchinson_init(void* state, int n_layers, hipStream_t st);

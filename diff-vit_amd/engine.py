@@ -133,6 +133,19 @@ class GramLayer(C.Structure):
     _fields_ = [('base', _p), ('shift', _p), ('sample_stride', _ll), ('row_stride', _ll), ('rows', _i), ('cols', _i), ('dtype', _i)]
 
 
+class Seg(C.Structure):
+    """``p2v_seg``: one tensor of ``p2v_rademacher_fill`` (n fp32 elements at ptr; layer selects the generator stream)."""
+    _fields_ = [('ptr', _p), ('n', _ll), ('layer', _i)]
+
+
+class Seg2(C.Structure):
+    """``p2v_seg2``: one pair of tensors of ``p2v_group_dot`` / ``p2v_hutchinson_step`` (n fp32 elements at a and at b)."""
+    _fields_ = [('a', _p), ('b', _p), ('n', _ll)]
+
+
+HS_HEADER_BYTES, HS_LAYER_BYTES = 16, 32      # the state of p2v_hutchinson_step: header, then a record per layer (include/p2vit.h)
+
+
 class P2VError(RuntimeError):
     pass
 
@@ -275,6 +288,15 @@ def lib():
         L.p2v_psaq_workspace_bytes.argtypes = [_i, _i, _i, _i, _i]
         L.p2v_psaq_workspace_bytes.restype = C.c_size_t
         L.p2v_patch_similarity_entropy.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p]
+    if hasattr(L, 'p2v_hutchinson_step'):         # the Hutchinson trace bookkeeping is additive, found by its symbols
+        L.p2v_rademacher_fill.argtypes = [C.POINTER(Seg), _i, C.c_uint64, C.c_uint64, _p]
+        L.p2v_group_dot_workspace_bytes.argtypes = [C.POINTER(Seg2), _i]
+        L.p2v_group_dot_workspace_bytes.restype = C.c_size_t
+        L.p2v_group_dot.argtypes = [C.POINTER(Seg2), _i, _p, _p, C.c_size_t, _p]
+        L.p2v_hutchinson_state_bytes.argtypes = [_i]
+        L.p2v_hutchinson_state_bytes.restype = C.c_size_t
+        L.p2v_hutchinson_init.argtypes = [_p, C.c_size_t, _i, _p]
+        L.p2v_hutchinson_step.argtypes = [C.POINTER(Seg2), _i, _i, _i, C.c_double, _p, _p, C.c_size_t, _p, C.c_size_t, _p]
     L.p2v_forward_profile.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_int32), _i]
     L.p2v_forward_profile_begin.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _p, C.POINTER(_p)]

@@ -67,6 +67,13 @@ def build_parser():
     p.add_argument('--search-iter', default=8, type=int, help='--mixed: evolutionary iterations (test_quant.py:343)')
     p.add_argument('--search-max-configs', default=50, type=int, help='--mixed: Pareto candidates kept (test_quant.py:281)')
     p.add_argument('--search-slack', default=1.1, type=float, help='--mixed: size constraint = slack x the all-4-bit model (test_quant.py:262)')
+    p.add_argument('--hessian-batches', default=0, type=int,
+                   help='--mixed: weight the search by the per-layer Hessian traces of this many batches (test_quant.py:147-191; 0: '
+                        'every layer weighs 1)')
+    p.add_argument('--hessian-batch-size', default=32, type=int, help='images per batch of --hessian-batches')
+    p.add_argument('--hessian-probes', default='joint', choices=['joint', 'layer'],
+                   help="'layer': one double backward per layer and probe, as the reference; 'joint': one per probe for all layers "
+                        '(unbiased, noisier; hessian.hutchinson_traces)')
     return p
 
 
@@ -354,6 +361,25 @@ def validate_many(args, val_loader, model, device, bit_configs):
     return [res[k] for k in keys]
 
 
+def _hessian_batches(args, loader, device):
+    """the first ``--hessian-batches`` batches of ``--hessian-batch-size`` images of the loader with its labels (uint8 batches through the
+    fp32 table, like the calibration batch)"""
+    xs, ys, have, want = [], [], 0, args.hessian_batches * args.hessian_batch_size
+    for x, y in loader:
+        x = x.to(device)
+        if x.dtype == torch.uint8:
+            from .data import expand_uint8, uint8_lut
+            x = expand_uint8(x, uint8_lut(*uint8_stats(args)), 'NHWC')
+        xs.append(x)
+        ys.append(y.to(device))
+        have += x.shape[0]
+        if have >= want:
+            break
+    x, y = torch.cat(xs)[:want], torch.cat(ys)[:want]
+    n = args.hessian_batch_size
+    return [(x[i:i + n], y[i:i + n]) for i in range(0, x.shape[0], n)]
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     seed(args.seed)
@@ -386,6 +412,14 @@ def main(argv=None):
         loader = SyntheticLoader(args.n_val, args.val_batchsize, arch['img_size'], arch['num_classes'], args.seed, device, tgt, uint8=u8)
     criterion = nn.CrossEntropyLoss().to(device)
     bit_config = None
+    mean_hessian = None
+    if args.mixed and args.hessian_batches > 0:
+        # test_quant.py:147-191, before the calibration as there: the float model's per-layer Hessian traces weight the search
+        print('Calculating the sensitiveties via the averaged Hessian trace.......')
+        from .hessian import mean_hessian as _mean_hessian
+        mean_hessian = _mean_hessian(model, criterion, _hessian_batches(args, loader if train_loader is None else train_loader, device), probes=args.hessian_probes, seed=args.seed,
+                                     select='layers' if _is_swin(model) else 'reference')
+        print('\n***Trace: ', mean_hessian)
     if args.quant:
         if args.mode == 0 and train_loader is not None:
             print('Calibrating with real data...')                       # test_quant.py:214-233, mode 0: the first training batch
@@ -418,7 +452,8 @@ def main(argv=None):
             # Swin: the candidates tie {qkv, proj} and {fc1, fc2} of a block and keep the convolution at 8 bits (search_ties)
             ranked, pop = mixed_precision_search(score, FLOPs, global_distance, seed=args.seed, pop_size=args.search_pop,
                                                  evo_iter=args.search_iter, max_configs=args.search_max_configs, slack=args.search_slack,
-                                                 score_many=score_many, ties=model.search_ties() if _is_swin(model) else None)
+                                                 score_many=score_many, ties=model.search_ties() if _is_swin(model) else None,
+                                                 mean_hessian=mean_hessian)
             print('best mixed-precision configuration: Prec@1 %.3f' % pop[0][1])
             print(pop[0][0])
             return validate(args, loader, model, criterion, device, pop[0][0], device_metrics=args.device_metrics) + (pop[0][0],)

@@ -20,6 +20,10 @@ one without the built library raises ``RuntimeError`` from ``engine.lib()``.
     torch.ops.p2vit.code_grams(tensors, shifts)                                 raw fp64 Grams X X^T of codes / values   DDV_CKA.py (MinibatchAdvCKA)
     torch.ops.p2vit.cka_centre(raw)                                             the centring of _generate_gram_matrix   efficient_CKA.py:28-39
     torch.ops.p2vit.patch_similarity_entropy(av, groups)                        entropy term and its gradient   generate_data.py:102-113, 128-134
+    torch.ops.p2vit.rademacher_fill(tensors, layers, seed, probe)               the +-1 probe vectors of all tensors   pyhessian/hessian.py:184-190
+    torch.ops.p2vit.group_dot(a, b)                                             fp64 sum(a * b) per tensor pair   pyhessian/utils.py:27-34
+    torch.ops.p2vit.hutchinson_init(state, n_layers)                            clears the stopping state
+    torch.ops.p2vit.hutchinson_step(a, b, probe, tol, record, state)            group_dot + the stopping rule per layer   pyhessian/hessian.py:196-204
 """
 import ctypes as C
 
@@ -46,6 +50,10 @@ _LIB.define('code_stats(Tensor[] tensors) -> Tensor[]')
 _LIB.define('code_grams(Tensor[] tensors, Tensor?[] shifts) -> Tensor')
 _LIB.define('cka_centre(Tensor raw) -> Tensor')
 _LIB.define('patch_similarity_entropy(Tensor av, int groups) -> (Tensor value, Tensor grad)')
+_LIB.define('rademacher_fill(Tensor(a!)[] tensors, int[] layers, int seed, int probe) -> ()')
+_LIB.define('group_dot(Tensor[] a, Tensor[] b) -> Tensor')
+_LIB.define('hutchinson_init(Tensor(a!) state, int n_layers) -> ()')
+_LIB.define('hutchinson_step(Tensor[] a, Tensor[] b, int probe, float tol, Tensor(a!) record, Tensor(b!) state) -> ()')
 
 
 def _f32(t):
@@ -464,6 +472,86 @@ def _patch_similarity_entropy(av, groups):
     return value, grad
 
 
+def _flat_f32(who, t, dev):
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() < 1:
+        raise AssertionError('%s: tensors are non-empty contiguous fp32 on %s (got %s %s on %s)' % (who, dev, t.dtype, tuple(t.shape), t.device))
+    return t
+
+
+def _rademacher_fill(tensors, layers, seed, probe):
+    """fills every tensor with +-1 in place: element e of tensors[k] from (seed, layers[k], probe, e) - ``hessian.rademacher_host`` gives
+    the same values; one launch per 64 tensors, nothing synchronises"""
+    if not tensors or len(layers) != len(tensors):
+        raise AssertionError('rademacher_fill: one layer id per tensor, at least one tensor')
+    dev = tensors[0].device
+    segs = (E.Seg * len(tensors))()
+    for k, (t, l) in enumerate(zip(tensors, layers)):
+        _flat_f32('rademacher_fill', t, dev)
+        segs[k].ptr, segs[k].n, segs[k].layer = t.data_ptr(), t.numel(), int(l)
+    with torch.cuda.device(dev):
+        E.check(E.lib().p2v_rademacher_fill(segs, len(tensors), int(seed) & (2 ** 64 - 1), int(probe) & (2 ** 64 - 1), E.stream_ptr(dev)))
+
+
+def seg2_table(who, a, b):
+    """the ``p2v_seg2`` array of the tensor pairs (a[k], b[k])"""
+    if not a or len(a) != len(b):
+        raise AssertionError('%s: as many tensors in a as in b, at least one' % who)
+    dev = a[0].device
+    segs = (E.Seg2 * len(a))()
+    for k, (x, y) in enumerate(zip(a, b)):
+        _flat_f32(who, x, dev)
+        _flat_f32(who, y, dev)
+        if x.numel() != y.numel():
+            raise AssertionError('%s: pair %d has %d and %d elements' % (who, k, x.numel(), y.numel()))
+        segs[k].a, segs[k].b, segs[k].n = x.data_ptr(), y.data_ptr(), x.numel()
+    return segs, dev
+
+
+def _dot_workspace(who, segs, n, dev):
+    nbytes = E.lib().p2v_group_dot_workspace_bytes(segs, n)
+    if nbytes == 0:
+        E.check(E.lib().p2v_group_dot(segs, n, None, None, 0, None))       # raises with the validation message
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+
+
+def _group_dot(a, b):
+    """fp64 [len(a)]: sum over the elements of a[k] * b[k], every product exact, fixed summation order (p2v_group_dot)"""
+    segs, dev = seg2_table('group_dot', a, b)
+    with torch.cuda.device(dev):
+        ws = _dot_workspace('group_dot', segs, len(a), dev)
+        out = torch.empty(len(a), dtype=torch.float64, device=dev)
+        E.check(E.lib().p2v_group_dot(segs, len(a), E.ptr(out), E.ptr(ws), ws.numel() * 8, E.stream_ptr(dev)))
+    return out
+
+
+def hutchinson_state(n_layers, device):
+    """a cleared stopping state of ``n_layers`` layers (int32 words; ``hessian.read_state`` decodes it)"""
+    state = torch.empty(E.lib().p2v_hutchinson_state_bytes(n_layers) // 4, dtype=torch.int32, device=device)
+    _hutchinson_init(state, n_layers)
+    return state
+
+
+def _hutchinson_init(state, n_layers):
+    if state.dtype != torch.int32 or not state.is_contiguous():
+        raise AssertionError('hutchinson_init: the state is a contiguous int32 tensor')
+    with torch.cuda.device(state.device):
+        E.check(E.lib().p2v_hutchinson_init(E.ptr(state), state.numel() * 4, n_layers, E.stream_ptr(state.device)))
+
+
+def _hutchinson_step(a, b, probe, tol, record, state):
+    """one probe of all layers: record[probe][k] = sum(a[k] * b[k]), then every layer's stopping rule on the device
+    (p2v_hutchinson_step); record fp64 [max_iter, len(a)], state from ``hutchinson_state``"""
+    segs, dev = seg2_table('hutchinson_step', a, b)
+    if record.dtype != torch.float64 or record.dim() != 2 or record.shape[1] != len(a) or not record.is_contiguous() or record.device != dev:
+        raise AssertionError('hutchinson_step: record is contiguous fp64 [max_iter, %d] on %s' % (len(a), dev))
+    if state.dtype != torch.int32 or not state.is_contiguous() or state.device != dev:
+        raise AssertionError('hutchinson_step: the state is a contiguous int32 tensor on %s' % dev)
+    with torch.cuda.device(dev):
+        ws = _dot_workspace('hutchinson_step', segs, len(a), dev)
+        E.check(E.lib().p2v_hutchinson_step(segs, len(a), int(probe), record.shape[0], float(tol), E.ptr(record), E.ptr(state), state.numel() * 4,
+                                            E.ptr(ws), ws.numel() * 8, E.stream_ptr(dev)))
+
+
 _LIB.impl('fake_quant', _fake_quant, 'CUDA')
 _LIB.impl('quantize_patchify', _quantize_patchify, 'CUDA')
 _LIB.impl('linear_requant', lambda x, w, cs, b, inv: _linear(E.EPI_REQUANT, x, w, cs, b, inv), 'CUDA')
@@ -481,7 +569,11 @@ _LIB.impl('code_stats', lambda tensors: _code_stats(tensors), 'CUDA')
 _LIB.impl('code_grams', _code_grams, 'CUDA')
 _LIB.impl('cka_centre', _cka_centre, 'CUDA')
 _LIB.impl('patch_similarity_entropy', _patch_similarity_entropy, 'CUDA')
+_LIB.impl('rademacher_fill', _rademacher_fill, 'CUDA')
+_LIB.impl('group_dot', _group_dot, 'CUDA')
+_LIB.impl('hutchinson_init', _hutchinson_init, 'CUDA')
+_LIB.impl('hutchinson_step', _hutchinson_step, 'CUDA')
 
 OPS = ('fake_quant', 'quantize_patchify', 'linear_requant', 'linear_gelu_requant', 'int_layernorm', 'lis_attention', 'lis_attention_rows', 'forward', 'cka_grams',
        'hsic_accumulate', 'pair_cosine', 'score_logits', 'score_accumulate', 'code_stats', 'code_grams', 'cka_centre',
-       'patch_similarity_entropy')
+       'patch_similarity_entropy', 'rademacher_fill', 'group_dot', 'hutchinson_init', 'hutchinson_step')

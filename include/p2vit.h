@@ -1125,6 +1125,47 @@ size_t p2v_psaq_workspace_bytes(int images, int groups, int heads, int tokens, i
 int p2v_patch_similarity_entropy(const float* av, int images, int groups, int heads, int tokens, int head_dim, void* workspace,
                                  double* value_out, float* grad_out, void* stream);
 
+/* ---- Hutchinson trace bookkeeping around torch's double backward (pyhessian/hessian.py:163-211) ----
+ * The Hessian-vector product stays autograd's; these entry points make the probe vectors of all selected tensors in one launch, take
+ * v . Hv of all of them in two, and keep every layer's stopping rule on the device.  `segs` is a HOST array, read during the call: up to
+ * 64 segments go into one launch, whose table travels as the kernel argument, so nothing is uploaded, nothing synchronises and a graph
+ * capture records the call.  Segment pointers are device fp32, 4-byte aligned; a start or length off the 16-byte grid costs scalar
+ * accesses at the two ends only.  Nothing outside [ptr, ptr + n) is touched.
+ *
+ * The generator.  splitmix64(x): x += 0x9E3779B97F4A7C15; z = x; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+ * 0x94D049BB133111EB; return z ^ z >> 31 (mod 2^64).  key(seed, layer, probe) = splitmix64(splitmix64(splitmix64(seed) ^ layer) ^
+ * probe), layer as an unsigned 32-bit value; element e of the stream is +1.0f when bit e % 64 of splitmix64(key + e / 64) is set, else
+ * -1.0f.  A segment's values depend on (seed, layer, probe, e) alone, not on its address or on the other segments of the call.
+ *
+ * P2V_E_ARG before any HIP call: n_segs outside 1 ... 65536, a null or misaligned pointer, n outside 1 ... 2^31 - 1, probe outside
+ * 0 ... max_iter - 1, tol not a number; P2V_E_WORKSPACE: ws / state smaller than the query says. */
+typedef struct {
+  float* ptr;
+  long long n;
+  int32_t layer;
+} p2v_seg;
+typedef struct {
+  const float* a;
+  const float* b;
+  long long n;
+} p2v_seg2;
+int p2v_rademacher_fill(const p2v_seg* segs, int n_segs, uint64_t seed, uint64_t probe, void* stream);
+/* out (dev fp64 [n_segs]): out[s] = sum_e (double)a[e] * (double)b[e] of segment s.  Every product is exact; a workgroup adds 4096 of
+ * them in a fixed order into one fp64 partial in ws (p2v_group_dot_workspace_bytes, 8-byte aligned; 0 = refused), a second launch adds a
+ * segment's partials in a fixed order.  No floating-point atomics: two runs give the same bytes; NaN and Inf propagate. */
+size_t p2v_group_dot_workspace_bytes(const p2v_seg2* segs, int n_segs);
+int p2v_group_dot(const p2v_seg2* segs, int n_segs, double* out, void* ws, size_t ws_bytes, void* stream);
+/* One probe of all layers: the group dot into record[probe][0 .. n_segs) (dev fp64 [max_iter][n_segs]), then, one thread per layer, the
+ * stopping rule: sum += value; mean = sum / (probe + 1); if |mean - trace| / (|trace| + 1e-6) < tol the layer is done and keeps `trace`
+ * (the PREVIOUS prefix mean), else trace = mean.  A finished layer ignores later values.  Call with probe = 0, 1, 2, ... in order.
+ * state (dev, 8-byte aligned, p2v_hutchinson_state_bytes(n_segs) bytes, cleared by p2v_hutchinson_init):
+ *   int32 running (layers not done - the one word a host needs to poll), int32 n_layers, 8 bytes unused; then per layer 32 bytes:
+ *   fp64 sum, fp64 trace, int32 probes (consumed; stop index + 1 once done), int32 done, int32 converged, 4 bytes unused. */
+size_t p2v_hutchinson_state_bytes(int n_segs);
+int p2v_hutchinson_init(void* state, size_t state_bytes, int n_segs, void* stream);
+int p2v_hutchinson_step(const p2v_seg2* segs, int n_segs, int probe, int max_iter, double tol, double* record, void* state,
+                        size_t state_bytes, void* ws, size_t ws_bytes, void* stream);
+
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
 
