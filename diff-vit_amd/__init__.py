@@ -52,6 +52,9 @@ from . import psaq  # noqa: F401
 from .psaq import generate_data, patch_similarity_entropy  # noqa: F401
 from . import hessian  # noqa: F401  (the module; its pyhessian drop-in class is ``diff_vit_amd.hessian.hessian``)
 from .hessian import hutchinson_traces, mean_hessian, select_params  # noqa: F401
+from . import restore  # noqa: F401
+from .harness import forward_many  # noqa: F401
+from .restore import restore_sweep  # noqa: F401
 
 __all__ = ['BIT_TYPE_DICT', 'QAct', 'QConv2d', 'QIntLayerNorm', 'QIntSoftmax', 'QLinear', 'Config', 'VisionTransformer',
            'deit_tiny_patch16_224', 'deit_small_patch16_224', 'deit_base_patch16_224', 'vit_base_patch16_224',
@@ -60,4 +63,5 @@ __all__ = ['BIT_TYPE_DICT', 'QAct', 'QConv2d', 'QIntLayerNorm', 'QIntSoftmax', '
            'swin_large_patch4_window12_384', 'SwinPlan', 'get_activations', 'MinibatchCKA',
            'MinibatchAdvCKA', 'compute_cka', 'compute_ddv', 'gen_adv_inputs', 'AttackPGD', 'DeviceMeter', 'score_rows_reference',
            'gen_profiling_inputs_in_blackbox', 'metrics_output_diversity', 'compute_stats', 'StageStats', 'code_stats_cpu',
-           'generate_data', 'patch_similarity_entropy', 'hutchinson_traces', 'mean_hessian', 'select_params']
+           'generate_data', 'patch_similarity_entropy', 'hutchinson_traces', 'mean_hessian', 'select_params', 'forward_many',
+           'restore_sweep']

@@ -880,12 +880,18 @@ struct Fwd {
     if (full() && (rc = ddv_i8_deq(LN, T, D, b.fc2_epi.s_mid))) return rc;                                       // mlp.qact2
     return ddv_i8(X, T, D, b.fc2_epi.s_next);                                                                    // Block.qact4
   }
+
+  // The pieces of a forward, in the order forward_impl runs them: stem, block_at 0 .. depth - 1, final_norm, head, finish.  Of the workspace
+  // only x carries state from one piece to the next (cls: from final_norm to head), which is what p2v_forward_many's shared prefixes rest on.
+  int stem(int bits);
+  int block_at(int i, const int8_t* bc);
+  int final_norm();
+  int head(int bits, float* logits);
+  int finish();
 };
 
-static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace, size_t workspace_bytes,
-                        void* stream, const FwdOpts& o) {
-  if (!p || !(o.images || o.u8) || !bit_config || !logits || !workspace) return fail(P2V_E_ARG, "p2v_forward: null argument");
-  if (batch <= 0) return fail(P2V_E_SHAPE, "batch must be positive");
+// What every whole-model entry point asks of a bit list and of the plan it runs on (before any HIP call)
+static int check_forward(const p2v_plan* p, const int8_t* bit_config, int n_cfg, const FwdOpts& o) {
   if (n_cfg != p->n_layers) return fail(P2V_E_BITS, "bit_config has %d entries, model needs %d", n_cfg, p->n_layers);
   for (int i = 0; i < n_cfg; ++i) {
     const int bi = bit_index(bit_config[i]);
@@ -902,18 +908,16 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
     if (p->float_softmax && o.ddv && o.ddv->attn)
       return fail(P2V_E_UNSUPPORTED, "P2V_DDV_STAGES_ATTN: the plan's softmax is the float one, its probabilities are not codes");
   }
-  const WsLayout w = ws_layout(p, batch);
-  if (workspace_bytes < w.total) return fail(P2V_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, w.total);
-  if (o.lin_tap && o.lin_tap[0] && !(p->inv_s_input > 0.f))
-    return fail(P2V_E_UNSUPPORTED, "p2v_forward_linear_taps: no patch-embed tap for input_quant = False (the fp32-image convolution); pass NULL for taps[0]");
-  const p2v_model_desc& d = p->d;
-  Fwd f(p, o, batch, w, workspace, (hipStream_t)stream);
-  const hipStream_t st = f.st;
-  const int D = f.D, T = f.T, Kp = p->k_patch_pad, rows_p = batch * p->patches;
-  int rc;
+  return P2V_OK;
+}
 
-  // qact_input + PatchEmbed + cls/pos/qact1                                 vit_fquant.py:705-733
-  const p2v_linear& embed = p->lin[bit_index(bit_config[0])][0];
+// qact_input + PatchEmbed + cls/pos/qact1 into x, every row of it; bits: the convolution's width      vit_fquant.py:705-733
+int Fwd::stem(int bits) {
+  Fwd& f = *this;
+  const p2v_model_desc& d = p->d;
+  const int Kp = p->k_patch_pad, rows_p = batch * p->patches;
+  int rc;
+  const p2v_linear& embed = p->lin[bit_index(bits)][0];
   if (p->inv_s_input > 0.f) {
     rc = f.step(P2V_K_PATCHIFY, [&] {
       return o.u8 ? launch_rc(p2v_launch_u8_patchify(o.u8, batch, d.in_chans, d.img_size, d.img_size, d.patch_size, o.layout, (const int8_t*)o.lut, f.P, Kp, st), "u8_patchify")
@@ -949,21 +953,27 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
     });
     if (rc) return rc;
   }
-  if ((rc = f.step(P2V_K_FILL_CLS, [&] { return launch_rc(p2v_launch_fill_cls(f.X, batch, T, D, p->cls_codes, st), "fill_cls"); })) ||
-      (rc = f.ddv_i8(f.X, T, D, p->embed_epi.s_next)))                                                           // qact1
+  if ((rc = f.step(P2V_K_FILL_CLS, [&] { return launch_rc(p2v_launch_fill_cls(f.X, batch, T, D, p->cls_codes, st), "fill_cls"); })))
     return rc;
+  return f.ddv_i8(f.X, T, D, p->embed_epi.s_next);                                                               // qact1
+}
 
+// Block i of the forward on the rows it needs; bc: its four bit widths
+int Fwd::block_at(int i, const int8_t* bc) {
   // The logits read the last block's output through its class-token rows only (the final norm below takes [:, 0]) and everything
   // behind the qkv GEMM is row-local but for the attention's keys and values: query row 0 of every (image, head), then proj, norm2,
   // fc1 and fc2 on `batch` rows - proj and fc2 in place on the class rows of x (stride T * D), the rows between them compact at the
   // start of ln / hid.  The patch rows of x / att / hid keep what the launches before left there.  So the last block runs on the class
   // rows when nothing but the logits is asked for (parity runs read the workspace), and T * D fits the int strides of a GEMM.
   const bool cls_only = g_cls_rows && !p->float_norm && !p->float_softmax && o.stop_after < 0 && !o.qkv_tap && !o.fc1_tap && !o.lin_tap && !o.ddv && (long long)T * D <= 0x7fffffffLL;
-  const RowSet all_rows{f.M, D, 0, false}, cls_rows{batch, (long long)T * D, 1, true};
-  for (int i = 0; i < d.depth && !f.done; ++i)
-    if ((rc = f.block(i, bit_config + 1 + 4 * i, (cls_only && i == d.depth - 1) ? cls_rows : all_rows))) return rc;
+  const RowSet all_rows{M, D, 0, false}, cls_rows{batch, (long long)T * D, 1, true};
+  return block(i, bc, (cls_only && i == p->d.depth - 1) ? cls_rows : all_rows);
+}
 
-  // norm over the cls rows only ([:,0]) -> qact2 -> head -> act_out         vit_fquant.py:766-796
+// norm over the cls rows only ([:,0]) -> qact2, into cls; x stays as it is                             vit_fquant.py:766-767
+int Fwd::final_norm() {
+  Fwd& f = *this;
+  int rc;
   if (p->float_norm) {
     if (float* vals = f.full()) {    // FULL DDV stages: the final norm once more, over every row, for its values
       const FloatLnArgs a{f.X, D, f.M, D, (double)p->final_fln.s_in, (double)p->final_fln.eps, p->final_fln.gamma, p->final_fln.beta, p->final_fln.g, f.LN, D, vals};
@@ -981,14 +991,27 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
     lf.pre = p->final_ln.pre;
     if ((rc = f.layernorm(lf)) || (rc = f.ddv_i8(f.CLS, 1, D, nullptr))) return rc;                               // qact2
   }
-  const p2v_linear& head = p->lin[bit_index(bit_config[n_cfg - 1])][n_cfg - 1];
+  return P2V_OK;
+}
+
+// head -> act_out: cls -> logits; bits: the head's width                                               vit_fquant.py:790-796
+int Fwd::head(int bits, float* logits) {
+  Fwd& f = *this;
+  const p2v_model_desc& d = p->d;
+  const int n_cfg = p->n_layers;
+  int rc;
+  const p2v_linear& lin = p->lin[bit_index(bits)][n_cfg - 1];
   p2v_epilogue eh{};
   eh.inv_s_out = p->head_inv_s;
   eh.s_out = p->head_s;
-  if ((rc = f.gemm(P2V_K_GEMM_HEAD, false, P2V_EPI_HEAD, f.CLS, D, batch, f.Dk, d.num_classes, head, eh, logits, d.num_classes))) return rc;
-  if ((rc = f.lin_tap(n_cfg - 1, f.CLS, D, batch, f.Dk, d.num_classes, head)) || (rc = f.ddv_tap(1, d.num_classes)) ||
-      (rc = f.ddv_f32(logits, 1, d.num_classes)))                                                                // head, act_out
-    return rc;
+  if ((rc = f.gemm(P2V_K_GEMM_HEAD, false, P2V_EPI_HEAD, f.CLS, D, batch, f.Dk, d.num_classes, lin, eh, logits, d.num_classes))) return rc;
+  if ((rc = f.lin_tap(n_cfg - 1, f.CLS, D, batch, f.Dk, d.num_classes, lin)) || (rc = f.ddv_tap(1, d.num_classes))) return rc;   // head
+  return f.ddv_f32(logits, 1, d.num_classes);                                                                    // act_out
+}
+
+// the end of a whole pass: the profile's closing events
+int Fwd::finish() {
+  Fwd& f = *this;
   if (f.done) return P2V_OK;
   if (Prof* prof = o.prof) {
     if (prof->used + 2 > (int)prof->ev.size()) return fail(P2V_E_LAUNCH, "profile: event pool exhausted");
@@ -999,6 +1022,161 @@ static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_
   return P2V_OK;
 }
 
+static int forward_impl(p2v_plan* p, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace, size_t workspace_bytes,
+                        void* stream, const FwdOpts& o) {
+  if (!p || !(o.images || o.u8) || !bit_config || !logits || !workspace) return fail(P2V_E_ARG, "p2v_forward: null argument");
+  if (batch <= 0) return fail(P2V_E_SHAPE, "batch must be positive");
+  if (const int rc = check_forward(p, bit_config, n_cfg, o)) return rc;
+  const WsLayout w = ws_layout(p, batch);
+  if (workspace_bytes < w.total) return fail(P2V_E_WORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, w.total);
+  if (o.lin_tap && o.lin_tap[0] && !(p->inv_s_input > 0.f))
+    return fail(P2V_E_UNSUPPORTED, "p2v_forward_linear_taps: no patch-embed tap for input_quant = False (the fp32-image convolution); pass NULL for taps[0]");
+  Fwd f(p, o, batch, w, workspace, (hipStream_t)stream);
+  int rc;
+  if ((rc = f.stem(bit_config[0]))) return rc;
+  for (int i = 0; i < p->d.depth && !f.done; ++i)
+    if ((rc = f.block_at(i, bit_config + 1 + 4 * i))) return rc;
+  if ((rc = f.final_norm()) || (rc = f.head(bit_config[n_cfg - 1], logits))) return rc;
+  return f.finish();
+}
+
+// ---- p2v_forward_many: several bit lists in one call --------------------------------------------------------------------------------------
+// A prefix tree over the lists, depth + 2 levels deep: level 0 is keyed by the stem's entry, level 1 + i by the four entries of block i, the
+// last one is the tail (the final norm once, then a head GEMM per distinct head entry).  The walk is depth first, the children of a node in
+// the order the caller's array first shows them; what the lists of a node share has run once when the walk reaches it.  A node with several
+// children keeps x in a snapshot slot (saved once, restored in front of every child but the first): x is all a block hands to the next, and
+// the engine is integer-exact, so a list's logits are those of a forward of its own.  The stem writes every row of x and the tail writes none
+// of it: the root and the tail need no slot.  The same walk with f == nullptr only counts (p2v_forward_many_plan, p2v_forward_many_bytes).
+struct ManyWalk {
+  const int8_t* cfgs;                 // host [n_lists][n_cfg]
+  int n_cfg, depth;
+  Fwd* f = nullptr;
+  float* logits = nullptr;            // dev [n_lists][per_list]
+  size_t per_list = 0;                // batch * classes
+  int8_t* slots = nullptr;            // the snapshot slots, slot_bytes apart; x_bytes of each are used
+  size_t slot_bytes = 0, x_bytes = 0;
+  int stems = 0, blocks = 0, norms = 0, heads = 0, copies = 0, snapshots = 0;
+
+  // the entries of list l that level `level` is keyed by, as one word (a level has at most four of them)
+  uint32_t key(int l, int level) const {
+    const int8_t* c = cfgs + (size_t)l * n_cfg;
+    const int lo = level == 0 ? 0 : (level <= depth ? 1 + 4 * (level - 1) : n_cfg - 1), n = (level >= 1 && level <= depth) ? 4 : 1;
+    uint32_t k = 0;
+    memcpy(&k, c + lo, n);
+    return k;
+  }
+  // `lists` by their key of `level`, groups and members in order of first appearance
+  std::vector<std::vector<int>> children(const std::vector<int>& lists, int level) const {
+    std::vector<std::vector<int>> groups;
+    std::vector<uint32_t> keys;
+    for (int l : lists) {
+      const uint32_t k = key(l, level);
+      size_t g = 0;
+      while (g < keys.size() && keys[g] != k) ++g;
+      if (g == keys.size()) {
+        keys.push_back(k);
+        groups.emplace_back();
+      }
+      groups[g].push_back(l);
+    }
+    return groups;
+  }
+  int copy(void* dst, const void* src, size_t bytes) {
+    if (!f) return P2V_OK;
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, f->st);
+    return e == hipSuccess ? P2V_OK : fail(P2V_E_LAUNCH, "p2v_forward_many: hipMemcpyAsync: %s", hipGetErrorString(e));
+  }
+  // the final norm of the lists' common x, a head GEMM per distinct head entry, a copy of the logits per repeated list
+  int tail(const std::vector<int>& lists) {
+    int rc;
+    ++norms;
+    if (f && (rc = f->final_norm())) return rc;
+    for (const std::vector<int>& g : children(lists, depth + 1)) {
+      float* out = logits + (size_t)g[0] * per_list;
+      ++heads;
+      if (f && (rc = f->head(cfgs[(size_t)g[0] * n_cfg + n_cfg - 1], out))) return rc;
+      for (size_t k = 1; k < g.size(); ++k)
+        if ((rc = copy(logits + (size_t)g[k] * per_list, out, per_list * sizeof(float)))) return rc;
+    }
+    return P2V_OK;
+  }
+  // `lists` agree on every level in front of `level`, whose launches have run; `held`: the snapshot slots in use on the way here
+  int visit(const std::vector<int>& lists, int level, int held) {
+    if (level == depth + 1) return tail(lists);
+    const std::vector<std::vector<int>> groups = children(lists, level);
+    const bool keep = level > 0 && groups.size() > 1;
+    int8_t* slot = f ? slots + (size_t)held * slot_bytes : nullptr;
+    int rc;
+    if (keep) {
+      snapshots = snapshots > held + 1 ? snapshots : held + 1;
+      ++copies;
+      if (f && (rc = copy(slot, f->X, x_bytes))) return rc;
+    }
+    for (size_t g = 0; g < groups.size(); ++g) {
+      const int8_t* c = cfgs + (size_t)groups[g][0] * n_cfg;
+      if (keep && g > 0) {
+        ++copies;
+        if (f && (rc = copy(f->X, slot, x_bytes))) return rc;
+      }
+      if (level == 0) {
+        ++stems;
+        if (f && (rc = f->stem(c[0]))) return rc;
+      } else {
+        ++blocks;
+        if (f && (rc = f->block_at(level - 1, c + 1 + 4 * (level - 1)))) return rc;
+      }
+      if ((rc = visit(groups[g], level + 1, held + (keep ? 1 : 0)))) return rc;
+    }
+    return P2V_OK;
+  }
+  int run(int n_lists) {
+    std::vector<int> all(n_lists);
+    for (int l = 0; l < n_lists; ++l) all[l] = l;
+    return visit(all, 0, 0);
+  }
+};
+
+// what the three p2v_forward_many* entry points ask of the lists; the plan only has to exist
+static int check_many_lists(const char* who, const p2v_plan* p, const int8_t* bit_configs, int n_lists, int n_cfg) {
+  if (!p || !bit_configs) return fail(P2V_E_ARG, "%s: null argument", who);
+  if (n_lists < 1 || n_lists > P2V_MANY_MAX_LISTS) return fail(P2V_E_SHAPE, "%s: %d lists (1 ... %d are taken)", who, n_lists, P2V_MANY_MAX_LISTS);
+  if (n_cfg != p->n_layers) return fail(P2V_E_BITS, "%s: the bit lists have %d entries, model needs %d", who, n_cfg, p->n_layers);
+  for (int l = 0; l < n_lists; ++l)
+    for (int i = 0; i < n_cfg; ++i)
+      if (bit_index(bit_configs[(size_t)l * n_cfg + i]) < 0)
+        return fail(P2V_E_BITS, "%s: list %d: %d is not in list", who, l, (int)bit_configs[(size_t)l * n_cfg + i]);
+  return P2V_OK;
+}
+static size_t many_slot_bytes(const p2v_plan* p, int batch) { return ((size_t)batch * p->tokens * p->d.embed_dim + 255) / 256 * 256; }
+
+static int forward_many_impl(const char* who, p2v_plan* p, int batch, const int8_t* bit_configs, int n_lists, int n_cfg, float* logits, void* ws,
+                             size_t ws_bytes, void* stream, const FwdOpts& o) {
+  if (!p || !(o.images || o.u8) || !bit_configs || !logits || !ws) return fail(P2V_E_ARG, "%s: null argument", who);
+  if (batch <= 0) return fail(P2V_E_SHAPE, "%s: batch must be positive", who);
+  int rc;
+  if ((rc = check_many_lists(who, p, bit_configs, n_lists, n_cfg))) return rc;
+  for (int l = 0; l < n_lists; ++l)
+    if ((rc = check_forward(p, bit_configs + (size_t)l * n_cfg, n_cfg, o))) {
+      char why[sizeof g_err];
+      memcpy(why, g_err, sizeof why);
+      return fail(rc, "%s: list %d: %.400s", who, l, why);
+    }
+  ManyWalk dry{bit_configs, n_cfg, p->d.depth};
+  dry.run(n_lists);
+  const WsLayout w = ws_layout(p, batch);
+  const size_t need = w.total + (size_t)dry.snapshots * many_slot_bytes(p, batch);
+  if (ws_bytes < need) return fail(P2V_E_WORKSPACE, "%s: workspace %zu < %zu bytes (p2v_forward_many_bytes)", who, ws_bytes, need);
+  Fwd f(p, o, batch, w, ws, (hipStream_t)stream);
+  ManyWalk walk{bit_configs, n_cfg, p->d.depth};
+  walk.f = &f;
+  walk.logits = logits;
+  walk.per_list = (size_t)batch * p->d.num_classes;
+  walk.slots = reinterpret_cast<int8_t*>(ws) + w.total;
+  walk.slot_bytes = many_slot_bytes(p, batch);
+  walk.x_bytes = (size_t)batch * p->tokens * p->d.embed_dim;
+  return walk.run(n_lists);
+}
+
 extern "C" {
 
 int p2v_forward(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,
@@ -1006,6 +1184,31 @@ int p2v_forward(p2v_plan* p, const float* images, int batch, const int8_t* bit_c
   FwdOpts o;
   o.images = images; o.stop_after = stop_after;
   return forward_impl(p, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stream, o);
+}
+
+int p2v_forward_many_plan(const p2v_plan* plan, const int8_t* bit_configs, int n_lists, int n_cfg, int* stems, int* blocks, int* norms, int* heads,
+                          int* copies, int* snapshots) {
+  if (const int rc = check_many_lists("p2v_forward_many_plan", plan, bit_configs, n_lists, n_cfg)) return rc;
+  ManyWalk w{bit_configs, n_cfg, plan->d.depth};
+  w.run(n_lists);
+  const struct { int* out; int v; } counts[] = {{stems, w.stems}, {blocks, w.blocks}, {norms, w.norms}, {heads, w.heads}, {copies, w.copies},
+                                                {snapshots, w.snapshots}};
+  for (const auto& c : counts)
+    if (c.out) *c.out = c.v;
+  return P2V_OK;
+}
+
+size_t p2v_forward_many_bytes(const p2v_plan* plan, int batch, const int8_t* bit_configs, int n_lists, int n_cfg) {
+  int snapshots = 0;
+  if (!plan || batch <= 0 || p2v_forward_many_plan(plan, bit_configs, n_lists, n_cfg, nullptr, nullptr, nullptr, nullptr, nullptr, &snapshots)) return 0;
+  return ws_layout(plan, batch).total + (size_t)snapshots * many_slot_bytes(plan, batch);
+}
+
+int p2v_forward_many(p2v_plan* p, const float* images, int batch, const int8_t* bit_configs, int n_lists, int n_cfg, float* logits, void* ws,
+                     size_t ws_bytes, void* stream) {
+  FwdOpts o;
+  o.images = images;
+  return forward_many_impl("p2v_forward_many", p, batch, bit_configs, n_lists, n_cfg, logits, ws, ws_bytes, stream, o);
 }
 
 // uint8 input (p2v_forward_u8, p2v_u8_patchify): images and table present, a known layout, images 4-byte aligned (the kernels read dwords)
@@ -1023,6 +1226,15 @@ int p2v_forward_u8(p2v_plan* p, const uint8_t* images, int layout, const void* l
   FwdOpts o;
   o.u8 = images; o.layout = layout; o.lut = lut; o.stop_after = stop_after;
   return forward_impl(p, batch, bit_config, n_cfg, logits, workspace, workspace_bytes, stream, o);
+}
+
+int p2v_forward_many_u8(p2v_plan* p, const uint8_t* images, int layout, const void* lut, int batch, const int8_t* bit_configs, int n_lists,
+                        int n_cfg, float* logits, void* ws, size_t ws_bytes, void* stream) {
+  const int rc = check_u8_input("p2v_forward_many_u8", images, layout, lut);
+  if (rc) return rc;
+  FwdOpts o;
+  o.u8 = images; o.layout = layout; o.lut = lut;
+  return forward_many_impl("p2v_forward_many_u8", p, batch, bit_configs, n_lists, n_cfg, logits, ws, ws_bytes, stream, o);
 }
 
 int p2v_forward_taps(p2v_plan* p, const float* images, int batch, const int8_t* bit_config, int n_cfg, float* logits, void* workspace,

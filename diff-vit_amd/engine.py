@@ -304,6 +304,12 @@ def lib():
     L.p2v_quantize_patchify.argtypes = [_p, _i, _i, _i, _i, _i, _f, _p, _i, _p]
     L.p2v_forward_u8.argtypes = [_p, _p, _i, _p, _i, C.POINTER(C.c_int8), _i, _p, _p, C.c_size_t, _i, _p]
     L.p2v_u8_patchify.argtypes = [_p, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p]
+    if hasattr(L, 'p2v_forward_many'):            # many bit lists in one call (host int8 [n_lists][n_cfg]), additive, found by their symbols
+        L.p2v_forward_many.argtypes = [_p, _p, _i, C.POINTER(C.c_int8), _i, _i, _p, _p, C.c_size_t, _p]
+        L.p2v_forward_many_u8.argtypes = [_p, _p, _i, _p, _i, C.POINTER(C.c_int8), _i, _i, _p, _p, C.c_size_t, _p]
+        L.p2v_forward_many_bytes.argtypes = [_p, _i, C.POINTER(C.c_int8), _i, _i]
+        L.p2v_forward_many_bytes.restype = C.c_size_t
+        L.p2v_forward_many_plan.argtypes = [_p, C.POINTER(C.c_int8), _i, _i] + [C.POINTER(_i)] * 6
     L.p2v_gemm_i8.argtypes = [_i, _p, _i, _i, _i, _i, C.POINTER(Linear), C.POINTER(Epilogue), _p, _i, _p, _p]
     L.p2v_int_layernorm.argtypes = [_p, _ll, _i, _i, C.POINTER(Ln), _p, _ll, _p]
     L.p2v_lis_attention.argtypes = [_p, _i, _i, _i, _i, C.POINTER(Attn), _p, _p, _p]

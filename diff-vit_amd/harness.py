@@ -110,6 +110,19 @@ def _forward(model, data, bit_config=None, stats=None):
     return model(data, bit_config, False)
 
 
+def forward_many(model, data, bit_configs, stats=None):
+    """[logits, ...]: those of ``_forward(model, data, bc, stats)`` for every ``bc`` of ``bit_configs``.  A fused ViT / DeiT model on a GPU
+    runs lists without a -1 in ONE engine call that executes what the lists share once (``VisionTransformer.forward_many``, bit-equal to
+    the per-list forwards).  Everything else is the per-list loop: any other model state, a list with -1, and Swin, whose forward is a
+    recorded p2v_op sequence with no single buffer carried from block to block."""
+    bit_configs = list(bit_configs)
+    if bit_configs and not _is_swin(model) and model.many_on_engine(data, bit_configs):
+        if stats is not None:
+            return model.forward_many_uint8(data, bit_configs, stats[0], stats[1], 'NHWC')
+        return model.forward_many(data, bit_configs)
+    return [_forward(model, data, bc, stats)[0] for bc in bit_configs]
+
+
 def uint8_stats(args):
     """(mean, std) of the model family (data.MODEL_STATS) when ``--uint8-input`` is on, else None"""
     if not getattr(args, 'uint8_input', False):
@@ -340,7 +353,8 @@ def validate_many(args, val_loader, model, device, bit_configs):
     """[(loss, top1, top5), ...] of ``validate(..., device_metrics=True)`` for every entry of ``bit_configs``, in input order, from ONE
     pass over the loader: batch-major, each batch is brought to the device once and forwarded under every distinct configuration into
     a meter slot of its own (duplicates are scored once).  The mixed-precision search scores a population this way instead of
-    re-reading the validation set per candidate."""
+    re-reading the validation set per candidate.  On a fused ViT / DeiT model the configurations of a batch are one engine call that
+    runs their common prefixes once (``forward_many``); the logits, and so the results, are those of the per-list forwards."""
     from .score import DeviceMeter
     keys = [None if bc is None else tuple(int(b) for b in bc) for bc in bit_configs]
     distinct = list(dict.fromkeys(keys))
@@ -349,10 +363,11 @@ def validate_many(args, val_loader, model, device, bit_configs):
     meter = DeviceMeter((1, 5), slots=len(distinct), device=device)
     model.eval()
     stats = uint8_stats(args)
+    lists = [None if bc is None else list(bc) for bc in distinct]
     for data, target in DevicePrefetcher(val_loader, device):
-        for s, bc in enumerate(distinct):
-            with torch.no_grad():
-                output, FLOPs, distance = _forward(model, data, None if bc is None else list(bc), stats)
+        with torch.no_grad():
+            outputs = forward_many(model, data, lists, stats)
+        for s, output in enumerate(outputs):
             meter.update(output, target, slot=s)
     res = {}
     for s, bc in enumerate(distinct):
@@ -380,10 +395,9 @@ def _hessian_batches(args, loader, device):
     return [(x[i:i + n], y[i:i + n]) for i in range(0, x.shape[0], n)]
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
-    seed(args.seed)
-    device = torch.device(args.device)
+def build_model_and_loaders(args, device):
+    """the model of ``--model`` (seeded synthetic weights, ``--pretrained`` or ``--checkpoint``) on ``device`` in eval mode, its validation
+    loader and, for ``--real-data``, the training loader the mode-0 calibration reads (else None)"""
     cfg = Config(args.ptf, args.lis, args.quant_method).set_softmax_bits(args.softmax_bits)
     model = str2model(args.model)(pretrained=args.pretrained, cfg=cfg)
     arch = model.arch
@@ -410,6 +424,36 @@ def main(argv=None):
         with torch.no_grad():
             tgt = torch.cat([_forward(model, d, None, uint8_stats(args))[0].argmax(1).cpu() for d, _ in loader])
         loader = SyntheticLoader(args.n_val, args.val_batchsize, arch['img_size'], arch['num_classes'], args.seed, device, tgt, uint8=u8)
+    return model, loader, train_loader
+
+
+def calibration_data(args, model, train_loader, device):
+    """the calibration batch of ``--mode`` (test_quant.py:205-233): 0 the first training batch, 2 images generated from the float model,
+    else Gaussian noise"""
+    if args.mode == 0 and train_loader is not None:
+        print('Calibrating with real data...')                       # test_quant.py:214-233, mode 0: the first training batch
+        calib_data = next(iter(train_loader))[0].to(device)
+        if calib_data.dtype == torch.uint8:                          # --uint8-input: the normalised batch, through the fp32 table
+            from .data import expand_uint8, uint8_lut
+            calib_data = expand_uint8(calib_data, uint8_lut(*uint8_stats(args)), 'NHWC')
+    elif args.mode == 2:
+        print('Generating data...')                                  # test_quant.py:205-208, mode 2: PSAQ-ViT images from the float model
+        from .data import model_family
+        from .psaq import generate_data
+        calib_data = generate_data(model, args.calib_batchsize, iterations=args.psaq_iters, family=model_family(args.model))
+        print('Calibrating with generated data...')
+    else:
+        print('Calibrating with Gaussian noise...')
+        calib_data = synth.images(args.seed + 1, args.calib_batchsize, model.arch['img_size']).to(device)
+    return calib_data
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    seed(args.seed)
+    device = torch.device(args.device)
+    model, loader, train_loader = build_model_and_loaders(args, device)
+    arch = model.arch
     criterion = nn.CrossEntropyLoss().to(device)
     bit_config = None
     mean_hessian = None
@@ -421,21 +465,7 @@ def main(argv=None):
                                      select='layers' if _is_swin(model) else 'reference')
         print('\n***Trace: ', mean_hessian)
     if args.quant:
-        if args.mode == 0 and train_loader is not None:
-            print('Calibrating with real data...')                       # test_quant.py:214-233, mode 0: the first training batch
-            calib_data = next(iter(train_loader))[0].to(device)
-            if calib_data.dtype == torch.uint8:                          # --uint8-input: the normalised batch, through the fp32 table
-                from .data import expand_uint8, uint8_lut
-                calib_data = expand_uint8(calib_data, uint8_lut(*uint8_stats(args)), 'NHWC')
-        elif args.mode == 2:
-            print('Generating data...')                                  # test_quant.py:205-208, mode 2: PSAQ-ViT images from the float model
-            from .data import model_family
-            from .psaq import generate_data
-            calib_data = generate_data(model, args.calib_batchsize, iterations=args.psaq_iters, family=model_family(args.model))
-            print('Calibrating with generated data...')
-        else:
-            print('Calibrating with Gaussian noise...')
-            calib_data = synth.images(args.seed + 1, args.calib_batchsize, arch['img_size']).to(device)
+        calib_data = calibration_data(args, model, train_loader, device)
         _, FLOPs, global_distance = calibrate_model(model, calib_data, where=args.calib_on)
         if args.mixed:
             # test_quant.py:253-408 on the fast path: every candidate bit_config is one validate() over the HIP engine (the frozen

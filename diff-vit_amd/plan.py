@@ -687,42 +687,110 @@ class FrozenPlan:
         return self._run_slices(images, out, n_streams, slices, lambda: self.forward(images, bit_config, out=out),
                                 lambda xi, n_i, oi, ws, ws_n, st: L.p2v_forward(handle, xi, n_i, cfg, n_cfg, oi, ws, ws_n, -1, st))
 
+    def _cfgs(self, bit_configs):
+        """``bit_configs`` (a sequence of bit lists of this plan's length) as the host array [n_lists][n_cfg] of p2v_forward_many"""
+        lists = [list(bc) if bc is not None else None for bc in bit_configs]
+        if not lists:
+            raise AssertionError('forward_many needs at least one bit list')
+        if any(bc is None for bc in lists):
+            raise ValueError('None is not in list')        # bit_pool.index(None), vit_fquant.py:282
+        if any(len(bc) != self.n_layers for bc in lists):
+            raise ValueError('bit lists of %r entries, model needs %d' % (sorted({len(bc) for bc in lists}), self.n_layers))
+        return self._cfg([b for bc in lists for b in bc]), len(lists)
+
+    def forward_many_plan(self, bit_configs):
+        """what ``forward_many`` runs for these lists, counted without a launch (p2v_forward_many_plan): stem runs, block runs, final norms,
+        head GEMMs, copies of the residual stream (saves + restores) and snapshot slots.  A loop of ``forward`` runs ``len(bit_configs)``
+        stems, norms and heads and ``len(bit_configs) * depth`` blocks."""
+        cfgs, n_lists = self._cfgs(bit_configs)
+        names = ('stems', 'blocks', 'norms', 'heads', 'copies', 'snapshots')
+        vals = [C.c_int() for _ in names]
+        E.check(E.lib().p2v_forward_many_plan(self._handle, cfgs, n_lists, self.n_layers, *[C.byref(v) for v in vals]))
+        return {k: v.value for k, v in zip(names, vals)}
+
+    def _forward_many(self, images, cfgs, n_lists, n_streams, slices, call):
+        """the body of ``forward_many`` / ``forward_many_uint8`` behind their input checks; ``call(images_ptr, n, out_ptr, ws_ptr, ws_bytes,
+        stream_ptr)`` is the entry point on a batch or a slice of it.  Every slice runs the whole tree of lists on its own stream and
+        workspace into a [n_lists, n, classes] tensor of its own, which is copied into its columns of the result once the streams have joined."""
+        L, B, nc = E.lib(), images.shape[0], self.arch['num_classes']
+        ws_bytes = lambda n: L.p2v_forward_many_bytes(self._handle, n, cfgs, n_lists, self.n_layers)
+        with torch.cuda.device(self.device):
+            out = torch.empty(n_lists, B, nc, dtype=torch.float32, device=self.device)
+            parts = {}
+
+            def whole():
+                ws = self.workspace(B, ws_bytes(B))
+                E.check(call(E.ptr(images), B, E.ptr(out), E.ptr(ws), ws.numel(), E.stream_ptr(self.device)))
+
+            def part(lo, hi):
+                parts[lo, hi] = torch.empty(n_lists, hi - lo, nc, dtype=torch.float32, device=self.device)
+                return parts[lo, hi]
+            self._run_slices(images, out, n_streams, slices, whole, call, ws_bytes, part)
+            for (lo, hi), t in parts.items():
+                out[:, lo:hi].copy_(t)
+        return out
+
+    def forward_many(self, images, bit_configs, n_streams=1, slices=None):
+        """``forward`` under every list of ``bit_configs`` in one call: fp32 [n_lists, B, classes], row l byte-equal to ``forward(images,
+        bit_configs[l])``.  The lists share what they have in common (p2v_forward_many): a prefix tree over (stem entry, the four entries of
+        block 0, 1, ...), every node run once, the residual stream saved where the tree branches.  ``n_streams`` / ``slices`` cut the batch
+        as ``forward_streams`` does."""
+        cfgs, n_lists = self._cfgs(bit_configs)
+        images, _ = self._check(images, bit_configs[0])
+        L, handle, n_cfg = E.lib(), self._handle, self.n_layers
+        return self._forward_many(images, cfgs, n_lists, n_streams, slices,
+                                  lambda xi, n_i, oi, ws, ws_n, st: L.p2v_forward_many(handle, xi, n_i, cfgs, n_lists, n_cfg, oi, ws, ws_n, st))
+
+    def forward_many_uint8(self, images, lut, bit_configs, layout='NHWC', n_streams=1, slices=None):
+        """``forward_many`` on uint8 images read through ``lut`` (``input_lut``): row l is byte-equal to ``forward_uint8(images, lut,
+        bit_configs[l], layout)``."""
+        cfgs, n_lists = self._cfgs(bit_configs)
+        images, _ = self._check_u8(images, lut, bit_configs[0], layout)
+        L, handle, n_cfg, lay, lp = E.lib(), self._handle, self.n_layers, E.LAYOUTS[layout], E.ptr(lut)
+        return self._forward_many(images, cfgs, n_lists, n_streams, slices,
+                                  lambda xi, n_i, oi, ws, ws_n, st: L.p2v_forward_many_u8(handle, xi, lay, lp, n_i, cfgs, n_lists, n_cfg, oi, ws, ws_n, st))
+
     @staticmethod
     def slice_streams(n_slices, n_side):
         """the stream of every slice: round robin over the ``n_side`` side streams and, as index ``n_side``, the caller's stream"""
         return [i % (n_side + 1) for i in range(n_slices)]
 
-    def _slices(self, sizes, n_streams):
+    def _slices(self, sizes, n_streams, ws_bytes=None):
         """what a sliced run needs, for ``_run_slices`` and ``profile_streams``: the borrowed side streams (the process's shared ones of this
-        device, never new ones) and per slice (lo, hi, stream index of ``slice_streams``, its own grow-only workspace)"""
+        device, never new ones) and per slice (lo, hi, stream index of ``slice_streams``, its own grow-only workspace of ``ws_bytes(n)``
+        bytes for its n images; default: p2v_workspace_bytes)"""
         n_side = min(len(sizes), max(n_streams, 1))
         self._streams = E.side_streams(self.device, n_side)
         self._ws_multi += [None] * (len(sizes) - len(self._ws_multi))
         L, rows, hi = E.lib(), [], 0
         for i, (n_i, j) in enumerate(zip(sizes, self.slice_streams(len(sizes), n_side))):
-            n = L.p2v_workspace_bytes(self._handle, n_i)
+            n = ws_bytes(n_i) if ws_bytes else L.p2v_workspace_bytes(self._handle, n_i)
             if self._ws_multi[i] is None or self._ws_multi[i].numel() < n:
                 self._ws_multi[i] = torch.empty(n, dtype=torch.uint8, device=self.device)
             rows.append((hi, hi + n_i, j, self._ws_multi[i]))
             hi += n_i
         return self._streams, rows
 
-    def _run_slices(self, images, out, n_streams, slices, whole, launch):
-        """the body of ``forward_streams`` / ``forward_uint8_streams`` behind their input checks: ``whole()`` runs a batch that stays in one
-        piece, ``launch(images_ptr, n, out_ptr, ws_ptr, ws_bytes, stream_ptr)`` enqueues one slice (``engine.run_on_streams``)"""
+    def _run_slices(self, images, out, n_streams, slices, whole, launch, ws_bytes=None, part=None):
+        """the body of ``forward_streams`` / ``forward_uint8_streams`` / ``forward_many`` behind their input checks: ``whole()`` runs a batch
+        that stays in one piece, ``launch(images_ptr, n, out_ptr, ws_ptr, ws_bytes, stream_ptr)`` enqueues one slice
+        (``engine.run_on_streams``).  ``ws_bytes(n)``: the workspace of a slice of n images when it is not p2v_workspace_bytes;
+        ``part(lo, hi)``: what the slice of images lo .. hi writes when that is not ``out[lo:hi]`` (``out`` is then the caller's to check)"""
         B = images.shape[0]
         n_streams = min(n_streams, E.compute_side_streams(self.device))      # (one less while an input pipeline copies on engine.copy_stream)
         sizes = list(slices) if slices is not None else self.slice_sizes(B, n_streams)
         if sum(sizes) != B or min(sizes) < 1:
             raise AssertionError('slices %r do not cover a batch of %d' % (sizes, B))
-        self._check_out(out, B)
+        if part is None:
+            self._check_out(out, B)
+            part = lambda lo, hi: out[lo:hi]
         if len(sizes) == 1:
             return whole()
         with torch.cuda.device(self.device):
-            side, rows = self._slices(sizes, n_streams)
+            side, rows = self._slices(sizes, n_streams, ws_bytes)
             jobs = [[] for _ in range(len(side) + 1)]                 # the calls of every stream, in slice order
             for lo, hi, j, ws in rows:
-                args = (E.ptr(images[lo:hi]), hi - lo, E.ptr(out[lo:hi]), E.ptr(ws), ws.numel())
+                args = (E.ptr(images[lo:hi]), hi - lo, E.ptr(part(lo, hi)), E.ptr(ws), ws.numel())
                 jobs[j].append(lambda st, args=args: E.check(launch(*args, C.c_void_p(st.cuda_stream))))
             E.run_on_streams(self.device, side, jobs)
         return out

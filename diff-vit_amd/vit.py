@@ -524,6 +524,42 @@ class VisionTransformer(nn.Module):
         x = self.act_out(x)
         return x, FLOPs, global_distance
 
+    def many_on_engine(self, x, bit_configs):
+        """``forward_many`` / ``forward_many_uint8`` go to the engine's many-list call in the state ``forward`` takes its plain hot path in
+        (fused, no hooks, no taps) when the input is on a GPU and no list asks for a float layer (-1); everything else is the per-list
+        ``forward``"""
+        return (x.is_cuda and self._fused() and not self.capture_taps and all(bc is not None and all(int(b) != -1 for b in bc) for bc in bit_configs)
+                and not any(m._forward_hooks for m in self.linear_modules()))
+
+    def forward_many(self, x, bit_configs):
+        """the logits of ``self(x, bc)[0]`` for every ``bc`` of ``bit_configs``, as a list in that order.  A fused model on the GPU runs
+        them in one engine call that shares the lists' common prefixes (``FrozenPlan.forward_many``), bit-equal to the per-list forwards;
+        any other state (float, dequant, CPU, a list with -1) is the per-list ``forward``."""
+        bit_configs = list(bit_configs)
+        if not bit_configs or not self.many_on_engine(x, bit_configs):
+            return [self(x, bc)[0] for bc in bit_configs]
+        if self._plan is None:
+            self.freeze(x.device if x.is_cuda else None)
+        return list(self._plan.forward_many(x, [[int(b) for b in bc] for bc in bit_configs], 3 if x.shape[0] >= 64 else 1).unbind(0))
+
+    def forward_many_uint8(self, images, bit_configs, mean, std, layout='NHWC'):
+        """``forward_many`` on uint8 images: the logits of ``self.forward_uint8(images, bc, mean, std, layout)[0]`` for every ``bc``."""
+        bit_configs = list(bit_configs)
+        if not bit_configs or not self.many_on_engine(images, bit_configs):
+            return [self.forward_uint8(images, bc, mean, std, layout)[0] for bc in bit_configs]
+        if self._plan is None:
+            self.freeze(images.device if images.is_cuda else None)
+        lut = self._plan_lut(self._uint8_lut(mean, std))
+        return list(self._plan.forward_many_uint8(images, lut, [[int(b) for b in bc] for bc in bit_configs], layout,
+                                                  3 if images.shape[0] >= 64 else 1).unbind(0))
+
+    def _plan_lut(self, lut):
+        """the device table of the frozen plan for the fp32 table ``lut``: it goes with the plan (input scale)"""
+        cache = self._plan.__dict__.setdefault('_u8_luts', {})
+        key = lut.numpy().tobytes()
+        if key not in cache:
+            cache[key] = self._plan.input_lut(lut)
+        return cache[key]
 
     def forward_uint8(self, images, bit_config, mean, std, layout='NHWC'):
         """``forward`` on uint8 images ([B, H, W, C] for layout 'NHWC', [B, C, H, W] for 'NCHW') that the device normalises with
@@ -537,15 +573,12 @@ class VisionTransformer(nn.Module):
                 raise ValueError('None is not in list')          # bit_pool.index(None), vit_fquant.py:282
             if self._plan is None:
                 self.freeze(images.device if images.is_cuda else None)
-            cache = self._plan.__dict__.setdefault('_u8_luts', {})       # device tables: they go with the plan (input scale)
-            key = lut.numpy().tobytes()
-            if key not in cache:
-                cache[key] = self._plan.input_lut(lut)
+            dev_lut = self._plan_lut(lut)
             bits = [int(b) for b in bit_config]
             if images.shape[0] >= 64:       # the slices of forward (FrozenPlan.slice_sizes)
                 out = torch.empty(images.shape[0], self.num_classes, dtype=torch.float32, device=self._plan.device)
-                return self._plan.forward_uint8_streams(images, cache[key], bits, out, layout, 3), self.flops(), []
-            return self._plan.forward_uint8(images, cache[key], bits, layout), self.flops(), []
+                return self._plan.forward_uint8_streams(images, dev_lut, bits, out, layout, 3), self.flops(), []
+            return self._plan.forward_uint8(images, dev_lut, bits, layout), self.flops(), []
         from .data import expand_uint8
         return self.forward(expand_uint8(images, lut, layout), bit_config)
 

@@ -17,7 +17,8 @@
  *     AssertionError (layers_quant.py:437), P2V_E_UNSUPPORTED -> NotImplementedError (quantizer/base.py:28).
  *   - HIP graph capture (hipStreamBeginCapture on `stream`, torch.cuda.graph): an entry point that only launches kernels and
  *     hipMemsetAsync on `stream`, with every argument passed by value or pointing at memory that outlives the call, can be recorded and
- *     replayed: the whole-model forwards (p2v_forward, _u8, _taps, _linear_taps, p2v_forward_ddv / _ex / _ex2, p2v_forward_stats), p2v_run_ops
+ *     replayed: the whole-model forwards (p2v_forward, _u8, _taps, _linear_taps, p2v_forward_ddv / _ex / _ex2, p2v_forward_stats; p2v_forward_many / _many_u8, whose
+ *     device-to-device copies on `stream` are recorded with the launches), p2v_run_ops
  *     and every per-operator entry point not named below.  HOST arguments (bit_config, the p2v_op table, tap pointer arrays, p2v_* structs)
  *     are read when the call is made, i.e. baked into the graph.  The entry points that copy from host memory of their own, read results
  *     back, allocate, or time with events cannot be recorded - a capture records work, it does not run it - and return
@@ -1165,6 +1166,43 @@ size_t p2v_hutchinson_state_bytes(int n_segs);
 int p2v_hutchinson_init(void* state, size_t state_bytes, int n_segs, void* stream);
 int p2v_hutchinson_step(const p2v_seg2* segs, int n_segs, int probe, int max_iter, double tol, double* record, void* state,
                         size_t state_bytes, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Many bit lists in one call (additive: no structure, existing entry point or P2V_ABI_VERSION changes; found by their symbols) --------
+ * p2v_forward for n_lists bit lists over the same images, sharing what the lists have in common.  bit_configs: HOST int8
+ * [n_lists][n_cfg], read when the call is made; logits: dev fp32 [n_lists][batch][classes].  logits[l] is byte-equal to what
+ * p2v_forward(plan, images, batch, bit_configs[l], ..., stop_after = -1) writes, for every l in the caller's order, repeated lists
+ * included (computed once, their logits copied).
+ *
+ * Between the blocks of the forward only the residual stream "x" (int8 [batch * tokens][embed_dim]) carries state, and the engine is
+ * integer-exact, so a forward resumed from a saved x equals a fresh one.  The lists form a prefix tree of depth + 2 levels: level 0 is
+ * keyed by the stem's entry cfg[0], level 1 + i by the four entries of block i, the tail runs the final norm once per distinct block
+ * prefix and one head GEMM per distinct cfg[n_cfg - 1] under it.  The tree is walked depth first, children in order of first appearance
+ * in the caller's array; every node's launches run once.  A node with c > 1 children saves x once into the snapshot slot of its depth
+ * (hipMemcpyAsync device to device on `stream`, batch * tokens * embed_dim bytes) and restores it in front of children 2 ... c.  The root
+ * needs none (the stem writes every row of x), nor does the tail (it writes none).  The class-row shortcut of the last block ("cls_rows")
+ * applies as in p2v_forward: it writes the class rows of x, which the restore puts back.
+ *
+ * Workspace: p2v_forward_many_bytes = p2v_workspace_bytes(plan, batch) plus `snapshots` slots of x, each rounded up to 256 bytes;
+ * snapshots = the largest number of branching nodes on one root-to-leaf path (0: refused).  Nothing outside [ws, ws + bytes) and logits
+ * is written.  No allocation, synchronisation or read-back: both calls can be recorded into a HIP graph (kernels and device-to-device
+ * copies on `stream`).  A plan with float operators (p2v_plan_set_float_ops) runs as in p2v_forward.
+ *
+ * p2v_forward_many_plan is the same walk with nothing enqueued and makes no HIP call; it needs the plan's geometry only.  It returns the
+ * numbers of stem runs, block runs, final norms, head GEMMs, copies of x (saves + restores) and snapshot slots; an output pointer may be
+ * NULL.  A loop of p2v_forward runs n_lists stems, n_lists * depth blocks, n_lists norms and heads.
+ *
+ * Refused before any HIP call, the message naming the entry point: P2V_E_ARG (null argument; the image checks of p2v_forward_u8),
+ * P2V_E_SHAPE (batch < 1, n_lists outside 1 ... P2V_MANY_MAX_LISTS), P2V_E_BITS (n_cfg is not the plan's, an entry not in {4, 8}),
+ * per list what p2v_forward refuses with the same status (P2V_E_STATE: a layer without weights of that width, an incomplete plan),
+ * P2V_E_WORKSPACE (ws_bytes < p2v_forward_many_bytes). */
+#define P2V_MANY_MAX_LISTS 4096
+int p2v_forward_many(p2v_plan* plan, const float* images, int batch, const int8_t* bit_configs, int n_lists, int n_cfg, float* logits,
+                     void* ws, size_t ws_bytes, void* stream);
+int p2v_forward_many_u8(p2v_plan* plan, const uint8_t* images, int layout, const void* lut, int batch, const int8_t* bit_configs,
+                        int n_lists, int n_cfg, float* logits, void* ws, size_t ws_bytes, void* stream);
+size_t p2v_forward_many_bytes(const p2v_plan* plan, int batch, const int8_t* bit_configs, int n_lists, int n_cfg);
+int p2v_forward_many_plan(const p2v_plan* plan, const int8_t* bit_configs, int n_lists, int n_cfg, int* stems, int* blocks, int* norms,
+                          int* heads, int* copies, int* snapshots);
 
 const char* p2v_last_error(void);
 int p2v_abi_version(void);
